@@ -2,6 +2,7 @@
 """Throughput bench of the CEM-projection optimizer hot path (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload mmd_opt|cvar|dynamic|configs0]
+                    [--dump-outputs DIR] [--full]
 
 One step = one outer CEM iteration (cem.py:221-315 body: initial guess,
 projection, controls, noisy rollouts, risk reducer (beta-CEM for mmd_opt),
@@ -17,7 +18,13 @@ configuration (config k = rank, seeded like S/main_mpc.py:12,114), so per-GPU
 work is fixed ("scaling": "weak"); RCCL is used for the barrier, the max of
 the elapsed times and the final gather of the per-config results (§8e).
 
-Extra fields: "roofline" for the dominant kernel (HIP-event durations of the
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR then writes what the solve of the last timed step returns
+(mpcmmd_finish after that step: cx, cy, cost_lane, cost_obs, sigma, res_beta,
+beta) as DIR/<name>.npy in float32; the inputs and the Philox seed are fixed
+by the arguments, so two builds can be compared output for output.
+
+--full adds: "roofline" for the dominant kernel (HIP-event durations of the
 library's launches on its stream, during a profiled pass of the same steps),
 "cpu_baseline" (the NumPy oracle on a bounded sample of the same workload,
 rank 0, N = 1 only) and, at N = 1, "extra_workloads": the other BASELINE
@@ -311,9 +318,10 @@ def cpu_baseline(w, inst, seconds):
                        f"({t_risk:.1f} s) scaled x{B / c:.1f}; BLAS threads {threads}")}
 
 
-def run_workload(name, steps, warmup, profile_steps, rank, world, local, dist=None):
+def run_workload(name, steps, warmup, profile_steps, rank, world, local, dist=None, full=True):
     """Time `steps` steps of workload `name` on this rank's GPU.  Returns the
-    timing record (rank-local elapsed time; the caller max-reduces it)."""
+    timing record (rank-local elapsed time; the caller max-reduces it).
+    full: also run the profiled pass (per-kernel times and the roofline)."""
     import torch
     from optimizer import _native
 
@@ -352,6 +360,9 @@ def run_workload(name, steps, warmup, profile_steps, rank, world, local, dist=No
     elapsed = time.perf_counter() - t0
     step_ms = np.array([evs[i].elapsed_time(evs[i + 1]) for i in range(steps)])
     res = h.finish()
+    if not full:
+        h.close()
+        return dict(w=w, elapsed=elapsed, step_ms=step_ms, res=res, inst=inst)
     # profiled pass (same steps, HIP events around every launch on the library's stream)
     h.write("stats", np.zeros(8, np.uint64))
     h.profile(True)
@@ -411,7 +422,7 @@ def _carla_modules():
     return importlib.import_module(name + ".cem"), rep
 
 
-def run_carla(ticks, warmup, local, n=None):
+def run_carla(ticks, warmup, local, n=None, dump=None):
     """Per-tick time of the CARLA loop body on replayed ticks
     (carla/main_carla.py:345-382): the path / obstacle preprocessing through
     the drop-in's helpers, then the solve.  The reference's driver runs ONE
@@ -453,6 +464,10 @@ def run_carla(ticks, warmup, local, n=None):
         means["mmd_opt"], means["cvar"], means["det"] = r1[4], r2[4], r3[4]
         if i >= warmup:
             rows.append((t1 - t0, t2 - t1, t3 - t2, t3 - t0, t4 - t3))
+    if dump is not None:  # the last timed tick's result tuples
+        names = ("cx", "cy", "v_best", "steering", "mean_param")
+        dump_outputs(dump, {f"{c}_{nm}": v for c, r in (("mmd", r1), ("cvar", r2), ("det", r3))
+                            for nm, v in zip(names, r)})
     torch.cuda.synchronize()
     a = np.array(rows) * 1e3
     # one profiled tick: per-kernel HIP-event times of both solves
@@ -508,15 +523,30 @@ def run_carla(ticks, warmup, local, n=None):
             "launches_per_tick": int(sum(v[0] for v in kt.values()))}
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array of `arrays` as <path>/<name>.npy in float32
+    (float64 stays float64)."""
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        np.save(os.path.join(path, f"{name}.npy"), v if v.dtype == np.float64 else v.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="mmd_opt", choices=sorted(WORKLOADS) + ["carla"])
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget (0 = skip)")
-    ap.add_argument("--profile-steps", type=int, default=20)
-    ap.add_argument("--extra", type=int, default=1, help="N = 1: also time the other BASELINE workloads (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the profiled pass (roofline, per-kernel times), the CPU baseline and, at N = 1, the "
+                         "other BASELINE workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step's solve returns as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: CPU baseline budget (0 = skip)")
+    ap.add_argument("--profile-steps", type=int, default=20, help="--full: steps of the profiled pass")
+    ap.add_argument("--extra", type=int, default=1,
+                    help="--full, N = 1: also time the other BASELINE workloads (0 = skip)")
     ap.add_argument("--carla-n", type=int, default=10, help="--workload carla: num_reduced_set (10 or 22)")
     a = ap.parse_args()
 
@@ -531,11 +561,12 @@ def main():
     torch.cuda.set_device(local)
     if a.workload == "carla":  # configs[4] alone (one GPU, a real-time tick loop: no sharding)
         print(json.dumps({"metric": "CARLA ticks/s (one compute_cem_* per tick, main_carla.py:188-194)",
-                          **run_carla(a.steps, a.warmup, local, n=a.carla_n)}), flush=True)
+                          **run_carla(a.steps, a.warmup, local, n=a.carla_n, dump=a.dump_outputs)}), flush=True)
         return
     if world > 1:
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    r = run_workload(a.workload, a.steps, a.warmup, a.profile_steps, rank, world, local, dist if world > 1 else None)
+    r = run_workload(a.workload, a.steps, a.warmup, a.profile_steps, rank, world, local, dist if world > 1 else None,
+                     full=a.full)
     elapsed = r["elapsed"]
     res = r["res"]
     if world > 1:
@@ -572,13 +603,16 @@ def main():
                                             if w["cost"] == "mmd_opt" else
                                             "KKT / basis products, projection transcendentals, Beta sampling: fp64")},
             "median_ms_per_step": float(np.median(r["step_ms"])),
-            "roofline": r["roof"],
-            "kernels_ms_per_step": r["kernels"],
             "results_gathered": int(gathered.shape[0]),
         }
-        if world == 1 and a.cpu_seconds > 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, res)
+        if a.full:
+            line["roofline"] = r["roof"]
+            line["kernels_ms_per_step"] = r["kernels"]
+        if a.full and world == 1 and a.cpu_seconds > 0:
             line["cpu_baseline"] = cpu_baseline(w, r["inst"], a.cpu_seconds)
-        if world == 1 and a.extra:
+        if a.full and world == 1 and a.extra:
             extra = {}
             for name in WORKLOADS:
                 if name == a.workload:

@@ -50,7 +50,7 @@ for m in "${LIST[@]}"; do
       tag=${1:-round}
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 || exit 1
       run_tests || exit 1
-      run_bench "default_$tag" || exit 1
+      run_bench "default_$tag" --full || exit 1
       MPCMMD_GROUPS=1 bash tools/prof.sh "$tag" --extra 0 || exit 1 ;;
     *) echo "unknown mode $m"; exit 2 ;;
   esac

@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 TAG=$1
 ( set -o pipefail
-  bash tools/gpu.sh bench default_$TAG && \
+  bash tools/gpu.sh bench default_$TAG --full && \
   MPCMMD_GROUPS=1 bash tools/prof.sh $TAG --extra 0 && \
   MPCMMD_GROUPS=1 bash tools/prof.sh ${TAG}_cvar --workload cvar && \
   mkdir -p gpurun_out/kt_carla_$TAG && \
