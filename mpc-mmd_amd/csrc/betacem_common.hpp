@@ -1,0 +1,241 @@
+// Stage "risk" for cost = mmd_opt: the mother rollouts, their Bernstein fit
+// and the nested beta-CEM that picks the reduced set and the MMD weights,
+// then the reduced-set MMD.  Per outer iteration:
+//
+//   k_mother    noisy control rows, n^2 mother rollouts (Cartesian product,
+//               cem_helper.py:469-530) with the ridge fit folded into the scan
+//               (compute_coeff, cem_helper.py:553-564) -> 22 features per row
+//   k_bdist     the M x M L1 distance matrix of the features (once)
+//   20 x { k_bsample  new samples of the beta-CEM (compute_beta.py:51-68)
+//          k_bselect  top-n |beta| rows and sigma per sample (compute_beta.py:41-49, 117-118)
+//          k_bkernel  Laplace-kernel row sums over the mother set and K_red
+//                     (kernel_computation.py:19-65, compute_beta.py:120-127)
+//          k_bqp      the equality-constrained QP and its cost per sample
+//                     (compute_beta.py:70-91, 129)
+//          k_belite   elite 11, mean, structured Cholesky of
+//                     cov = D D^T / 10 + 0.05 I, next generators (compute_beta.py:51-68, 133-145) }
+//   k_mmdfinal  reduced-set rollouts, collision residual, MMD obs / lane
+//               (costs.py:121-135, 173-186)
+//
+// The beta-iteration kernels work on a candidate range [p.b0, p.b0 + p.nb):
+// the host splits the batch into groups, each on its own stream, so the
+// kernels of different groups (bound by different units: MFMA, exp, fp64
+// FMA latency, LDS) run side by side.  Every supported size n <= 64
+// (M = n^2 <= 4096) takes the same kernels; the LDS-resident pieces are sized
+// at launch (ker_lds, dir_lds, elite_lds).
+//
+// The covariance of the beta-CEM is rank <= 10 plus 0.05 I
+// (jnp.cov of 11 elites, compute_beta.py:61).  Its Cholesky factor is never
+// formed: with U = (E - mean)^T / sqrt(10), Phi_j = I + U_{<j}^T U_{<j} / d,
+// v_j = Phi_j^-1 u_j, L_jj = sqrt(d + u_j.v_j), w_j = v_j / L_jj, one has
+// L_ij = u_i . w_j (i > j), so (L z)_i = L_ii z_i + u_i . sum_{j<i} w_j z_j.
+// Same factor as chol(cov) in exact arithmetic, O(M r^2) instead of O(M^3).
+//
+// This header: what every beta-CEM file shares (the thread index, sizes,
+// small wave / quad helpers, launch sizing, the LDS layouts).  The phase
+// bodies that both the per-iteration kernels and the fused k_bcem_small run
+// are in betacem_{sample,select,kernel,qp,elite}.hpp; the kernels and their
+// launchers in k_mother, k_bdist, k_bsample, k_bkernel, k_bqp, k_belite and
+// k_bcem_small.hip.
+#pragma once
+#include "block.hpp"
+#include "kernels.hpp"
+
+namespace mpcmmd {
+
+namespace {
+
+// The thread's index.  The small-batch fused kernel (k_bcem_small.hip, which
+// alone defines MPCMMD_OPAQUE_TIDX before its includes) runs every phase
+// inside one loop over the beta-iterations; there each read is opaque, so
+// nothing computed from the index is hoisted out of the loop and held in
+// registers across the other phases (spills).  The per-iteration kernels read
+// threadIdx.x.  This is the one thing that differs between the phase bodies
+// as the fused kernel and as the per-iteration kernels compile them.
+#ifdef MPCMMD_OPAQUE_TIDX
+DEVI unsigned tidx() {
+  unsigned t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  return t;
+}
+#else
+DEVI unsigned tidx() { return threadIdx.x; }
+#endif
+
+constexpr int kF = 22;                               // features: cx (11) | cy (11)
+constexpr int kNew = kBetaSamples - kBetaElite;      // 89 resampled rows per iteration
+constexpr int kThreads = 512;
+constexpr double kSqrt20 = 4.47213595499957927704;   // chol(20 I) (compute_beta.py:24)
+constexpr double kRidge = 0.05;                      // cov jitter (compute_beta.py:61)
+constexpr double kInvRidge = 20.0;
+
+// first sample a beta-iteration processes: from the second iteration on,
+// samples 0..10 are the previous iteration's elites, unchanged, and k_belite
+// carries their top-n rows, sigma, QP solution and cost
+HDI int first_sample(int tb) { return tb > 0 ? kBetaElite : 0; }
+
+#define kconst __attribute__((address_space(4)))
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+// Intra-wave LDS hand-off: a wave's LDS operations execute in order, so only
+// the compiler must be kept from reordering them (no memory-counter waits).
+DEVI void wave_sync() {
+  __builtin_amdgcn_wave_barrier();
+  __asm__ volatile("" ::: "memory");
+}
+
+// sum over each row of 16 lanes (every lane of the row holds it)
+DEVI double row16_sum(double v) {
+  v += dpp_d<0xB1>(v);
+  v += dpp_d<0x4E>(v);
+  v += dpp_d<0x124>(v);
+  return v + dpp_d<0x128>(v);
+}
+
+// fp64 MFMA (v_mfma_f64_16x16x4_f64; layouts: betacem_sample.hpp)
+typedef double d4 __attribute__((ext_vector_type(4)));
+DEVI d4 mfma64(double a, double b, d4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+
+// value of quad lane l (0..3) in every lane of the quad; l is a constant
+// after unrolling, so the switch folds
+DEVI float quad_bcast(float v, int l) {
+  const int b = __float_as_int(v);
+  switch (l & 3) {
+    case 0: return __int_as_float(dpp_full<0x00>(b));
+    case 1: return __int_as_float(dpp_full<0x55>(b));
+    case 2: return __int_as_float(dpp_full<0xAA>(b));
+    default: return __int_as_float(dpp_full<0xFF>(b));
+  }
+}
+DEVI double quad_bcast(double v, int l) {
+  const long long b = __double_as_longlong(v);
+  int lo = int(b), hi = int(b >> 32);
+  switch (l & 3) {
+    case 0: lo = dpp_full<0x00>(lo), hi = dpp_full<0x00>(hi); break;
+    case 1: lo = dpp_full<0x55>(lo), hi = dpp_full<0x55>(hi); break;
+    case 2: lo = dpp_full<0xAA>(lo), hi = dpp_full<0xAA>(hi); break;
+    default: lo = dpp_full<0xFF>(lo), hi = dpp_full<0xFF>(hi); break;
+  }
+  return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned>(lo));
+}
+// sum over the quad, bit-identical in its 4 lanes
+DEVI float quad_sum(float v) {
+  v = v + __int_as_float(dpp_full<0xB1>(__float_as_int(v)));  // quad_perm(1,0,3,2)
+  return v + __int_as_float(dpp_full<0x4E>(__float_as_int(v)));  // quad_perm(2,3,0,1)
+}
+DEVI double quad_sum(double v) {
+  auto sw = [](double x, auto f) {
+    const long long b = __double_as_longlong(x);
+    return __longlong_as_double((static_cast<long long>(f(int(b >> 32))) << 32) | static_cast<unsigned>(f(int(b))));
+  };
+  v = v + sw(v, [](int x) { return dpp_full<0xB1>(x); });
+  return v + sw(v, [](int x) { return dpp_full<0x4E>(x); });
+}
+
+// launch sizing
+constexpr int kXcds = 8;   // workgroups are dealt round-robin to the 8 XCDs by linear id
+constexpr int kCUs = 256;  // MI355X compute units (launch sizing only)
+constexpr int kKerWaves = 16;  // waves per k_bkernel workgroup
+constexpr int kDirWaves = 4;   // waves per k_bdirect / k_bdirect_pairs workgroup
+constexpr int kLptBins = 128;  // pair counts per distinct row (<= 100 samples)
+// the series of a K_mixed row sum (k_bmoment's records, summed by k_bkernel)
+// covers a = R / sigma <= kSeriesAMax: k_bmoment's error bound holds for a <= 1
+constexpr double kSeriesAMax = 1.0;
+constexpr float kNegLog2e = -1.44269504088896340736f;
+constexpr size_t kLdsBudget = 160 * 1024 - 1024;
+
+struct LdsTake {  // consecutive 16-byte aligned LDS pieces
+  size_t o = 0;
+  HDI size_t operator()(size_t bytes) {
+    const size_t at = o;
+    o = (o + bytes + 15) & ~size_t(15);
+    return at;
+  }
+};
+
+// k_bkernel LDS.  persistent: sel (short; union ranks once the records are
+// staged), -log2 e / sigma, 1 / sigma, the entry table (k | kk << 8), union
+// rank of a row, row of a rank; scratch (`scratch` bytes, chosen at launch):
+// the union flags, then the union's series records, then the distance table
+// and the union's feature rows, or the waves' per-sample feature rows
+struct KerLds {
+  size_t sel, csg, csd, tri, urank, urow, misc, scratch, total;
+};
+HDI KerLds ker_lds(int M, int n, size_t scratch) {
+  KerLds L{};
+  LdsTake take;
+  L.sel = take(size_t(kBetaSamples) * n * 2);
+  L.csg = take(size_t(kBetaSamples) * 4);
+  L.csd = take(size_t(kBetaSamples) * 8);
+  L.tri = take(size_t(n) * (n - 1));
+  L.urank = take(size_t(M) * 2);
+  L.urow = take(size_t(M) * 2);
+  L.misc = take(32 * 4);  // [0] union rows, [1] series pairs, [2] direct pairs, [16..] wave totals
+  L.scratch = take(scratch);
+  L.total = take.o;
+  return L;
+}
+HDI size_t ker_sample_bytes(int n, int nw = kKerWaves) { return size_t(nw) * n * kFeatStride * 4; }
+HDI size_t ker_tab_bytes(int U) { return ((size_t(U) * (U - 1) / 2 * 4 + 15) & ~size_t(15)) + size_t(U) * kFeatStride * 4; }
+constexpr size_t kKerTabBytes = 55 * 1024;  // the table of a union of <= 144 rows
+// scratch: the series records of every mother row (up to kKerRecBytes;
+// larger unions read them from global memory), and the union table (up to
+// kKerTabBytes) from the second beta-iteration on (the first one's 100 fresh
+// samples select nearly every mother row)
+constexpr size_t kKerRecBytes = 64 * 1024;
+HDI size_t ker_scratch(int M, int n, int tb, int nw = kKerWaves) {
+  size_t sc = ker_sample_bytes(n, nw);
+  size_t rec = size_t(M) * kMomStride * 4;
+  if (rec > kKerRecBytes) rec = kKerRecBytes;
+  if (rec > sc) sc = rec;
+  if (tb > 0 && kKerTabBytes > sc) sc = kKerTabBytes;
+  return sc;
+}
+
+// k_bdirect LDS.  persistent: sel (short), -log2 e / sigma, the direct pairs
+// sorted by row, the distinct direct rows and their first pair, the grab
+// order; scratch: the setup's counts / fill / scan (10 M bytes)
+struct DirLds {
+  size_t sel, csg, pairs, ulist, ustart, order, bins, misc, scratch, total;
+};
+HDI DirLds dir_lds(int M, int n) {
+  DirLds L{};
+  LdsTake take;
+  L.sel = take(size_t(kBetaSamples) * n * 2);
+  L.csg = take(size_t(kBetaSamples) * 4);
+  L.pairs = take(size_t(kBetaSamples) * n * 2);
+  L.ulist = take(size_t(M) * 2);
+  L.ustart = take(size_t(M + 1) * 2);
+  L.order = take(size_t(M) * 2);
+  L.bins = take(kLptBins * 4);
+  L.misc = take(32 * 4);  // [0] next row, [1] distinct rows, [16..] wave totals
+  L.scratch = take(size_t(M) * 10);
+  L.total = take.o;
+  return L;
+}
+
+// k_belite LDS: the block sums (nblk x 66 fp64), small bookkeeping, the
+// carried elite rows and a 16-position u staging per wave
+struct EliteLds {
+  size_t Gb, misc, carry, ublk, total;
+};
+constexpr int kUPitch = 12;  // doubles per position row of the per-wave u staging
+HDI EliteLds elite_lds(int M1, int waves = kThreads / 64) {
+  EliteLds L{};
+  const int nblk = (M1 + 15) / 16;
+  L.Gb = 0;
+  L.misc = (size_t(nblk) * 66 * 8 + 15) & ~size_t(15);
+  L.carry = L.misc + 1024;
+  L.ublk = (L.carry + size_t(kBetaElite) * (2 * kMaxReduced + 2) * 4 + 15) & ~size_t(15);
+  L.total = L.ublk + size_t(waves) * 16 * kUPitch * 8;  // one 16-position block per wave
+  return L;
+}
+
+// the fused kernel's sampler: an LDS copy of the candidate's generators and
+// every block's T (betacem_sample.hpp: bsample_tblocks)
+HDI size_t gen_lds_bytes(int M) { return size_t(pos_pad(M)) * (2 * kGenRow + 1) * 8 + 16 * 8; }  // + wA's overreach
+HDI size_t tblk_lds_bytes(int M) { return size_t(pos_pad(M) >> 4) * 4 * 64 * 8; }
+
+}  // namespace
+
+}  // namespace mpcmmd

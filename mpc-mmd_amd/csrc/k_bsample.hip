@@ -1,0 +1,231 @@
+// k_bsample, k_bsample_chunks, k_bsel0, k_bselect: a beta-iteration's new
+// samples and their top-n selection (betacem_common.hpp has the pipeline).
+#include <algorithm>
+
+#include "betacem_sample.hpp"
+#include "betacem_select.hpp"
+
+namespace mpcmmd {
+
+namespace {
+
+// The first beta-iteration's selection from the handle's table (Params::sel0,
+// sig0: k_bselect's output for the shared initial samples, computed once per
+// table) into every candidate's bsel / bsig.
+__global__ __launch_bounds__(256) void k_bsel0(Params p) {
+  const int n = p.n, per = kBetaSamples * n + kBetaSamples;
+  for (size_t x = size_t(blockIdx.x) * 256 + tidx(); x < size_t(p.nb) * per; x += size_t(gridDim.x) * 256) {
+    const int c = int(x / per), e = int(x - size_t(c) * per), b = p.b0 + c;
+    if (e < kBetaSamples * n)
+      p.bsel[size_t(b) * kBetaSamples * n + e] = p.sel0[e];
+    else
+      p.bsig[size_t(b) * kBetaSamples + e - kBetaSamples * n] = p.sig0[e - kBetaSamples * n];
+  }
+}
+
+template <int TPW>
+__global__ __launch_bounds__(64 * sample_waves<TPW>()) void k_bsample(Params p, int tb) {
+  const int b = p.b0 + blockIdx.x, M = p.M, Pp = pos_pad(M);
+  const int lane = tidx() & 63, w = tidx() >> 6;
+  const int r = lane & 15, h = lane >> 4;
+  const int s0 = w * TPW * 16;
+  MPCMMD_STAMP(p, 0);
+  const double* G = p.gen + size_t(b) * Pp * kGenStride;
+  const double* gm = p.genm + size_t(b) * Pp;
+  const float* z = p.beta_z + size_t(tb - 1) * Pp * kBzCols;
+  const int ys = ygen_stride(M);
+  float* plane = p.ygen + size_t(b) * kBzCols * ys;
+  d4 S[TPW], Sp[TPW], Ya[TPW], Yb[TPW];
+#pragma unroll
+  for (int t = 0; t < TPW; ++t) {
+    S[t] = Sp[t] = d4{0.0, 0.0, 0.0, 0.0};
+    Sp[t][2] = h == 3 ? 1.0 : 0.0;  // row 11 of S_pre: the mean's coefficient
+  }
+  const int nblk = Pp >> 4, cl = sample_chunk(nblk);
+  const __amdgpu_buffer_rsrc_t yr = ygen_rsrc(plane, ys);
+  const int vl = (2 * h * ys + r) * 4, v43 = h == 0 ? vl : kDropOffset;
+  auto store = [&](const d4* Yv, int q0) {
+    if (TPW == kSampleTiles && q0 + 15 < M)  // block-uniform
+      block_store_rows(Yv, yr, q0, ys, vl, v43);
+    else
+      block_store<TPW>(Yv, plane, q0, M, ys, s0, r, h);
+  };
+  // blocks in pairs, operands and outputs ping-ponged: the next block's loads
+  // are in flight and its MFMAs issued while the previous block's samples
+  // are converted and stored (the last prefetch re-reads a block; nblk and
+  // the chunk length are even; sched barriers keep that order)
+  SampleBlock<TPW> qa, qb;
+  const SampleRsrc srs = sample_rsrc(G, gm, z, Pp, r, h);
+  auto load = [&](SampleBlock<TPW>& q, int q0) {
+    if constexpr (TPW == kSampleTiles)
+      load_block_buf(q, srs, q0);
+    else
+      load_block(q, G, G + gen_uplane(Pp), gm, z, q0, s0, r, h);
+  };
+  load(qa, 0);
+  for (int c = 0; c < nblk; c += 2) {
+    const int p0 = c << 4;
+    load(qb, p0 + 16);
+    __builtin_amdgcn_sched_barrier(0);
+    block_mfma(qa, S, Sp, Ya, r, h);
+    __builtin_amdgcn_sched_barrier(0);
+    if (c > 0) store(Yb, p0 - 16);
+    __builtin_amdgcn_sched_barrier(0);
+    load(qa, min(p0 + 32, Pp - 16));
+    __builtin_amdgcn_sched_barrier(0);
+    block_mfma(qb, S, Sp, Yb, r, h);
+    if ((c + 2) % cl == 0)
+#pragma unroll
+      for (int t = 0; t < TPW; ++t) fold_chunk(Sp[t], S[t]);
+    __builtin_amdgcn_sched_barrier(0);
+    store(Ya, p0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  store(Yb, Pp - 16);
+  MPCMMD_STAMP(p, 1);
+}
+
+// k_bsample_chunks: the samples of k_bsample for small batches, workgroup =
+// (candidate, tile of 16 samples), one wave per chunk of blocks.  Phase 1:
+// each wave but the last sums W^T Z over its chunk (the MFMAs of the walker's
+// S_loc, from zero) into LDS; phase 2: S_pre = the earlier chunks' sums in
+// order (the walker's folds), then the chunk's blocks as in k_bsample.
+__global__ __launch_bounds__(64 * kChunkWavesMax) void k_bsample_chunks(Params p, int tb) {
+  __shared__ double dS[kChunkWavesMax - 1][3][64];
+  const int b = p.b0 + blockIdx.x, M = p.M, Pp = pos_pad(M), nblk = Pp >> 4;
+  const int lane = tidx() & 63, k = tidx() >> 6, P = blockDim.x >> 6;
+  const int r = lane & 15, h = lane >> 4, s0 = blockIdx.y * 16;
+  const int cl = sample_chunk(nblk), c0 = k * cl, c1 = min(nblk, c0 + cl);
+  MPCMMD_STAMP(p, 0);
+  const double* G = p.gen + size_t(b) * Pp * kGenStride;
+  const double* gm = p.genm + size_t(b) * Pp;
+  const float* z = p.beta_z + size_t(tb - 1) * Pp * kBzCols;
+  const int ys = ygen_stride(M);
+  float* plane = p.ygen + size_t(b) * kBzCols * ys;
+  if (k < P - 1) {
+    // operands of W^T Z for block c: W[p0 + 4 kk + h][r], Z[p0 + 4 kk + h][s0 + r]
+    auto ld = [&](double (&wa)[4], double (&zz)[4], int c) {
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        const size_t pos = size_t(c) * 16 + 4 * kk + h;
+        wa[kk] = G[pos * kGenRow + kGenW + r];
+        zz[kk] = double(z[bz_index(int(pos), s0 + r)]);
+      }
+    };
+    d4 Sl = d4{0.0, 0.0, 0.0, 0.0};
+    double wa[4], zz[4], wn[4], zn[4];
+    ld(wa, zz, c0);
+    for (int c = c0; c < c1; ++c) {
+      ld(wn, zn, min(c + 1, c1 - 1));
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) Sl = mfma64(wa[kk], zz[kk], Sl);
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        wa[kk] = wn[kk];
+        zz[kk] = zn[kk];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) dS[k][i][lane] = Sl[i];
+  }
+  __syncthreads();
+  d4 S[1] = {d4{0.0, 0.0, 0.0, 0.0}}, Sp[1] = {d4{0.0, 0.0, 0.0, 0.0}}, Ya[1], Yb[1];
+  Sp[0][2] = h == 3 ? 1.0 : 0.0;  // row 11 of S_pre: the mean's coefficient (the chunks' row 11 sums are 0)
+  for (int j = 0; j < k; ++j)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) Sp[0][i] = Sp[0][i] + dS[j][i][lane];
+  SampleBlock<1> qa, qb;
+  const int pend = c1 << 4;
+  load_block(qa, G, G + gen_uplane(Pp), gm, z, c0 << 4, s0, r, h);
+  for (int c = c0; c < c1; c += 2) {
+    const int p0 = c << 4;
+    load_block(qb, G, G + gen_uplane(Pp), gm, z, p0 + 16, s0, r, h);
+    __builtin_amdgcn_sched_barrier(0);
+    block_mfma(qa, S, Sp, Ya, r, h);
+    __builtin_amdgcn_sched_barrier(0);
+    if (c > c0) block_store<1>(Yb, plane, p0 - 16, M, ys, s0, r, h);
+    __builtin_amdgcn_sched_barrier(0);
+    load_block(qa, G, G + gen_uplane(Pp), gm, z, min(p0 + 32, pend - 16), s0, r, h);
+    __builtin_amdgcn_sched_barrier(0);
+    block_mfma(qb, S, Sp, Yb, r, h);
+    __builtin_amdgcn_sched_barrier(0);
+    block_store<1>(Ya, plane, p0, M, ys, s0, r, h);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  block_store<1>(Yb, plane, pend - 16, M, ys, s0, r, h);
+  MPCMMD_STAMP(p, 1);
+}
+
+template <int NQ, int R, int G>
+__global__ __launch_bounds__(64) void k_bselect(Params p, int tb) {
+  __shared__ __attribute__((aligned(16))) unsigned long long cand[64 * R + 8];
+  __shared__ __attribute__((aligned(16))) uint32_t lm[64];
+  __shared__ int scratch[128];
+  // this beta-iteration's direct-pair list starts empty (k_bkernel appends)
+  if (blockIdx.y == 0 && tidx() == 0) p.bdlcount[size_t(p.b0 + blockIdx.x) * kBetaIters + tb] = 0;
+  bselect_wave<NQ, R, G>(p, tb, p.b0 + blockIdx.x, blockIdx.y, gridDim.y, cand, lm, scratch);
+}
+
+}  // namespace
+
+void launch_bsample(const Params& p, int tb, hipStream_t s) {
+  // one wave per candidate when the launch alone holds >= ~half a wave per
+  // SIMD; smaller batches one wave per (candidate, tile, chunk)
+  if (p.nb >= 384) {
+    hipLaunchKernelGGL((k_bsample<6>), dim3(p.nb), dim3(64 * sample_waves<6>()), 0, s, p, tb);
+  } else {
+    const int nblk = pos_pad(p.M) >> 4, cl = sample_chunk(nblk);
+    hipLaunchKernelGGL(k_bsample_chunks, dim3(p.nb, kSampleTiles), dim3(64 * ((nblk + cl - 1) / cl)), 0, s, p, tb);
+  }
+}
+
+void launch_bsel0(const Params& p, hipStream_t s) {
+  const size_t total = size_t(p.nb) * (kBetaSamples * p.n + kBetaSamples);
+  hipLaunchKernelGGL(k_bsel0, dim3(unsigned(std::min<size_t>((total + 255) / 256, 4096))), dim3(256), 0, s, p);
+}
+
+// waves per candidate: ~16 single-wave workgroups per SIMD over the launch,
+// at most 16 per candidate (B = 1024: 8 -> 16 measured -8.5%; the 512-candidate
+// groups of the two-stream split: 25 -> 16 +1%); small launches (nb <= 128:
+// up to Params::sel_cap waves per candidate -- CARLA n = 22, B = 100: 16 -> 64
+// took 1.5 ms off a 49.5 ms solve)
+int sel_waves(int nb, int cap) { return std::max(4, std::min(nb <= 128 ? cap : 16, 16384 / std::max(1, nb))); }
+
+template <int NQ>
+void launch_bselect_q(const Params& p, int tb, hipStream_t s) {
+  const dim3 grid(p.nb, sel_waves(p.nb, p.sel_cap));
+  if (p.n <= 24)
+    hipLaunchKernelGGL((k_bselect<NQ, 1, 32>), grid, dim3(64), 0, s, p, tb);
+  else if (p.n <= 48)
+    hipLaunchKernelGGL((k_bselect<NQ, 2, 64>), grid, dim3(64), 0, s, p, tb);
+  else
+    hipLaunchKernelGGL((k_bselect<NQ, 2, 0>), grid, dim3(64), 0, s, p, tb);
+}
+
+void launch_bselect(const Params& p, int tb, hipStream_t s) {
+  const int nq = (p.M + 63) >> 6;
+  switch (nq) {
+#define MPCMMD_SEL_CASE(q) \
+  case q:                  \
+    return launch_bselect_q<q>(p, tb, s);
+    MPCMMD_SEL_CASE(1)
+    MPCMMD_SEL_CASE(2)
+    MPCMMD_SEL_CASE(4)
+    MPCMMD_SEL_CASE(8)
+    MPCMMD_SEL_CASE(16)
+#undef MPCMMD_SEL_CASE
+    default:
+      break;
+  }
+  if (nq <= 4) return launch_bselect_q<4>(p, tb, s);
+  if (nq <= 8) return launch_bselect_q<8>(p, tb, s);
+  if (nq <= 12) return launch_bselect_q<12>(p, tb, s);
+  if (nq <= 16) return launch_bselect_q<16>(p, tb, s);
+  if (nq <= 24) return launch_bselect_q<24>(p, tb, s);
+  if (nq <= 32) return launch_bselect_q<32>(p, tb, s);
+  if (nq <= 40) return launch_bselect_q<40>(p, tb, s);
+  if (nq <= 48) return launch_bselect_q<48>(p, tb, s);
+  return launch_bselect_q<64>(p, tb, s);
+}
+
+}  // namespace mpcmmd

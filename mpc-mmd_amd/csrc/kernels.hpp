@@ -105,9 +105,9 @@ struct Params {
   int32_t* bdlcount;       // [Bt][20] their count per beta-iteration (zeroed by k_bselect of that iteration)
   int32_t dir_pairs;       // 1: k_bdirect_pairs (a wave per 8 listed pairs); 0: k_bdirect (rows sorted in LDS)
   int32_t qp_small;        // k_bqp at 64 threads (16 QPs) per workgroup for launches of < 2 workgroups per CU
-  int32_t sel_cap;         // k_bselect: at most this many single-wave workgroups per candidate (default 16)
+  int32_t sel_cap;         // k_bselect: at most this many single-wave workgroups per candidate (default 64)
   int32_t dir_waves;       // waves per k_bdirect workgroup (4, 8 or 16)
-  int32_t ker_target;      // k_bkernel parts: enough for this many workgroups per launch (default 512)
+  int32_t ker_target;      // k_bkernel parts: enough for this many workgroups per launch (default 128)
   int32_t dir_target;      // k_bdirect parts: enough for this many workgroups per launch (default 2048)
   int32_t mom_rows;        // 1 (default): k_bmoment_rows (16 lanes per distance row, 4 rows per wave); 0: a wave
                            // per row (MPCMMD_MOM_ROWS=0)

@@ -2,7 +2,7 @@
 """Per-kernel instruction statistics of a HIP source's gfx950 assembly:
 global loads, vmcnt(0) waits (serialised loads show as one wait per load),
 branches, DPP moves, fp64 / MFMA counts.
-    python tools/isa_stats.py mpc-mmd_amd/csrc/k_betacem.hip [name-filter]"""
+    python tools/isa_stats.py mpc-mmd_amd/csrc/k_bkernel.hip [name-filter]"""
 import re
 import subprocess
 import sys

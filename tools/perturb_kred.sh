@@ -1,11 +1,15 @@
 # Negative control for the beta-CEM parity tests (GPU box): build the library
-# with a deliberately wrong K_red entry (csrc/k_betacem.hip: kred_perturb) and
-# run the mmd_opt parity tests against it; they must FAIL.
+# with a deliberately wrong K_red entry (tools/exp_perturb_kred.patch adds
+# kred_perturb to csrc/betacem_kernel.hpp) and run the mmd_opt parity tests
+# against it; they must FAIL.
 #   bash tools/perturb_kred.sh 1   # entry 0 of every sample x 1.001  -> profiles/..._x1.001_tests.log
 #   bash tools/perturb_kred.sh 2   # mantissa bit 10 of entry 0 flipped -> ..._flip_tests.log
-# The build runs here (CPU container, make); the tests on the GPU box:
-#   make -C mpc-mmd_amd LIB=libmpcmmd_pk1.so BUILD=build_pk1 EXTRA=-DMPCMMD_PERTURB_KRED=1 -j8
-#   gpurun -- 'bash tools/perturb_kred.sh 1'
+# Apply the patch in a scratch copy, build there (CPU container, make), copy
+# the library here, run the tests on the GPU box:
+#   cp -r mpc-mmd_amd include tools /tmp/pk && (cd /tmp/pk && git apply tools/exp_perturb_kred.patch)
+#   make -C /tmp/pk/mpc-mmd_amd LIB=libmpcmmd_pk1.so BUILD=build_pk1 EXTRA=-DMPCMMD_PERTURB_KRED=1 -j8
+#   cp /tmp/pk/mpc-mmd_amd/libmpcmmd_pk1.so mpc-mmd_amd/
+#   bash tools/perturb_kred.sh 1
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mode=${1:-1}

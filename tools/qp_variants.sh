@@ -1,13 +1,19 @@
-# k_bqp LDS-conflict attribution.  Build (container):
+# k_bqp LDS-conflict attribution.  The variants are
+# tools/exp_qp_variant.patch (csrc/betacem_qp.hpp): apply the patch in a
+# scratch copy, build, run.  Build (container):
 #   bash tools/qp_variants.sh build      -> mpc-mmd_amd/libmpcmmd_qpV.so, V = 1 (no cost phase),
 #                                           2 (staging + row loads), 3 (staging only)
 # Measure (GPU box): bash tools/qp_variants.sh run   -> gpurun_out/qpv/*.csv + a table
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 if [ "$1" = build ]; then
+  W=$(mktemp -d)  # the patched copy; the product sources stay untouched
+  cp -r mpc-mmd_amd include tools "$W"/ && (cd "$W" && git apply tools/exp_qp_variant.patch) || exit 1
   for v in 1 2 3; do
-    make -C mpc-mmd_amd -j8 LIB=libmpcmmd_qp$v.so BUILD=build_qp$v EXTRA=-DMPCMMD_QP_VARIANT=$v > /dev/null || exit 1
+    make -C "$W"/mpc-mmd_amd -j8 LIB=libmpcmmd_qp$v.so BUILD=build_qp$v EXTRA=-DMPCMMD_QP_VARIANT=$v > /dev/null || exit 1
+    cp "$W"/mpc-mmd_amd/libmpcmmd_qp$v.so mpc-mmd_amd/
   done
+  rm -rf "$W"
   exit 0
 fi
 export TMPDIR=/tmp

@@ -1,11 +1,11 @@
 # Build an experiment variant of libmpcmmd.so from a patched copy of the
 # sources (the product sources stay untouched):
-#   bash tools/variant.sh TAG 'python-expression editing s (the text of k_betacem.hip etc.)' [file]
+#   bash tools/variant.sh TAG 'python-expression editing s (the text of the file)' [file]
 # -> mpc-mmd_amd/libmpcmmd_TAG.so  (compare with MPCMMD_LIB=... on the GPU box)
 set -e
 TAG=$1
 EXPR=$2
-FILE=${3:-k_betacem.hip}
+FILE=${3:-betacem_kernel.hpp}  # csrc/ file: a betacem_*.hpp phase header or a k_*.hip
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 W=/tmp/mpcmmd_variant_$TAG
 rm -rf $W && mkdir -p $W && cp -r $ROOT/mpc-mmd_amd $ROOT/include $W/
