@@ -24,8 +24,9 @@
 extern "C" {
 #endif
 
-/* 4: MPCMMD_COST_DET (CARLA compute_cem_det), mpcmmd_handle_info */
-#define MPCMMD_ABI_VERSION 4
+/* 4: MPCMMD_COST_DET (CARLA compute_cem_det), mpcmmd_handle_info
+ * 5: mpcmmd_validate_carla */
+#define MPCMMD_ABI_VERSION 5
 
 /* status codes */
 #define MPCMMD_OK 0
@@ -357,6 +358,73 @@ typedef struct mpcmmd_validate_args {
   int32_t* count_lane;    /* [num_cfg] out */
 } mpcmmd_validate_args;
 int mpcmmd_validate(const mpcmmd_validate_args* args);
+
+/* Monte-Carlo validation of CARLA plans on the GPU.  The reference measures
+ * CARLA safety with the live simulator's collision sensor only; this call
+ * evaluates the optimizer's own risk model instead -- the cvar risk stage of
+ * carla/optimizer/cem.py (noisy initial states, noisy rollouts in the global
+ * frame, closest-point Frenet transform, collision / lane bars) -- with
+ * num_rollouts fresh noise rows, reduced as validation.py:153-169 reduces
+ * (counts, not CVaR).  One configuration k is one simulator tick with one
+ * returned plan; num_cfg ticks run in one launch.  fp32 arithmetic with the
+ * fp64-evaluated transcendentals of the optimizer's CARLA rollouts.
+ *
+ * Per tick k (R = num_rollouts, H = num_prime, O = num_obs, P = num_path):
+ *   controls  acc[h] = (v[h+1] - v[h]) / 0.15f with v[100] = v[99], steer[h] as
+ *             given (the solve's v_best, steering_best); only h < H - 1 is used
+ *   rows      (x0 + (eps[r][0] sx + mx), y0 + (eps[r][1] sy + my), vx, vy,
+ *             atan2(vy, vx)) from init_state = init_state_global (x, y, v,
+ *             vdot, psi, psidot): the noisy initial rows of mpcmmd_carla_begin
+ *   noise     gaussian  acc + (sigma |acc|) n_a + acc_const n_c
+ *             beta      acc + sigma (2 b_a - 1) + acc_const n_c
+ *             steer likewise (beta: K_steer sigma), per (row, step)
+ *   rollout   the point recorded at h is the state before step h
+ *   counts    hit[o][r][h]  = !(f_bar(s, d, x_obs[o][h], y_obs[o][h]) <= 0) on
+ *                             the point's Frenet (s, d) against the tick's path
+ *             count_oh[o][h] = sum_r hit
+ *             count[k]       = max_{o,h} count_oh
+ *             count_rows[k]  = #{r : any hit}   (collision probability x R)
+ *             count_lane[k]  = max_h #(-d + y_lb > 0) + max_h #(d - y_ub > 0)
+ *
+ * draws [num_cfg][3][R][H] fp32 -- gaussian: the standard normals of acc,
+ * steer, const; beta: the two Beta variates and the const normals -- and
+ * init_eps [num_cfg][R][4] fp32 (columns 0, 1 used; mpcmmd_draws.init_eps'
+ * layout).  Either may be NULL: then the library's Philox streams keyed
+ * (keys[k], seed) are used, streams 32..34 (normals of acc, steer, const), 35..38
+ * (the gammas of Beta(2|acc|, 5|acc|) and Beta(2|steer|, 5|steer|): acc a, acc b,
+ * steer a, steer b; fp64 combine as the CARLA optimizer) and 39 (init_eps), element
+ * r H + h of the [R][H] tensors and r 4 + c of init_eps.
+ *
+ * Limits: 1 <= num_obs <= 32, 2 <= num_prime <= 100, 4 <= num_path <= 2048,
+ * num_rollouts >= 1 (num_rollouts * num_prime < 2^31), num_cfg <= 65535;
+ * variant one of the two MPCMMD_VARIANT_CARLA_*.  Anything else is
+ * MPCMMD_E_INVALID before any HIP call; num_cfg == 0 returns MPCMMD_OK without
+ * touching a device.  A shape whose workgroup does not fit the device's LDS
+ * is MPCMMD_E_UNSUPPORTED (never on an MI355X: the largest shape needs 130 KiB).
+ * Synchronous, needs no handle, allocates its own device buffers. */
+typedef struct mpcmmd_validate_carla_args {
+  int32_t num_cfg, num_obs, num_prime, num_rollouts, num_path;
+  int32_t noise;            /* MPCMMD_NOISE_* */
+  int32_t variant;          /* MPCMMD_VARIANT_CARLA_* (y_lb, y_ub) */
+  float noise_level, acc_const_noise, steer_const_noise;
+  uint32_t seed;
+  int32_t device;
+  const float* init_state;  /* [num_cfg][6] init_state_global */
+  const float* v;           /* [num_cfg][100] v_best */
+  const float* steer;       /* [num_cfg][100] steering_best */
+  const float* x_obs;       /* [num_cfg][num_obs][100] Frenet tracks */
+  const float* y_obs;
+  const float* path;        /* [num_cfg][6][num_path]: x_path, y_path, arc_vec, Fx_dot, Fy_dot, kappa */
+  const float* draws;       /* [num_cfg][3][R][H] or NULL */
+  const float* init_eps;    /* [num_cfg][R][4] or NULL */
+  const uint32_t* keys;     /* [num_cfg] */
+  int32_t* count;           /* [num_cfg] out */
+  int32_t* count_lane;      /* [num_cfg] out */
+  int32_t* count_rows;      /* [num_cfg] out */
+  int32_t* count_oh;        /* [num_cfg][num_obs][num_prime] out, or NULL (not copied) */
+  float* elapsed_ms;        /* out, or NULL: HIP-event time of the device work (counter reset + the two kernels) */
+} mpcmmd_validate_carla_args;
+int mpcmmd_validate_carla(const mpcmmd_validate_carla_args* args);
 
 #ifdef __cplusplus
 }

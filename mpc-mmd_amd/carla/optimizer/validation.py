@@ -1,0 +1,38 @@
+"""Monte-Carlo validation of CARLA plans on the GPU (``mpcmmd_validate_carla``,
+include/mpcmmd.h).
+
+The reference measures the safety of its CARLA runs with the live simulator's
+collision sensor only.  Without the simulator, the question the paper asks --
+which cost gives plans that collide less under the noise model -- is answered
+here by the optimizer's own risk model: for every simulator tick the returned
+plan (``v_best``, ``steering_best``) is rolled out ``num_rollouts`` times from
+fresh noisy initial states with fresh control noise, mapped to the tick's
+Frenet frame and compared with the obstacle ellipses and the lane bounds, and
+the hits are counted as ``synthetic_static_obs/validation.py:153-169`` counts
+them.  All ticks run in ONE launch.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from ._lib import native
+
+NUM_ROLLOUTS = 1000  # validation.py:173 (_num_batch)
+
+
+def validate_plans(prob, plans, num_rollouts=NUM_ROLLOUTS, draws=None, init_eps=None, seed=0, count_oh=False,
+                   timing=False):
+    """Counts of every plan of ``plans`` under ``prob``'s noise model.
+
+    prob: the CARLA ``CEM`` drop-in (town, noise, levels, H, O are taken from
+    it).  plans: per-tick dicts with ``init`` (init_state_global [6]), ``xo``,
+    ``yo`` (Frenet obstacle tracks [O, 100]), ``path`` (dict of the six path
+    arrays), ``v_best``, ``steering`` ([100], the solve's return) and ``key``
+    (the tick's Philox key, e.g. the tick index).  Returns the dict of
+    ``_native.validate_carla``: count, count_lane, count_rows [len(plans)]."""
+    N = native()
+    g = lambda name: [p[name] for p in plans]
+    return N.validate_carla(g("init"), g("v_best"), g("steering"), g("xo"), g("yo"), g("path"), g("key"),
+                            prob.num_prime, prob.noise, prob.sigma_acc, prob.acc_const_noise, prob.steer_const_noise,
+                            num_rollouts=num_rollouts, variant=prob.variant, draws=draws, init_eps=init_eps,
+                            seed=seed, device=prob._cfg.device, count_oh=count_oh, timing=timing)

@@ -1,0 +1,150 @@
+"""Monte-Carlo validation of a CARLA replay: which cost gives plans that
+collide less under the noise model, tick by tick.
+
+For a replay file (``replay.py``; or ``--synthetic TICKS``) and each cost of
+``--costs`` (``mmd``, ``cvar``, ``det``) the ticks of ``--ticks A B`` are solved
+one after the other as ``carla/main_carla.py:378-382`` does -- ``mean_param``
+carried from tick to tick, ``idx_mpc`` = the tick -- the returned plans
+(``v_best``, ``steering_best``) are collected, and all ticks of the cost are
+validated in ONE ``mpcmmd_validate_carla`` call (``optimizer/validation.py``:
+``num_rollouts`` noisy rollouts per plan against the tick's obstacles and lane
+bounds).  Per cost one ``validate_<cost>.npz`` is written with ``count``
+(max over (obstacle, step) of the rollouts in collision), ``count_rows``
+(rollouts with any collision: the plan's collision probability times R),
+``count_lane``, ``tick`` and ``num_rollouts``; and one line is printed with the
+share of ticks with ``count_rows > 0`` and the mean ``count_rows / R``.
+
+    cd mpc-mmd_amd/carla
+    python -m validate_replay --synthetic 200 --costs cvar det --ticks 40 120 --out stats
+
+The solver, the validator and the per-tick inputs are parameters of
+``validate_replay`` (``solve=``, ``validate=``, ``inputs=``), so the accounting
+is testable without a GPU.
+"""
+from __future__ import annotations
+
+import argparse
+import importlib
+import importlib.util
+import os
+import sys
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+COSTS = {"mmd": "compute_cem_mmd", "cvar": "compute_cem_cvar", "det": "compute_cem_det"}
+# main_carla.py:302-320: v_des = 10, mean (v_des x 4, y = 0 x 4), cov diag(20 x 4, 100 x 4)
+V_DES = 10.0
+MEAN = np.array([V_DES] * 4 + [0.0] * 4, np.float32)
+COV = np.diag([20.0] * 4 + [100.0] * 4).astype(np.float32)
+
+
+def _replay():
+    """replay.py of this directory (loaded by path: the module may itself be loaded by path)."""
+    name = "mpcmmd_carla_replay"
+    if name not in sys.modules:
+        spec = importlib.util.spec_from_file_location(name, os.path.join(_HERE, "replay.py"))
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules[name] = mod
+        spec.loader.exec_module(mod)
+    return sys.modules[name]
+
+
+def _solve(prob, cost, tick, init, mean, cov, xo, yo, v_des, path):
+    """func_cem of main_carla.py:188-194, 378-382."""
+    p = path
+    return getattr(prob, COSTS[cost])(tick, init, mean, cov, xo, yo, v_des, p["x_path"], p["y_path"], p["arc_vec"],
+                                      p["Fx_dot"], p["Fy_dot"], p["kappa"])
+
+
+def _inputs(rec, prob, tick):
+    return _replay().tick_inputs(rec, tick, prob.cem_helper, prob.num_obs)
+
+
+def _validate(prob, plans, num_rollouts, seed):
+    # optimizer/validation.py of the package prob's class lives in (whatever name it was imported under)
+    pkg = type(prob).__module__.rpartition(".")[0]
+    validate_plans = importlib.import_module(pkg + ".validation").validate_plans
+    return validate_plans(prob, plans, num_rollouts=num_rollouts, seed=seed)
+
+
+def solve_ticks(prob, rec, cost, ticks, v_des=V_DES, solve=None, inputs=None):
+    """The plans of ``ticks`` (in order) under ``cost``: per tick a dict with
+    init, xo, yo, path, v_best, steering, mean_param, tick, key (= tick)."""
+    solve = solve or _solve
+    inputs = inputs or _inputs
+    mean = MEAN.copy()
+    plans = []
+    for k in ticks:
+        init, xo, yo, path = inputs(rec, prob, int(k))
+        _, _, v_best, steering, mean = solve(prob, cost, int(k), init, mean, COV, xo, yo, v_des, path)
+        plans.append(dict(tick=int(k), key=int(k), init=init, xo=xo, yo=yo, path=path, v_best=np.array(v_best),
+                          steering=np.array(steering), mean_param=np.array(mean)))
+    return plans
+
+
+def validate_replay(rec, prob, costs=("mmd", "cvar", "det"), ticks=None, num_rollouts=1000, out_dir=None, seed=0,
+                    v_des=V_DES, solve=None, validate=None, inputs=None, log=print):
+    """See the module docstring.  ticks: iterable of tick indices (default:
+    every tick of the recording).  Returns {cost: the npz fields}."""
+    ticks = list(range(rec["ego"].shape[0])) if ticks is None else [int(k) for k in ticks]
+    validate = validate or _validate
+    R = int(num_rollouts)
+    results = {}
+    for cost in costs:
+        if cost not in COSTS:
+            raise ValueError(f"cost must be one of {sorted(COSTS)}")
+        plans = solve_ticks(prob, rec, cost, ticks, v_des, solve, inputs)
+        res = validate(prob, plans, R, seed) if plans else {}
+        out = {k: np.asarray(res.get(k, np.zeros(0, np.int32)), np.int32).reshape(len(ticks))
+               for k in ("count", "count_rows", "count_lane")}
+        out["tick"] = np.asarray(ticks, np.int32)
+        out["num_rollouts"] = np.int32(R)
+        if out_dir is not None:
+            os.makedirs(out_dir, exist_ok=True)
+            np.savez(os.path.join(out_dir, f"validate_{cost}.npz"), **out)
+        n = len(ticks)
+        share = float((out["count_rows"] > 0).mean()) if n else 0.0
+        prob_mean = float((out["count_rows"] / R).mean()) if n else 0.0
+        log(f"{cost}: {n} ticks, share with count_rows > 0 = {share:.4f}, mean count_rows / R = {prob_mean:.6f}")
+        results[cost] = out
+    return results
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Monte-Carlo validation of the plans of a CARLA replay")
+    ap.add_argument("replay", nargs="?", help="replay .npz (replay.py)")
+    ap.add_argument("--synthetic", type=int, metavar="TICKS", help="record_synthetic(TICKS) instead of a file")
+    ap.add_argument("--town", default="Town05", help="town of the synthetic recording")
+    ap.add_argument("--costs", nargs="+", default=["mmd", "cvar", "det"], choices=sorted(COSTS))
+    ap.add_argument("--ticks", type=int, nargs=2, metavar=("A", "B"), help="ticks A .. B-1 (default: all)")
+    ap.add_argument("--num-rollouts", type=int, default=1000)
+    ap.add_argument("--out", default="stats_carla")
+    ap.add_argument("--num-reduced", type=int, default=10, help="num_reduced_sqrt (main_carla.py: 10)")
+    ap.add_argument("--num-obs", type=int, default=3)
+    ap.add_argument("--num-prime", type=int, default=60)
+    ap.add_argument("--noise", default="gaussian", choices=["gaussian", "beta"])
+    ap.add_argument("--noise-level", type=float, default=0.1)
+    ap.add_argument("--acc-const-noise", type=float, default=0.0)
+    ap.add_argument("--steer-const-noise", type=float, default=0.0)
+    ap.add_argument("--num-batch", type=int, default=100)
+    ap.add_argument("--maxiter-cem", type=int, default=20)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args(argv)
+    if (a.replay is None) == (a.synthetic is None):
+        ap.error("give a replay file or --synthetic TICKS")
+    R = _replay()
+    rec = R.record_synthetic(a.synthetic, town=a.town) if a.synthetic is not None else R.load(a.replay)
+    if sys.path[0] != _HERE:
+        sys.path.insert(0, _HERE)
+    from optimizer import cem
+    prob = cem.CEM(a.num_reduced, 1, a.num_obs, a.noise_level, a.num_prime, a.noise, str(rec["town"]),
+                   a.acc_const_noise, a.steer_const_noise, num_batch=a.num_batch, maxiter_cem=a.maxiter_cem,
+                   seed=a.seed)
+    ticks = None if a.ticks is None else range(a.ticks[0], a.ticks[1])
+    validate_replay(rec, prob, a.costs, ticks, a.num_rollouts, a.out, a.seed)
+    prob.handle.close()
+
+
+if __name__ == "__main__":
+    main()

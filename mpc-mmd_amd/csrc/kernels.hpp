@@ -277,6 +277,35 @@ struct ValidateParams {
 };
 bool validate_shape_ok(int O, int H);
 void launch_validate(const ValidateParams& v, hipStream_t s);
+
+// Monte-Carlo validation of CARLA plans (k_validate_carla.hip): the cvar risk
+// stage's rollouts / Frenet transform / bars with R fresh noise rows per tick,
+// reduced to collision counts instead of CVaR
+struct ValidateCarlaParams {
+  int32_t K, O, H, R, P, noise;
+  float sigma_acc, sigma_steer, K_steer, acc_const, steer_const;  // as Params (K_steer = float32(K_steer * sigma))
+  float y_lb, y_ub, wheel_base, obs_a2, obs_b2;
+  float init_mu_x, init_mu_y, init_sigma_x, init_sigma_y;
+  uint32_t seed;
+  const float* st0;       // [K][8]: x0, y0, vx, vy, psi of the tick's initial state (carla_rows before the noise)
+  const float* acc;       // [K][H]  controls of the plan
+  const float* steer;     // [K][H]
+  const float* x_obs;     // [K][O][100] Frenet tracks
+  const float* y_obs;
+  const float* path;      // [K][6][P]
+  const float* draws;     // [K][3][R][H] or null (internal Philox)
+  const float* init_eps;  // [K][R][4] or null
+  const uint32_t* keys;   // [K]
+  int32_t* cnt_oh;        // [K][O][H]  accumulators, zero before launch_validate_carla
+  int32_t* cnt_lane;      // [K][2][H]
+  int32_t* count_rows;    // [K]        (accumulator and result)
+  int32_t* count;         // [K]
+  int32_t* count_lane;    // [K]
+};
+bool validate_carla_shape_ok(int O, int H, int P);
+size_t validate_carla_lds(int O, int H, int P);  // dynamic LDS bytes of a workgroup
+// false: the shape's LDS need exceeds lds_limit (nothing is launched)
+bool launch_validate_carla(const ValidateCarlaParams& v, size_t lds_limit, hipStream_t s);
 void launch_gamma_tab(const Params& p, int t, hipStream_t s);
 void launch_beta_planes(const Params& p, int t, hipStream_t s);
 // mmd_opt risk, one launch each (mpcmmd.hip chains them)

@@ -1460,7 +1460,9 @@ int mpcmmd_validate(const mpcmmd_validate_args* a) {
   if (K < 0 || R < 1 || !validate_shape_ok(O, H)) return fail(MPCMMD_E_INVALID, "validate: shape out of range");
   if (a->noise != MPCMMD_NOISE_GAUSSIAN && a->noise != MPCMMD_NOISE_BETA) return fail(MPCMMD_E_INVALID, "noise");
   if (a->variant != MPCMMD_VARIANT_STATIC && a->variant != MPCMMD_VARIANT_DYNAMIC)
-    return fail(MPCMMD_E_UNSUPPORTED, "validate: static / dynamic variants (S/validation.py, D/validation.py)");
+    return fail(MPCMMD_E_UNSUPPORTED,
+                "validate: static / dynamic variants (S/validation.py, D/validation.py); CARLA plans: "
+                "mpcmmd_validate_carla");
   if (K == 0) return MPCMMD_OK;
   if (!a->cx || !a->cy || !a->init_state || !a->x_obs || !a->y_obs || !a->keys || !a->count || !a->count_lane)
     return fail(MPCMMD_E_INVALID, "null argument");
@@ -1509,6 +1511,106 @@ int mpcmmd_validate(const mpcmmd_validate_args* a) {
     HIPC(hipDeviceSynchronize());
     HIPC(hipMemcpy(a->count, v.count, size_t(K) * 4, hipMemcpyDeviceToHost));
     HIPC(hipMemcpy(a->count_lane, v.count_lane, size_t(K) * 4, hipMemcpyDeviceToHost));
+    return MPCMMD_OK;
+  });
+}
+
+int mpcmmd_validate_carla(const mpcmmd_validate_carla_args* a) {
+  if (!a) return fail(MPCMMD_E_INVALID, "null argument");
+  const int K = a->num_cfg, O = a->num_obs, H = a->num_prime, R = a->num_rollouts, P = a->num_path;
+  if (K < 0 || K > 65535 || R < 1 || !validate_carla_shape_ok(O, H, P) || int64_t(R) * H >= (int64_t(1) << 31))
+    return fail(MPCMMD_E_INVALID, "validate_carla: shape out of range");
+  if (a->noise != MPCMMD_NOISE_GAUSSIAN && a->noise != MPCMMD_NOISE_BETA) return fail(MPCMMD_E_INVALID, "noise");
+  if (a->variant != MPCMMD_VARIANT_CARLA_TOWN05 && a->variant != MPCMMD_VARIANT_CARLA_TOWN10HD)
+    return fail(MPCMMD_E_INVALID, "validate_carla: a CARLA variant (static / dynamic optima: mpcmmd_validate)");
+  if (K == 0) return MPCMMD_OK;
+  if (!a->init_state || !a->v || !a->steer || !a->x_obs || !a->y_obs || !a->path || !a->keys || !a->count ||
+      !a->count_lane || !a->count_rows)
+    return fail(MPCMMD_E_INVALID, "null argument");
+  return guarded([&] {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) throw HipError("no HIP device visible");
+    if (a->device < 0 || a->device >= ndev) throw std::invalid_argument("device out of range");
+    HIPC(hipSetDevice(a->device));
+    int lds_max = 0;
+    HIPC(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, a->device));
+    if (validate_carla_lds(O, H, P) > size_t(lds_max))
+      return fail(MPCMMD_E_UNSUPPORTED, "validate_carla: the shape's workgroup needs " +
+                                            std::to_string(validate_carla_lds(O, H, P)) + " B of LDS, the device has " +
+                                            std::to_string(lds_max));
+    const ProblemConsts pc = build_constants(H, a->variant);
+    // the plan's controls (compute_controls, cem_helper.py: acc = diff([v, v_end]) / t) and the
+    // tick's initial state as carla_rows forms it
+    std::vector<float> acc(size_t(K) * H), steer(size_t(K) * H), st0(size_t(K) * 8, 0.0f);
+    for (int k = 0; k < K; ++k) {
+      const float* v = a->v + size_t(k) * kNum;
+      for (int h = 0; h < H; ++h) {
+        const float vn = h + 1 < kNum ? v[h + 1] : v[kNum - 1];
+        acc[size_t(k) * H + h] = (vn - v[h]) / 0.15f;  // prob.t (rollout.hpp: kDt)
+        steer[size_t(k) * H + h] = a->steer[size_t(k) * kNum + h];
+      }
+      const float* is = a->init_state + size_t(k) * 6;
+      const float v0 = is[2], psi0 = is[4];
+      const float vx = v0 * float(std::cos(double(psi0))), vy = v0 * float(std::sin(double(psi0)));
+      float* o = st0.data() + size_t(k) * 8;
+      o[0] = is[0], o[1] = is[1], o[2] = vx, o[3] = vy;
+      o[4] = float(std::atan2(double(vy), double(vx)));
+    }
+    std::vector<void*> bufs;
+    auto up = [&](const void* src, size_t bytes) -> void* {
+      void* d = nullptr;
+      HIPC(hipMalloc(&d, bytes));
+      bufs.push_back(d);
+      if (src) HIPC(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+      return d;
+    };
+    struct Free {
+      std::vector<void*>& b;
+      hipEvent_t e0 = nullptr, e1 = nullptr;
+      ~Free() {
+        for (void* x : b) (void)hipFree(x);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+      }
+    } guard{bufs};
+    ValidateCarlaParams v{};
+    v.K = K, v.O = O, v.H = H, v.R = R, v.P = P, v.noise = a->noise, v.seed = a->seed;
+    v.sigma_acc = v.sigma_steer = a->noise_level;
+    v.K_steer = float(pc.K_steer * double(a->noise_level));
+    v.acc_const = a->acc_const_noise, v.steer_const = a->steer_const_noise;
+    v.y_lb = float(pc.y_lb), v.y_ub = float(pc.y_ub), v.wheel_base = float(pc.wheel_base);
+    v.obs_a2 = float(pc.a_obs * pc.a_obs), v.obs_b2 = float(pc.b_obs * pc.b_obs);
+    v.init_mu_x = float(pc.init_mu_x), v.init_mu_y = float(pc.init_mu_y);
+    v.init_sigma_x = float(pc.init_sigma_x), v.init_sigma_y = float(pc.init_sigma_y);
+    v.st0 = (const float*)up(st0.data(), st0.size() * 4);
+    v.acc = (const float*)up(acc.data(), acc.size() * 4);
+    v.steer = (const float*)up(steer.data(), steer.size() * 4);
+    v.x_obs = (const float*)up(a->x_obs, size_t(K) * O * kNum * 4);
+    v.y_obs = (const float*)up(a->y_obs, size_t(K) * O * kNum * 4);
+    v.path = (const float*)up(a->path, size_t(K) * 6 * P * 4);
+    v.draws = a->draws ? (const float*)up(a->draws, size_t(K) * 3 * R * H * 4) : nullptr;
+    v.init_eps = a->init_eps ? (const float*)up(a->init_eps, size_t(K) * R * 4 * 4) : nullptr;
+    v.keys = (const uint32_t*)up(a->keys, size_t(K) * 4);
+    // one allocation of the integer counters: count_oh | lane | count_rows | count | count_lane
+    const size_t n_oh = size_t(K) * O * H, n_lane = size_t(K) * 2 * H, n_all = n_oh + n_lane + size_t(3) * K;
+    int32_t* ctr = (int32_t*)up(nullptr, n_all * 4);
+    v.cnt_oh = ctr, v.cnt_lane = ctr + n_oh, v.count_rows = v.cnt_lane + n_lane;
+    v.count = v.count_rows + K, v.count_lane = v.count + K;
+    if (a->elapsed_ms) {
+      HIPC(hipEventCreate(&guard.e0));
+      HIPC(hipEventCreate(&guard.e1));
+      HIPC(hipEventRecord(guard.e0, nullptr));
+    }
+    HIPC(hipMemsetAsync(ctr, 0, n_all * 4, nullptr));
+    if (!launch_validate_carla(v, size_t(lds_max), nullptr)) throw std::logic_error("validate_carla: LDS check");
+    HIPC(hipGetLastError());
+    if (a->elapsed_ms) HIPC(hipEventRecord(guard.e1, nullptr));
+    HIPC(hipDeviceSynchronize());
+    if (a->elapsed_ms) HIPC(hipEventElapsedTime(a->elapsed_ms, guard.e0, guard.e1));
+    HIPC(hipMemcpy(a->count, v.count, size_t(K) * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(a->count_lane, v.count_lane, size_t(K) * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(a->count_rows, v.count_rows, size_t(K) * 4, hipMemcpyDeviceToHost));
+    if (a->count_oh) HIPC(hipMemcpy(a->count_oh, v.cnt_oh, n_oh * 4, hipMemcpyDeviceToHost));
     return MPCMMD_OK;
   });
 }

@@ -33,6 +33,16 @@ enum Stream : uint32_t {
   kStreamBetaZ0 = 17,
   kStreamBetaZ = 18,
   kStreamInitEps = 19,  // CARLA noisy initial states, key (idx_mpc, seed) (carla/optimizer/cem_helper.py:662-665)
+  // CARLA plan validation (k_validate_carla), key (keys[k], seed): element r*H + h of the [R][H] normals of
+  // acc / steer / const and of the Beta gammas (attempt counters as gamma_attempt), element r*4 + c of init_eps
+  kStreamVcAcc = 32,
+  kStreamVcSteer = 33,
+  kStreamVcConst = 34,
+  kStreamVcGammaAccA = 35,
+  kStreamVcGammaAccB = 36,
+  kStreamVcGammaSteerA = 37,
+  kStreamVcGammaSteerB = 38,
+  kStreamVcInitEps = 39,
 };
 constexpr uint32_t kFixedKey0 = 0xFFFFFFFFu;
 constexpr int kGammaMaxAttempts = 32;

@@ -18,7 +18,7 @@ COST = {"mmd_opt": 0, "mmd_random": 1, "cvar": 2, "saa": 3, "det": 4}  # det: CA
 NOISE = {"gaussian": 0, "beta": 1}
 VARIANT = {"static": 0, "dynamic": 1, "carla_town05": 2, "carla_town10hd": 3}
 RESULT_STRIDE_BETA_MAX = 32
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 SYMBOLS = (
     "mpcmmd_abi_version", "mpcmmd_last_error", "mpcmmd_device_count", "mpcmmd_create",
@@ -28,7 +28,7 @@ SYMBOLS = (
     "mpcmmd_host_constant", "mpcmmd_obs_dynamic_traj", "mpcmmd_validate", "mpcmmd_create_batch",
     "mpcmmd_max_configs", "mpcmmd_solve_batch", "mpcmmd_begin_batch", "mpcmmd_finish_batch",
     "mpcmmd_carla_begin", "mpcmmd_carla_solve", "mpcmmd_path_smoothing", "mpcmmd_path_parameters",
-    "mpcmmd_global_to_frenet", "mpcmmd_set_graphs", "mpcmmd_handle_info",
+    "mpcmmd_global_to_frenet", "mpcmmd_set_graphs", "mpcmmd_handle_info", "mpcmmd_validate_carla",
 )
 
 
@@ -72,6 +72,19 @@ class ValidateArgs(C.Structure):
                 ("y_obs", C.POINTER(C.c_float)), ("draws", C.POINTER(C.c_double)),
                 ("keys", C.POINTER(C.c_uint32)), ("count", C.POINTER(C.c_int32)),
                 ("count_lane", C.POINTER(C.c_int32))]
+
+
+class ValidateCarlaArgs(C.Structure):
+    _fields_ = [("num_cfg", C.c_int32), ("num_obs", C.c_int32), ("num_prime", C.c_int32),
+                ("num_rollouts", C.c_int32), ("num_path", C.c_int32), ("noise", C.c_int32), ("variant", C.c_int32),
+                ("noise_level", C.c_float), ("acc_const_noise", C.c_float), ("steer_const_noise", C.c_float),
+                ("seed", C.c_uint32), ("device", C.c_int32),
+                ("init_state", C.POINTER(C.c_float)), ("v", C.POINTER(C.c_float)), ("steer", C.POINTER(C.c_float)),
+                ("x_obs", C.POINTER(C.c_float)), ("y_obs", C.POINTER(C.c_float)), ("path", C.POINTER(C.c_float)),
+                ("draws", C.POINTER(C.c_float)), ("init_eps", C.POINTER(C.c_float)),
+                ("keys", C.POINTER(C.c_uint32)), ("count", C.POINTER(C.c_int32)),
+                ("count_lane", C.POINTER(C.c_int32)), ("count_rows", C.POINTER(C.c_int32)),
+                ("count_oh", C.POINTER(C.c_int32)), ("elapsed_ms", C.POINTER(C.c_float))]
 
 
 class NativeError(RuntimeError):
@@ -126,6 +139,7 @@ def lib():
     L.mpcmmd_run_stage.argtypes = [vp, C.c_int32, C.c_int32]
     L.mpcmmd_host_constant.argtypes = [C.POINTER(Config), C.c_char_p, C.POINTER(C.c_double), C.c_size_t]
     L.mpcmmd_validate.argtypes = [C.POINTER(ValidateArgs)]
+    L.mpcmmd_validate_carla.argtypes = [C.POINTER(ValidateCarlaArgs)]
     L.mpcmmd_obs_dynamic_traj.argtypes = [C.c_int32, fp, fp, fp, fp, fp, C.c_float, fp, fp]
     cargs = [vp, C.c_int32, C.c_int32, fp, fp, fp, fp, fp, C.c_float, C.POINTER(Path), C.POINTER(Draws)]
     L.mpcmmd_set_graphs.argtypes = [vp, C.c_int32]
@@ -200,6 +214,58 @@ def validate(cx, cy, init_state, x_obs, y_obs, keys, num_prime, noise, noise_lev
                         cl.ctypes.data_as(C.POINTER(C.c_int32)))
     check(lib().mpcmmd_validate(C.byref(args)))
     return cnt, cl
+
+
+def validate_carla(init_state, v, steer, x_obs, y_obs, paths, keys, num_prime, noise, noise_level,
+                   acc_const_noise=0.0, steer_const_noise=0.0, num_rollouts=1000, variant="carla_town05", draws=None,
+                   init_eps=None, seed=0, device=0, count_oh=False, timing=False):
+    """mpcmmd_validate_carla over K simulator ticks, one returned plan each:
+    the optimizer's cvar risk model with ``num_rollouts`` fresh noise rows,
+    reduced to counts (include/mpcmmd.h).  init_state [K,6]
+    (init_state_global); v, steer [K,100] (v_best, steering_best); x_obs, y_obs
+    [K,O,100] Frenet tracks; paths: K path dicts (PATH_KEYS) of one length, or
+    an array [K,6,P]; keys [K]; draws [K,3,R,H], init_eps [K,R,4] fp32 or None
+    (internal Philox streams).  Returns a dict: count, count_lane, count_rows
+    [K] int32, with ``count_oh`` also count_oh [K,O,H], with ``timing`` also
+    elapsed_ms (HIP events around the device work)."""
+    f = lambda a, *shape: np.ascontiguousarray(np.asarray(a, np.float32).reshape(*shape))
+    K = int(np.asarray(keys).reshape(-1).shape[0])
+    H, R = int(num_prime), int(num_rollouts)
+    if K == 0:
+        pa = np.zeros((0, 6, 4), np.float32)
+    elif isinstance(paths, np.ndarray):
+        pa = f(paths, K, 6, -1)
+    else:
+        if len(paths) != K:
+            raise ValueError("one path per tick")
+        if len({np.asarray(p[k]).size for p in paths for k in PATH_KEYS}) > 1:
+            raise ValueError("path arrays differ in length (one num_path per call)")
+        pa = f([[np.asarray(p[k], np.float32).reshape(-1) for k in PATH_KEYS] for p in paths], K, 6, -1)
+    P = pa.shape[2]
+    st, vv, ss = f(init_state, K, 6), f(v, K, 100), f(steer, K, 100)
+    if K:
+        xo, yo = f(x_obs, K, -1, 100), f(y_obs, K, -1, 100)
+    else:  # nothing to run: the library returns before it looks at the arrays
+        xo = yo = np.zeros((0, 1, 100), np.float32)
+    O = xo.shape[1]
+    ks = np.ascontiguousarray(np.asarray(keys, np.int64).reshape(K).astype(np.uint32))
+    dr = None if draws is None else f(draws, K, 3, R, H)
+    ie = None if init_eps is None else f(init_eps, K, R, 4)
+    out = {k: np.zeros(K, np.int32) for k in ("count", "count_lane", "count_rows")}
+    oh = np.zeros((K, O, H), np.int32) if count_oh else None
+    ms = C.c_float(0.0)
+    ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    args = ValidateCarlaArgs(K, O, H, R, P, NOISE[noise], VARIANT[variant], float(noise_level),
+                             float(acc_const_noise), float(steer_const_noise), int(seed) & 0xFFFFFFFF, int(device),
+                             _fptr(st), _fptr(vv), _fptr(ss), _fptr(xo), _fptr(yo), _fptr(pa), _fptr(dr), _fptr(ie),
+                             ks.ctypes.data_as(C.POINTER(C.c_uint32)), ip(out["count"]), ip(out["count_lane"]),
+                             ip(out["count_rows"]), ip(oh), C.pointer(ms) if timing else None)
+    check(lib().mpcmmd_validate_carla(C.byref(args)))
+    if count_oh:
+        out["count_oh"] = oh
+    if timing:
+        out["elapsed_ms"] = float(ms.value)
+    return out
 
 
 def _fptr(a):
