@@ -92,7 +92,6 @@ struct mpcmmd_handle {
   int last_t = -1;
   bool ext_roll = false, ext_res = false;
   bool beta_tables_internal = false;  // device beta tables hold the internal streams
-  bool dist_pad = false;              // the distance matrix's +inf pad columns written (k_dist_pad)
   bool sel0_valid = false;            // sel0 / sig0 / rp0 / rpair0 match the device beta_z0
   // generation of the sel0 table (bumped by every rebuild) and the one
   // k_bmoment last used for the first beta-iteration's direct row sums: the
@@ -371,7 +370,8 @@ void run_beta_cem(mpcmmd_handle* h) {
   // the default split applies to launches of >= 1024 candidates (a batch
   // handle may run fewer configurations than it holds); MPCMMD_GROUPS forces it
   const bool small = B >= 64 && B <= 256;
-  const int G = h->prof ? 1 : (B >= 1024 || h->groups_forced ? h->groups : (small ? std::min(h->groups, h->small_groups) : 1));
+  const int Gw = h->prof ? 1 : (B >= 1024 || h->groups_forced ? h->groups : (small ? std::min(h->groups, h->small_groups) : 1));
+  const int G = std::min(Gw, int(mpcmmd_handle::kMaxGroups));  // gstream[] / gev_done[] hold kMaxGroups
   if (G <= 1) {
     for (int tb = 0; tb < kBetaIters; ++tb) run_beta_iteration(h, h->p, tb, h->stream);
     return;
@@ -442,10 +442,6 @@ void run_stage(mpcmmd_handle* h, int stage, int t) {
         if (!h->mmd_ok) throw std::invalid_argument("mmd_opt unsupported for this configuration: " + h->mmd_why);
         ensure_sel0(h);
         h->launch(kKMother, [&] { launch_mother(p, t, h->stream); });
-        if (!h->dist_pad) {
-          launch_dist_pad(p, h->Gmax * h->B, h->stream);  // the whole capacity: later solves may hold more candidates
-          h->dist_pad = true;
-        }
         h->launch(kKBDist, [&] { launch_bdist(p, h->stream); });
         h->launch(kKBMoment, [&] { launch_bmoment(p, h->stream); });
         h->bmoment_gen = h->sel0_gen;
@@ -484,10 +480,6 @@ void run_stage(mpcmmd_handle* h, int stage, int t) {
         ensure_gamma_tab(h, t);
         ensure_sel0(h);
         h->launch(kKMother, [&] { launch_mother(p, t, h->stream); });
-        if (!h->dist_pad) {
-          launch_dist_pad(p, h->Gmax * h->B, h->stream);  // the whole capacity: later solves may hold more candidates
-          h->dist_pad = true;
-        }
         h->launch(kKBDist, [&] { launch_bdist(p, h->stream); });
         h->launch(kKBMoment, [&] { launch_bmoment(p, h->stream); });
         h->bmoment_gen = h->sel0_gen;
@@ -687,6 +679,11 @@ int mpcmmd_create_batch(const mpcmmd_config* cfg, int32_t max_configs, mpcmmd_ha
       p.rpair0 = (const int2*)h->alloc("rpair0", size_t(kBetaSamples) * n * 8);
       p.rperm = (const int32_t*)h->alloc("rperm", size_t(M) * 4);
       p.bdist = (float*)h->alloc("bdist", BT * M * dist_stride(int(M)) * 4);
+      // the +inf pad columns, once per handle and for the whole capacity (later
+      // solves may hold more candidates); here, after the buffer's clear on the
+      // same stream, so the launch can never land inside a graph capture
+      launch_dist_pad(p, int(BT), h->stream);
+      HIPC(hipGetLastError());
       p.ctrl_n = (float*)h->alloc("ctrl_n", BT * 2 * n * H * 4);
       p.bsel = (int32_t*)h->alloc("bsel", BT * kBetaSamples * n * 4);
       p.bsig = (float*)h->alloc("bsig", BT * kBetaSamples * 4);
@@ -759,7 +756,8 @@ int mpcmmd_create_batch(const mpcmmd_config* cfg, int32_t max_configs, mpcmmd_ha
     if (BT >= 1024) h->groups = 2;
     // small batches on the per-iteration kernels (num_reduced > 16; CARLA n = 22 at
     // B = 100): two groups as well, for launches of 64..256 candidates
-    if (const char* g = std::getenv("MPCMMD_SMALL_GROUPS")) h->small_groups = std::max(1, std::atoi(g));
+    if (const char* g = std::getenv("MPCMMD_SMALL_GROUPS"))
+      h->small_groups = std::max(1, std::min(mpcmmd_handle::kMaxGroups, std::atoi(g)));
     if (BT >= 64 && BT <= 256) h->groups = std::max(h->groups, h->small_groups);
     h->groups_forced = std::getenv("MPCMMD_GROUPS") != nullptr;
     if (const char* g = std::getenv("MPCMMD_GRAPH")) h->graphs = std::atoi(g) != 0;

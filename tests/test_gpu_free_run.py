@@ -149,6 +149,42 @@ def test_iteration_graphs(native, cost, noise, n):
                 assert got[k] == v or (v != v and got[k] != got[k]), f"{k} differs with graphs (run {rep})"
 
 
+@pytest.mark.parametrize("n", [6, 17])
+def test_iteration_graphs_out_of_order_first(native, n):
+    """A fresh handle whose first call is iterate(1, 1): with single-iteration
+    graphs every iteration is captured at that call, so work the handle does
+    once (the +inf pad columns of the distance matrix, k_dist_pad) must not
+    be recorded into one iteration's graph -- replaying another iteration
+    first would then sum exp(-0) = 1 per pad column into every direct row
+    sum.  n = 6 (M = 36, 220 pad columns) runs the fused k_bcem_small, n = 17
+    (M = 289, 223 pad columns) the per-iteration kernels.  Graph replay must
+    give the bits of direct launches after each of iterate(1, 1),
+    iterate(0, 1), iterate(1, 1), and every pad column must hold +inf."""
+    from parity import make_pair
+    M, Md = n * n, (n * n + 255) & ~255
+    nats = []
+    for graphs in (False, True):
+        ora, nat, xo, yo = make_pair(native, "mmd_opt", "gaussian", n=n, O=O, H=10, B=B, T=3)
+        nat.set_graphs(graphs)
+        nat.begin("mmd_opt", 3, DEFAULT_INIT, DEFAULT_MEAN, DEFAULT_COV, xo, yo, 15.0)
+        nats.append(nat)
+    for step, t in enumerate((1, 0, 1)):
+        for nat in nats:
+            nat.iterate(t, 1)
+            nat.sync()
+        assert np.all(np.isfinite(nats[0].read("brow"))), f"call {step}: row sums of the direct launches not finite"
+        for k in ("brow", "res_beta", "obs_cost", "lane_cost", "pop"):
+            a, b = nats[0].read(k), nats[1].read(k)
+            ne = np.flatnonzero((a != b) & ~(np.isnan(a) & np.isnan(b)))
+            assert ne.size == 0, (f"call {step} (iterate({t}, 1)): {k} differs with graphs in {ne.size} elements; first "
+                                  f"at {ne[0]}: {a[ne[0]]} (direct launches) vs {b[ne[0]]} (graphs)")
+        for nat, what in zip(nats, ("direct launches", "graphs")):
+            pad = nat.read("bdist", np.float32, (B, M, Md))[:, :, M:]
+            assert np.all(np.isposinf(pad)), f"call {step} (iterate({t}, 1)), {what}: pad columns of bdist not +inf"
+    for nat in nats:
+        nat.close()
+
+
 @pytest.mark.parametrize("cost,noise,n", [("cvar", "beta", 24), ("mmd_opt", "gaussian", 6)])
 def test_draws_ahead(native, cost, noise, n, monkeypatch):
     """k_select of iteration t drawing iteration t + 1's noise and Beta attempt

@@ -91,7 +91,19 @@ def test_mother_features(native, noise):
     (32, 20, 50, 20, "dynamic", [0, 19], None),
     # BASELINE configs[0] shape: n = 50 (M = 2500), B = 100, H = 20, O = 4 (the wave-per-QP path, n > 32);
     # the oracle QP (100 x 50 x 2500 kernel entries per sample set) is checked on three iterations
-    (50, 100, 20, 4, "static", [0, 99], (0, 1, 19))])
+    (50, 100, 20, 4, "static", [0, 99], (0, 1, 19)),
+    # the first n of each QP padding class (the most pad rows): quad QPs of 12, 16, 24 and 32 rows, then
+    # k_bqp_wave<48>; M = 289 / 625 / 1089: 2, 3 and 5 float4s per lane of a distance row (5: the first
+    # direct-sum form without the prefetch)
+    (9, 20, 10, 3, "static", None, None), (13, 20, 10, 3, "static", None, None),
+    (17, 20, 10, 3, "static", [0, 7, 19], None), (25, 20, 10, 3, "static", [0, 19], None),
+    (33, 20, 10, 3, "static", [0, 19], (0, 1, 19)),
+    # n = NP of both wave QPs: no pad lanes; M = 2304 has no pad columns, M = 4096 is the largest supported
+    # (the default: case of the row-sum kernels' switches, the largest LDS footprints)
+    (48, 20, 10, 3, "static", [0, 19], (0, 1, 19)), (64, 20, 10, 3, "static", [0, 19], (0, 1, 19)),
+    # a large launch at the benchmark's n (nb = 300 > 256: k_bkernel<false>, the row-sorted k_bdirect in 8
+    # parts, k_bqp at 128 threads, 16 select waves); candidates off every multiple of 16 / 64
+    (22, 300, 10, 3, "static", [1, 37, 150, 299], (0, 1, 19))])
 def test_beta_cem_lockstep(native, n, B, H, O, variant, check, qp_iters):
     ora, nat, xo, yo, draws, st, acc, steer = _run_mother(native, n, B, H, O, "gaussian", 2, variant)
     p = ora.prob
