@@ -38,6 +38,8 @@
 // launchers in k_mother, k_bdist, k_bsample, k_bkernel, k_bqp, k_belite and
 // k_bcem_small.hip.
 #pragma once
+#include <type_traits>
+
 #include "block.hpp"
 #include "kernels.hpp"
 
@@ -143,6 +145,21 @@ constexpr int kLptBins = 128;  // pair counts per distinct row (<= 100 samples)
 constexpr double kSeriesAMax = 1.0;
 constexpr float kNegLog2e = -1.44269504088896340736f;
 constexpr size_t kLdsBudget = 160 * 1024 - 1024;
+
+// Host dispatch on the float4s a lane holds of a distance row, V =
+// dist_stride(M) / 256 (one per 256-column block): calls f with
+// std::integral_constant<int, V>, V = 1..16, so a launcher picks its kernel
+// instance by f's argument type.  M <= 4096 (kMaxReduced^2) keeps V <= 16;
+// anything else takes 16.
+template <int V = 1, class F>
+void with_dist_blocks(int M, F&& f) {
+  if constexpr (V == 16) {
+    f(std::integral_constant<int, 16>{});
+  } else {
+    if ((dist_stride(M) >> 8) == V) f(std::integral_constant<int, V>{});
+    else with_dist_blocks<V + 1>(M, f);
+  }
+}
 
 struct LdsTake {  // consecutive 16-byte aligned LDS pieces
   size_t o = 0;

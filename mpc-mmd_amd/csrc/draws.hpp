@@ -42,7 +42,7 @@ __device__ inline void noise_item(const Params& p, int t, const Cfg& cf, int j) 
 }
 
 // Beta-noise attempt table (rng.hpp): one item per (stream, attempt, r, h).
-// Item 0 of configuration 0 also clears k_beta_planes' deferred-list count.
+// Item 0 of configuration 0 also clears k_beta_planes_c's deferred-list count.
 HDI int gamma_items(const Params& p) { return kGammaTabStreams * kGammaTabAttempts * p.S * p.H; }
 
 __device__ inline void gamma_item(const Params& p, int t, const Cfg& cf, int idx) {

@@ -502,18 +502,7 @@ void launch_bmoment(const Params& p, hipStream_t s) {
         break;
     }
   }
-  switch (dist_stride(p.M) >> 8) {
-#define MPCMMD_MOM_CASE(V) \
-  case V:                  \
-    return launch_bmoment_v<V>(p, s);
-    MPCMMD_MOM_CASE(1) MPCMMD_MOM_CASE(2) MPCMMD_MOM_CASE(3) MPCMMD_MOM_CASE(4)
-    MPCMMD_MOM_CASE(5) MPCMMD_MOM_CASE(6) MPCMMD_MOM_CASE(7) MPCMMD_MOM_CASE(8)
-    MPCMMD_MOM_CASE(9) MPCMMD_MOM_CASE(10) MPCMMD_MOM_CASE(11) MPCMMD_MOM_CASE(12)
-    MPCMMD_MOM_CASE(13) MPCMMD_MOM_CASE(14) MPCMMD_MOM_CASE(15)
-    default:
-      return launch_bmoment_v<16>(p, s);
-#undef MPCMMD_MOM_CASE
-  }
+  with_dist_blocks(p.M, [&](auto v) { launch_bmoment_v<decltype(v)::value>(p, s); });
 }
 
 }  // namespace mpcmmd

@@ -111,33 +111,9 @@ void launch_bdirect_pairs_v(const Params& p, int tb, hipStream_t s) {
 }
 
 void launch_bdirect(const Params& p, int tb, hipStream_t s) {
-  if (use_pairs(p)) {
-    switch (dist_stride(p.M) >> 8) {
-#define MPCMMD_PAIR_CASE(V) \
-  case V:                   \
-    return launch_bdirect_pairs_v<V>(p, tb, s);
-      MPCMMD_PAIR_CASE(1) MPCMMD_PAIR_CASE(2) MPCMMD_PAIR_CASE(3) MPCMMD_PAIR_CASE(4)
-      MPCMMD_PAIR_CASE(5) MPCMMD_PAIR_CASE(6) MPCMMD_PAIR_CASE(7) MPCMMD_PAIR_CASE(8)
-      MPCMMD_PAIR_CASE(9) MPCMMD_PAIR_CASE(10) MPCMMD_PAIR_CASE(11) MPCMMD_PAIR_CASE(12)
-      MPCMMD_PAIR_CASE(13) MPCMMD_PAIR_CASE(14) MPCMMD_PAIR_CASE(15)
-      default:
-        return launch_bdirect_pairs_v<16>(p, tb, s);
-#undef MPCMMD_PAIR_CASE
-    }
-  }
+  if (use_pairs(p)) return with_dist_blocks(p.M, [&](auto v) { launch_bdirect_pairs_v<decltype(v)::value>(p, tb, s); });
   const int split = ker_split(p.nb, p.dir_target);
-  switch (dist_stride(p.M) >> 8) {
-#define MPCMMD_KER_CASE(V) \
-  case V:                  \
-    return launch_bdirect_v<V>(p, tb, split, s);
-    MPCMMD_KER_CASE(1) MPCMMD_KER_CASE(2) MPCMMD_KER_CASE(3) MPCMMD_KER_CASE(4)
-    MPCMMD_KER_CASE(5) MPCMMD_KER_CASE(6) MPCMMD_KER_CASE(7) MPCMMD_KER_CASE(8)
-    MPCMMD_KER_CASE(9) MPCMMD_KER_CASE(10) MPCMMD_KER_CASE(11) MPCMMD_KER_CASE(12)
-    MPCMMD_KER_CASE(13) MPCMMD_KER_CASE(14) MPCMMD_KER_CASE(15)
-    default:
-      return launch_bdirect_v<16>(p, tb, split, s);
-#undef MPCMMD_KER_CASE
-  }
+  with_dist_blocks(p.M, [&](auto v) { launch_bdirect_v<decltype(v)::value>(p, tb, split, s); });
 }
 
 }  // namespace mpcmmd

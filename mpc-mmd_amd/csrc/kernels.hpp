@@ -93,14 +93,11 @@ struct Params {
   const float* roll;       // [G][T][3][H][S]
   const float* resample;   // [G][T][B-5][8]
   float* bplane;           // [Bt][2][H][S] Beta draws (acc, steer) of the baseline rollouts (beta noise)
-  uint32_t* bfix;          // [Bt*H*S] elements k_beta_planes deferred to k_beta_fix
+  uint32_t* bfix;          // [Bt*H*S] elements k_beta_planes_c deferred to k_beta_fix
   uint32_t* bfix_n;        // their count (zeroed by k_gamma_tab)
   double* gtab;            // [G][gamma_tab_size] Beta-noise attempt tables of the current iteration
-  void* mttab;             // [H][Bt] gamma constants per (step, candidate) of the fused rollouts (k_mt_tab)
-  float* rbar;             // [3][Bt][S] per-row maxima (collision, lane lb, ub) of the fused rollouts
   int32_t select_prep;     // the risk launch also sorts the residuals and forms the cost norms (cost.hpp)
-  int32_t beta_dump;       // fused rollouts also store their Beta draws in bplane (MPCMMD_BETA_DUMP, tests)
-  int32_t risk_rows;       // 1 (default): the row-lane rollouts over Beta planes; 0: fused (MPCMMD_RISK_FUSED=1)
+  int32_t beta_dump;       // k_beta_planes_c also draws the last step's planes (MPCMMD_BETA_DUMP, tests)
   int32_t* bdlist;         // [Bt][100 n] the flagged (direct) pairs of a beta-iteration, appended by k_bkernel
   int32_t* bdlcount;       // [Bt][20] their count per beta-iteration (zeroed by k_bselect of that iteration)
   int32_t dir_pairs;       // 1: k_bdirect_pairs (a wave per 8 listed pairs); 0: k_bdirect (rows sorted in LDS)
@@ -253,10 +250,6 @@ void launch_front(const Params& p, int t, hipStream_t s);
 // (draws.hpp: kAheadNoise | kAheadGamma) in spare workgroups
 void launch_select(const Params& p, int t, hipStream_t s, int ahead_t = -1, int kind = 0);
 void launch_risk_baseline(const Params& p, int t, hipStream_t s);
-// the same risk with candidate lanes and the Beta draws inside the rollouts
-// (k_mt_tab, k_roll_cand, k_risk_reduce): Params::risk_rows = 0 (MPCMMD_RISK_FUSED=1)
-void launch_risk_fused(const Params& p, int t, hipStream_t s);
-size_t mt_tab_entry_bytes();  // Params::mttab bytes per (step, candidate)
 
 // Monte-Carlo validation (k_validate.hip; S/validation.py:134-171)
 struct ValidateParams {

@@ -346,15 +346,32 @@ void check_bmoment_gen(mpcmmd_handle* h) {
         "beta_z0 changed (or stage 4 not run) since k_bmoment: rerun stage 4 before beta-iteration 0");
 }
 
-// one beta-CEM iteration (compute_beta.py:112-147) of candidates [p.b0, p.b0 + p.nb)
-void run_beta_iteration(mpcmmd_handle* h, const Params& p, int tb, hipStream_t st) {
+// The three thirds of one beta-CEM iteration (compute_beta.py:112-147) of
+// candidates [p.b0, p.b0 + p.nb), also stages 5, 6 and 7 of the stage API:
+// the samples and their top-n rows,
+void run_beta_select(mpcmmd_handle* h, const Params& p, int tb, hipStream_t st) {
   if (tb > 0) h->launch(kKBSample, [&] { launch_bsample(p, tb, st); });
   h->launch(kKBSelect, [&] { tb == 0 ? launch_bsel0(p, st) : launch_bselect(p, tb, st); });
+}
+
+// the kernel sums and the QPs,
+void run_beta_qp(mpcmmd_handle* h, const Params& p, int tb, hipStream_t st) {
   h->launch(kKBKernel, [&] { launch_bkernel(p, tb, st); });
   if (tb > 0) h->launch(kKBDirect, [&] { launch_bdirect(p, tb, st); });  // first iteration: in k_bmoment
   h->launch(kKBQp, [&] { launch_bqp(p, tb, st); });
+}
+
+// the elites and the next iteration's generators
+void run_beta_elite(mpcmmd_handle* h, const Params& p, int tb, hipStream_t st) {
   h->launch(kKBElite, [&] { launch_belite(p, tb, st); });
   h->launch(kKBGen, [&] { launch_bgen(p, tb, st); });
+}
+
+// one beta-CEM iteration: the three thirds in order
+void run_beta_iteration(mpcmmd_handle* h, const Params& p, int tb, hipStream_t st) {
+  run_beta_select(h, p, tb, st);
+  run_beta_qp(h, p, tb, st);
+  run_beta_elite(h, p, tb, st);
 }
 
 // the 20 beta-CEM iterations of every candidate: one chain per candidate
@@ -425,6 +442,24 @@ void ensure_gamma_tab(mpcmmd_handle* h, int t) {
   h->ahead_t = -1;  // the table's one slot now holds t
 }
 
+// mmd_opt's preparation (stage 4): mother rollouts, features, their distance
+// matrix and its series records
+void run_mmd_prep(mpcmmd_handle* h, int t) {
+  const Params& p = h->p;
+  ensure_gamma_tab(h, t);
+  ensure_sel0(h);
+  h->launch(kKMother, [&] { launch_mother(p, t, h->stream); });
+  h->launch(kKBDist, [&] { launch_bdist(p, h->stream); });
+  h->launch(kKBMoment, [&] { launch_bmoment(p, h->stream); });
+  h->bmoment_gen = h->sel0_gen;
+}
+
+// mmd_opt's final reducer (stage 8) over the reduced set the beta-CEM chose
+void run_mmd_final(mpcmmd_handle* h, int t) {
+  if (h->carla) run_carla_risk(h, t, 1);
+  else h->launch(kKMmdFinal, [&] { launch_mmdfinal(h->p, t, h->stream); });
+}
+
 void run_stage(mpcmmd_handle* h, int stage, int t) {
   const Params& p = h->p;
   switch (stage) {
@@ -437,24 +472,18 @@ void run_stage(mpcmmd_handle* h, int stage, int t) {
       break;
     case 2:
       if (p.cost == MPCMMD_COST_DET) break;  // compute_cem_det: no rollouts, zero risks (carla/optimizer/cem.py:717-722)
-      ensure_gamma_tab(h, t);
       if (p.cost == MPCMMD_COST_MMD_OPT) {
         if (!h->mmd_ok) throw std::invalid_argument("mmd_opt unsupported for this configuration: " + h->mmd_why);
-        ensure_sel0(h);
-        h->launch(kKMother, [&] { launch_mother(p, t, h->stream); });
-        h->launch(kKBDist, [&] { launch_bdist(p, h->stream); });
-        h->launch(kKBMoment, [&] { launch_bmoment(p, h->stream); });
-        h->bmoment_gen = h->sel0_gen;
+        run_mmd_prep(h, t);
         run_beta_cem(h);
-        if (h->carla) run_carla_risk(h, t, 1);
-        else h->launch(kKMmdFinal, [&] { launch_mmdfinal(p, t, h->stream); });
-      } else if (h->carla) {
-        if (p.noise == MPCMMD_NOISE_BETA) h->launch(kKBetaPlanes, [&] { launch_beta_planes(p, t, h->stream); });
+        run_mmd_final(h, t);
+        break;
+      }
+      ensure_gamma_tab(h, t);
+      if (p.noise == MPCMMD_NOISE_BETA) h->launch(kKBetaPlanes, [&] { launch_beta_planes(p, t, h->stream); });
+      if (h->carla) {
         run_carla_risk(h, t, 0);
-      } else if (!p.risk_rows) {
-        h->launch(kKRiskBaseline, [&] { launch_risk_fused(p, t, h->stream); });
       } else {
-        if (p.noise == MPCMMD_NOISE_BETA) h->launch(kKBetaPlanes, [&] { launch_beta_planes(p, t, h->stream); });
         h->launch(kKRiskBaseline, [&] { launch_risk_baseline(p, t, h->stream); });
         if (p.select_prep) h->prep_t = t;
       }
@@ -476,36 +505,20 @@ void run_stage(mpcmmd_handle* h, int stage, int t) {
     case 8:
       if (p.cost != MPCMMD_COST_MMD_OPT || !h->mmd_ok) throw std::invalid_argument("stages 4-8 need cost mmd_opt");
       if (stage >= 5 && stage <= 7 && t >= kBetaIters) throw std::invalid_argument("beta-CEM iteration out of range");
-      if (stage == 4) {  // mother rollouts, features and their distance matrix
-        ensure_gamma_tab(h, t);
-        ensure_sel0(h);
-        h->launch(kKMother, [&] { launch_mother(p, t, h->stream); });
-        h->launch(kKBDist, [&] { launch_bdist(p, h->stream); });
-        h->launch(kKBMoment, [&] { launch_bmoment(p, h->stream); });
-        h->bmoment_gen = h->sel0_gen;
-      }
-      if (stage == 5) {  // samples + their top-n rows
-        if (t > 0) h->launch(kKBSample, [&] { launch_bsample(p, t, h->stream); });
+      if (stage == 4) run_mmd_prep(h, t);
+      if (stage == 5) {
         if (t == 0) {
           ensure_sel0(h);
           check_bmoment_gen(h);
         }
-        h->launch(kKBSelect, [&] { t == 0 ? launch_bsel0(p, h->stream) : launch_bselect(p, t, h->stream); });
+        run_beta_select(h, p, t, h->stream);
       }
-      if (stage == 6) {  // kernel sums + QP
+      if (stage == 6) {
         if (t == 0) check_bmoment_gen(h);
-        h->launch(kKBKernel, [&] { launch_bkernel(p, t, h->stream); });
-        if (t > 0) h->launch(kKBDirect, [&] { launch_bdirect(p, t, h->stream); });
-        h->launch(kKBQp, [&] { launch_bqp(p, t, h->stream); });
+        run_beta_qp(h, p, t, h->stream);
       }
-      if (stage == 7) {
-        h->launch(kKBElite, [&] { launch_belite(p, t, h->stream); });
-        h->launch(kKBGen, [&] { launch_bgen(p, t, h->stream); });
-      }
-      if (stage == 8) {
-        if (h->carla) run_carla_risk(h, t, 1);
-        else h->launch(kKMmdFinal, [&] { launch_mmdfinal(p, t, h->stream); });
-      }
+      if (stage == 7) run_beta_elite(h, p, t, h->stream);
+      if (stage == 8) run_mmd_final(h, t);
       break;
     default:
       throw std::invalid_argument("stage must be 0..8");
@@ -660,8 +673,6 @@ int mpcmmd_create_batch(const mpcmmd_config* cfg, int32_t max_configs, mpcmmd_ha
     p.bfix = (uint32_t*)h->alloc("bfix", c.noise == MPCMMD_NOISE_BETA ? BT * H * S * 4 : 16);
     p.bfix_n = (uint32_t*)h->alloc("bfix_n", 16);
     p.gtab = c.noise == MPCMMD_NOISE_BETA ? (double*)h->alloc("gtab", size_t(GM) * gamma_tab_size(S, H) * 8) : nullptr;
-    p.mttab = c.noise == MPCMMD_NOISE_BETA ? h->alloc("mttab", BT * H * mt_tab_entry_bytes()) : nullptr;
-    p.rbar = (float*)h->alloc("rbar", size_t(3) * BT * S * 4);
     if (mmd_ok) {
       p.beta_z0 = (const float*)h->alloc("beta_z0", size_t(kBetaSamples) * (h->M + 1) * 4);
       p.beta_z = (const float*)h->alloc("beta_z", size_t(kBetaIters) * pos_pad(h->M) * kBzCols * 4);
@@ -786,8 +797,6 @@ int mpcmmd_create_batch(const mpcmmd_config* cfg, int32_t max_configs, mpcmmd_ha
     if (const char* g = std::getenv("MPCMMD_KER_TARGET")) p.ker_target = std::max(1, std::atoi(g));
     if (const char* g = std::getenv("MPCMMD_DIR_TARGET")) p.dir_target = std::max(1, std::atoi(g));
     if (const char* g = std::getenv("MPCMMD_BETA_DUMP")) p.beta_dump = std::atoi(g) != 0;
-    p.risk_rows = 1;  // the row-lane path is the faster one at configs[2]; MPCMMD_RISK_FUSED=1: fused
-    if (const char* g = std::getenv("MPCMMD_RISK_FUSED")) p.risk_rows = std::atoi(g) == 0;
     if (const char* g = std::getenv("MPCMMD_GROUPS")) h->groups = std::max(1, std::min(mpcmmd_handle::kMaxGroups, std::atoi(g)));
     if (h->groups > 1) {
       HIPC(hipEventCreateWithFlags(&h->gev_start, hipEventDisableTiming));
@@ -949,7 +958,7 @@ int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t
     p.cost = cost_kind;
     // k_select's residual sort and cost norms in the risk launch (cost.hpp):
     // the baseline rollouts on Beta / Gaussian planes (k_risk_baseline)
-    p.select_prep = h->prep_on && !h->carla && p.risk_rows &&
+    p.select_prep = h->prep_on && !h->carla &&
                     (cost_kind == MPCMMD_COST_CVAR || cost_kind == MPCMMD_COST_SAA || cost_kind == MPCMMD_COST_MMD_RANDOM);
     p.G = G;
     p.Bt = G * B;
@@ -1263,7 +1272,7 @@ int mpcmmd_handle_info(mpcmmd_handle* h, const char* name, int64_t* value) {
   if (!h || !name || !value) return fail(MPCMMD_E_INVALID, "null argument");
   const std::string k(name);
   if (k == "gen_wave") *value = h->p.gen_wave ? 1 : 0;
-  else if (k == "select_prep") *value = h->prep_on && !h->carla && h->p.risk_rows ? 1 : 0;
+  else if (k == "select_prep") *value = h->prep_on && !h->carla ? 1 : 0;
   else if (k == "fused_small") *value = h->fused_small ? 1 : 0;
   else if (k == "groups") *value = h->groups;
   else if (k == "capacity") *value = int64_t(h->Gmax) * h->B;

@@ -256,12 +256,4 @@ DEVI float beta_draw_tab(double a, double b, double ra, double rb, MtConst mc_a,
   return cr ? beta_combine_cr(a, b, ra, rb, ga, ua, gb, ub) : beta_combine(a, b, ra, rb, ga, ua, gb, ub);
 }
 
-// Table-only path for the hot plane kernel: attempts k0 .. kGammaTabAttempts
-// - 1 of the table; false when a gamma needs more (rare: the caller defers
-// the element to the full beta_draw_tab, identical arithmetic)
-DEVI bool gamma_tab_from(MtConst mc, const double* tab, size_t plane, size_t at, int k0, double& g, double& lub) {
-  for (int k = k0; k < kGammaTabAttempts; ++k)
-    if (tab_attempt(mc, tab + size_t(k) * 4 * plane + at, plane, g, lub)) return true;
-  return false;
-}
 }  // namespace mpcmmd

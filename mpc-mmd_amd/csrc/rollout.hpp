@@ -38,7 +38,7 @@ DEVI void beta_pair(const Params& p, const Cfg& cf, int t, int r, int h, float a
 // every candidate, Q2).  Gaussian rows come from p.roll [T][3][H][S]; Beta
 // draws from the Philox gamma streams (elements r*H + h) through the
 // iteration's attempt table p.gtab (k_gamma_tab).
-// kPlanes: Beta draws read from bpl (k_beta_planes) instead of sampled here.
+// kPlanes: Beta draws read from bpl (k_beta_planes_c) instead of sampled here.
 template <bool kPlanes = false>
 DEVI void noisy_control(const Params& p, const Cfg& cf, int t, int r, int h, float a, float s, float& an, float& sn,
                         const float* bpl = nullptr) {
@@ -51,7 +51,7 @@ DEVI void noisy_control(const Params& p, const Cfg& cf, int t, int r, int h, flo
     sp = (p.sigma_steer * fabsf(s)) * roll[(1 * H + h) * S + r];
   } else {
     float nba, nbs;
-    if constexpr (kPlanes) {  // precomputed by k_beta_planes: [2][H][S] of this candidate
+    if constexpr (kPlanes) {  // precomputed by k_beta_planes_c: [2][H][S] of this candidate
       nba = bpl[size_t(h) * S + r];
       nbs = bpl[(size_t(H) + h) * S + r];
     } else {

@@ -236,13 +236,13 @@ PAIRS0 = "MPCMMD_DIR_PAIRS=0,MPCMMD_DIR_WAVES="
         "MPCMMD_GROUPS=1", "MPCMMD_GROUPS=4", PAIRS0 + "16")])
 def test_knob_bits(native, monkeypatch, n, B, knob):
     """mmd_opt, static, H = 10, O = 3, two outer iterations; n = 17 at B = 100
-    and n = 33 at B = 64.  Every setting selects a launch geometry that a
-    default run reaches at some batch size (candidate groups, k_bqp's
-    workgroup size, k_bselect's waves, the parts of k_bkernel and of the
-    direct sums, the row-sorted k_bdirect at 4 / 8 / 16 waves); per outer
-    iteration the beta-CEM outputs, the row sums left in brow, the costs and
-    elite sets, and the finished result carry the bits of the run with no
-    knob set."""
+    and n = 33 at B = 64.  Every setting but MPCMMD_DIR_WAVES 8 / 16 selects a
+    launch geometry that a default run reaches at some batch size (candidate
+    groups, k_bqp's workgroup size, k_bselect's waves, the parts of k_bkernel
+    and of the direct sums, the row-sorted k_bdirect at 4 waves); the 8- and
+    16-wave k_bdirect run only under that knob.  Per outer iteration the
+    beta-CEM outputs, the row sums left in brow, the costs and elite sets,
+    and the finished result carry the bits of the run with no knob set."""
     ref = _reference(native, monkeypatch, n, B)
     got = _run_knobs(native, monkeypatch, n, B, dict(kv.split("=") for kv in knob.split(",")))
     _same_run(knob, got, ref)

@@ -91,16 +91,13 @@ def test_stage_lockstep(native, cost, noise):
 BETA_RTOL, BETA_ATOL = 1e-5, 3e-7
 
 
-@pytest.mark.parametrize("fused", ["1", "0"])
-def test_beta_planes(native, monkeypatch, fused):
-    """The Beta draws of the baseline rollouts against the oracle's: the
-    fused rollouts (candidate lanes, draws inside the rollout; stored as
-    planes only under MPCMMD_BETA_DUMP for this test) and the row-lane plane
-    kernel (MPCMMD_RISK_FUSED=0)."""
+def test_beta_planes(native, monkeypatch):
+    """The Beta draws of the baseline rollouts (the planes k_risk_baseline's
+    row lanes read) against the oracle's.  MPCMMD_BETA_DUMP makes the plane
+    kernel draw the last step too, which no rollout applies."""
     from oracle.rng import (STREAM_GAMMA_ACC_A, STREAM_GAMMA_ACC_B, STREAM_GAMMA_STEER_A, STREAM_GAMMA_STEER_B,
                             beta_draws, iteration_key)
     monkeypatch.setenv("MPCMMD_BETA_DUMP", "1")   # read when the handle is created
-    monkeypatch.setenv("MPCMMD_RISK_FUSED", fused)
     ora, nat, xo, yo = make_pair(native, "cvar", "beta", n=N_S, O=O, H=H, B=B, T=T, acc_c=0.05, steer_c=0.01)
     draws = oracle.Draws.random(ora.prob, np.random.default_rng(3), idx_mpc=123, seed=0, with_beta_cem=False)
     nat.begin("cvar", 123, DEFAULT_INIT, DEFAULT_MEAN, DEFAULT_COV, xo, yo, 15.0, draws)
@@ -192,13 +189,3 @@ def test_free_run_solve(native):
     assert float(ref[3]) == 0.0 and float(got["cost_obs"]) == 0.0
     close("cx[:3]", got["cx"][:3], ref[0][:3], atol=1e-4)
     close("cy[:3]", got["cy"][:3], ref[1][:3], atol=1e-4)
-
-
-@pytest.mark.parametrize("cost,noise", [("cvar", "beta"), ("saa", "gaussian")])
-def test_iteration_lockstep_fused_risk(native, monkeypatch, cost, noise):
-    """The opt-in fused risk path (MPCMMD_RISK_FUSED=1: Beta draws inside the
-    candidate-lane rollouts, k_risk_reduce) against the oracle, iteration by
-    iteration, like the default row-lane path."""
-    monkeypatch.setenv("MPCMMD_RISK_FUSED", "1")  # read when the handle is created
-    exact = run_iteration_lockstep(native, cost, noise)
-    assert exact >= 15, f"only {exact}/20 iterations had identical elite sets"
