@@ -1,10 +1,7 @@
 // libmpcmmd: the C ABI (include/mpcmmd.h), handle / buffer management and
 // the per-iteration launch sequence.  Host code is plain HIP runtime; no
 // torch, no allocation after mpcmmd_create.
-#include "../../include/mpcmmd.h"
-
-#include <hip/hip_runtime.h>
-
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -15,34 +12,24 @@
 #include <string>
 #include <vector>
 
-#include "carla_host.hpp"
+#include "api_common.hpp"
 #include "draws.hpp"
-#include "host_constants.hpp"
 #include "kernels.hpp"
 #include "rng.hpp"
+#include "solve_host.hpp"
 
 using namespace mpcmmd;
 
 namespace {
-
 thread_local std::string g_err;
+}
 
-int fail(int code, const std::string& msg) {
+int mpcmmd::fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
 
-struct HipError : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-
-#define HIPC(x)                                                                                     \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess)                                                                           \
-      throw HipError(std::string(#x) + ": " + hipGetErrorString(e_) + " (" + __FILE__ + ":" +     \
-                     std::to_string(__LINE__) + ")");                                              \
-  } while (0)
+namespace {
 
 enum KernelId {
   kKNoise = 0,
@@ -209,6 +196,18 @@ namespace {
 
 void check_device(mpcmmd_handle* h) { HIPC(hipSetDevice(h->device)); }
 
+PathView view_of(const mpcmmd_path& p) {
+  return path_view(p.num_path, p.x_path, p.y_path, p.arc_vec, p.Fx_dot, p.Fy_dot, p.kappa);
+}
+
+// knobs of mpcmmd_create_batch from the environment: dflt when unset
+int env_int(const char* name, int dflt) {
+  const char* g = std::getenv(name);
+  return g ? std::atoi(g) : dflt;
+}
+bool env_flag(const char* name, bool dflt) { return env_int(name, dflt) != 0; }
+int env_clamped(const char* name, int dflt, int lo, int hi) { return std::max(lo, std::min(hi, env_int(name, dflt))); }
+
 // host Philox normals of stream (stream, word1) with key (k0, k1): `count` values
 std::vector<float> host_normals(uint32_t k0, uint32_t k1, uint32_t stream, uint32_t word1, size_t count) {
   std::vector<float> out(count);
@@ -218,23 +217,6 @@ std::vector<float> host_normals(uint32_t k0, uint32_t k1, uint32_t stream, uint3
     for (int q = 0; q < 4 && j * 4 + q < count; ++q) out[j * 4 + q] = float(z[q]);
   }
   return out;
-}
-
-bool chol8(const double* a, double* L) {
-  for (int i = 0; i < 64; ++i) L[i] = 0.0;
-  for (int j = 0; j < 8; ++j) {
-    double d = a[j * 8 + j];
-    for (int k = 0; k < j; ++k) d -= L[j * 8 + k] * L[j * 8 + k];
-    if (!(d > 0.0)) return false;
-    d = std::sqrt(d);
-    L[j * 8 + j] = d;
-    for (int i = j + 1; i < 8; ++i) {
-      double s = a[i * 8 + j];
-      for (int k = 0; k < j; ++k) s -= L[i * 8 + k] * L[j * 8 + k];
-      L[i * 8 + j] = s / d;
-    }
-  }
-  return true;
 }
 
 void upload(mpcmmd_handle* h, const char* name, const void* src, size_t bytes, size_t offset = 0) {
@@ -262,14 +244,9 @@ size_t stage_size(int B, int S, int H, int O, int T, int G) {
   return s + 16 * 64;
 }
 
-// beta_z iteration t: [89][M+1] (draw order) -> device bz_index layout (the
-// sampler's lane image per 16-position block, zero padded), so the generation
-// kernel reads whole blocks without bounds in coalesced float4 loads
+// beta_z iteration t: [89][M+1] (draw order) in the device layout (beta_z_image)
 void upload_beta_z(mpcmmd_handle* h, int t, const float* z) {
-  const int M1 = h->M + 1, R = kBetaSamples - kBetaElite;
-  std::vector<float> tr(size_t(pos_pad(h->M)) * kBzCols, 0.0f);
-  for (int r = 0; r < R; ++r)
-    for (int j = 0; j < M1; ++j) tr[bz_index(j, r)] = z[size_t(r) * M1 + j];
+  const std::vector<float> tr = beta_z_image(z, h->M);
   upload(h, "beta_z", tr.data(), tr.size() * 4, size_t(t) * tr.size() * 4);
   HIPC(hipStreamSynchronize(h->stream));  // tr is a host temporary
 }
@@ -304,35 +281,12 @@ void ensure_sel0(mpcmmd_handle* h) {
   HIPC(hipMemcpyAsync(sel.data(), h->p.bsel, np * 4, hipMemcpyDeviceToHost, h->stream));
   HIPC(hipMemcpyAsync(sig.data(), h->p.bsig, kBetaSamples * 4, hipMemcpyDeviceToHost, h->stream));
   HIPC(hipStreamSynchronize(h->stream));
-  std::vector<int32_t> rp(M + 1, 0), pairs(2 * size_t(np));  // (i, sigma bits): one 8-byte load per pair
-  for (int i = 0; i < np; ++i) {
-    if (sel[i] < 0 || sel[i] >= M) throw std::runtime_error("first beta-iteration selection out of range");
-    ++rp[sel[i] + 1];
-  }
-  for (int r = 0; r < M; ++r) rp[r + 1] += rp[r];
-  std::vector<int32_t> fill(rp.begin(), rp.end() - 1);
-  for (int i = 0; i < np; ++i) {
-    const int at = fill[sel[i]]++;
-    pairs[2 * at] = i;
-    std::memcpy(&pairs[2 * at + 1], &sig[i / n], 4);
-  }
+  const Sel0Tables tab = first_selection_tables(sel.data(), sig.data(), n, M);
   upload(h, "sel0", sel.data(), np * 4);
   upload(h, "sig0", sig.data(), kBetaSamples * 4);
-  upload(h, "rp0", rp.data(), (M + 1) * 4);
-  upload(h, "rpair0", pairs.data(), size_t(np) * 8);
-  // k_bmoment_rows' row order: descending number of distinct sigmas among a
-  // row's pairs (its direct-sum rounds), so a wave's four rows need about the
-  // same number
-  std::vector<int32_t> perm(M), nsig(M, 0);
-  for (int r = 0; r < M; ++r) {
-    perm[r] = r;
-    std::vector<int32_t> sg;
-    for (int q = rp[r]; q < rp[r + 1]; ++q) sg.push_back(pairs[2 * q + 1]);
-    std::sort(sg.begin(), sg.end());
-    nsig[r] = int(std::unique(sg.begin(), sg.end()) - sg.begin());
-  }
-  std::stable_sort(perm.begin(), perm.end(), [&](int a, int c) { return nsig[a] > nsig[c]; });
-  upload(h, "rperm", perm.data(), size_t(M) * 4);
+  upload(h, "rp0", tab.rp.data(), (M + 1) * 4);
+  upload(h, "rpair0", tab.pairs.data(), size_t(np) * 8);
+  upload(h, "rperm", tab.rperm.data(), size_t(M) * 4);
   HIPC(hipStreamSynchronize(h->stream));  // host temporaries
   h->sel0_valid = true;
   ++h->sel0_gen;
@@ -525,19 +479,6 @@ void run_stage(mpcmmd_handle* h, int stage, int t) {
   }
 }
 
-template <class F>
-int guarded(F&& f) {
-  try {
-    return f();
-  } catch (const HipError& e) {
-    return fail(MPCMMD_E_HIP, e.what());
-  } catch (const std::invalid_argument& e) {
-    return fail(MPCMMD_E_INVALID, e.what());
-  } catch (const std::exception& e) {
-    return fail(MPCMMD_E_INVALID, e.what());
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -631,35 +572,11 @@ int mpcmmd_create_batch(const mpcmmd_config* cfg, int32_t max_configs, mpcmmd_ha
     if (h->carla && max_configs != 1)
       throw std::invalid_argument("CARLA handles solve one configuration (max_configs = 1)");
     // constants
-    std::vector<float> basis(3 * kNum * kNvar);
-    for (int i = 0; i < kNum * kNvar; ++i) {
-      basis[i] = float(h->pc.P[i]);
-      basis[kNum * kNvar + i] = float(h->pc.Pd[i]);
-      basis[2 * kNum * kNvar + i] = float(h->pc.Pdd[i]);
-    }
+    const std::vector<float> basis = pack_basis(h->pc);
     p.basis = (const float*)h->alloc("basis", basis.size() * 4);
-    // guess: c_bar = G v + h with G[k][j] = sum_i Kinv[k][i] (-k_p colsum_j[i])
-    std::vector<double> gg(2 * kNvar * 4);
-    for (int xy = 0; xy < 2; ++xy) {
-      const auto& Ki = xy == 0 ? h->pc.guess_kinv_x : h->pc.guess_kinv_y;
-      const auto& cs = xy == 0 ? h->pc.guess_colsum_x : h->pc.guess_colsum_y;
-      const int n = xy == 0 ? 14 : 15;
-      const double kp = xy == 0 ? h->pc.k_p_v : h->pc.k_p;
-      for (int k = 0; k < kNvar; ++k)
-        for (int j = 0; j < 4; ++j) {
-          double s = 0.0;
-          for (int i = 0; i < kNvar; ++i) s += Ki[k * n + i] * (-kp * cs[j * kNvar + i]);
-          gg[(xy * kNvar + k) * 4 + j] = s;
-        }
-    }
+    const std::vector<double> gg = pack_guess_g(h->pc);
     p.guess_g = (const double*)h->alloc("guess_g", gg.size() * 8);
-    std::vector<double> pm(2 * kNvar * kNvar);
-    for (int xy = 0; xy < 2; ++xy) {
-      const auto& Ki = xy == 0 ? h->pc.proj_kinv_x : h->pc.proj_kinv_y;
-      const int n = xy == 0 ? 14 : 15;
-      for (int k = 0; k < kNvar; ++k)
-        for (int j = 0; j < kNvar; ++j) pm[(xy * kNvar + k) * kNvar + j] = Ki[k * n + j];
-    }
+    const std::vector<double> pm = pack_proj_m(h->pc.proj_kinv_x, h->pc.proj_kinv_y);
     p.proj_m = (const double*)h->alloc("proj_m", pm.size() * 8);
     p.fit = (const double*)h->alloc("fit", h->pc.fit.size() * 8);
     p.solve_c = (const double*)h->alloc("solve_c", size_t(GM) * 4 * kNvar * 8);
@@ -716,13 +633,7 @@ int mpcmmd_create_batch(const mpcmmd_config* cfg, int32_t max_configs, mpcmmd_ha
       h->R0 = mmd_ok ? std::max(h->M, S) : S;
       // compute_cem_det's projection (projection_det.py:149-160): its own KKT
       det_projection_kinv(h->pc, O, h->det_kx, h->det_ky);
-      pm_det.assign(2 * kNvar * kNvar, 0.0);
-      for (int xy = 0; xy < 2; ++xy) {
-        const auto& Ki = xy == 0 ? h->det_kx : h->det_ky;
-        const int n = xy == 0 ? 14 : 15;
-        for (int k = 0; k < kNvar; ++k)
-          for (int j = 0; j < kNvar; ++j) pm_det[(xy * kNvar + k) * kNvar + j] = Ki[k * n + j];
-      }
+      pm_det = pack_proj_m(h->det_kx, h->det_ky);
       p.proj_m_det = (const double*)h->alloc("proj_m_det", pm_det.size() * 8);
       p.obs_full = (const float*)h->alloc("obs_full", size_t(GM) * 2 * O * kNum * 4);
       p.R0 = h->R0;
@@ -767,37 +678,30 @@ int mpcmmd_create_batch(const mpcmmd_config* cfg, int32_t max_configs, mpcmmd_ha
     if (BT >= 1024) h->groups = 2;
     // small batches on the per-iteration kernels (num_reduced > 16; CARLA n = 22 at
     // B = 100): two groups as well, for launches of 64..256 candidates
-    if (const char* g = std::getenv("MPCMMD_SMALL_GROUPS"))
-      h->small_groups = std::max(1, std::min(mpcmmd_handle::kMaxGroups, std::atoi(g)));
+    const int kMaxG = mpcmmd_handle::kMaxGroups, kNoMax = INT_MAX;
+    h->small_groups = env_clamped("MPCMMD_SMALL_GROUPS", h->small_groups, 1, kMaxG);
     if (BT >= 64 && BT <= 256) h->groups = std::max(h->groups, h->small_groups);
     h->groups_forced = std::getenv("MPCMMD_GROUPS") != nullptr;
-    if (const char* g = std::getenv("MPCMMD_GRAPH")) h->graphs = std::atoi(g) != 0;
-    if (const char* g = std::getenv("MPCMMD_AHEAD")) h->ahead_on = std::atoi(g) != 0;
-    if (const char* g = std::getenv("MPCMMD_FUSED")) h->fused_small = std::atoi(g) != 0;
-    if (const char* g = std::getenv("MPCMMD_SELECT_PREP")) h->prep_on = std::atoi(g) != 0;
+    h->graphs = env_flag("MPCMMD_GRAPH", h->graphs);
+    h->ahead_on = env_flag("MPCMMD_AHEAD", h->ahead_on);
+    h->fused_small = env_flag("MPCMMD_FUSED", h->fused_small);
+    h->prep_on = env_flag("MPCMMD_SELECT_PREP", h->prep_on);
     // the generators' variant is a property of the handle (its capacity), not
     // of a launch's candidate group: a candidate's bits do not depend on how
     // the batch is split into groups or whether k_bcem_small runs it
-    p.gen_wave = BT <= 512 && h->n <= 24;
-    if (const char* g = std::getenv("MPCMMD_GENWAVE")) p.gen_wave = std::atoi(g) != 0;
-    p.mom_rows = 1;
-    if (const char* g = std::getenv("MPCMMD_MOM_ROWS")) p.mom_rows = std::atoi(g) != 0;
+    p.gen_wave = env_flag("MPCMMD_GENWAVE", BT <= 512 && h->n <= 24);
+    p.mom_rows = env_flag("MPCMMD_MOM_ROWS", true);
     p.mom_amax = 1.0;  // == kSeriesAMax
     if (const char* g = std::getenv("MPCMMD_MOM_AMAX")) p.mom_amax = std::atof(g);
-    p.dir_pairs = 1;
-    if (const char* g = std::getenv("MPCMMD_DIR_PAIRS")) p.dir_pairs = std::atoi(g) != 0;
-    p.qp_small = 1;
-    if (const char* g = std::getenv("MPCMMD_QP_SMALL")) p.qp_small = std::atoi(g) != 0;
-    p.sel_cap = 64;
-    if (const char* g = std::getenv("MPCMMD_SEL_CAP")) p.sel_cap = std::max(1, std::atoi(g));
-    p.dir_waves = 4;
-    if (const char* g = std::getenv("MPCMMD_DIR_WAVES")) p.dir_waves = std::atoi(g);
-    p.ker_target = 128;  // parts per candidate only below 128 candidates per launch (B = 100: 8 -> 2 parts)
-    p.dir_target = 2048;
-    if (const char* g = std::getenv("MPCMMD_KER_TARGET")) p.ker_target = std::max(1, std::atoi(g));
-    if (const char* g = std::getenv("MPCMMD_DIR_TARGET")) p.dir_target = std::max(1, std::atoi(g));
-    if (const char* g = std::getenv("MPCMMD_BETA_DUMP")) p.beta_dump = std::atoi(g) != 0;
-    if (const char* g = std::getenv("MPCMMD_GROUPS")) h->groups = std::max(1, std::min(mpcmmd_handle::kMaxGroups, std::atoi(g)));
+    p.dir_pairs = env_flag("MPCMMD_DIR_PAIRS", true);
+    p.qp_small = env_flag("MPCMMD_QP_SMALL", true);
+    p.sel_cap = env_clamped("MPCMMD_SEL_CAP", 64, 1, kNoMax);
+    p.dir_waves = env_int("MPCMMD_DIR_WAVES", 4);
+    // parts per candidate only below 128 candidates per launch (B = 100: 8 -> 2 parts)
+    p.ker_target = env_clamped("MPCMMD_KER_TARGET", 128, 1, kNoMax);
+    p.dir_target = env_clamped("MPCMMD_DIR_TARGET", 2048, 1, kNoMax);
+    p.beta_dump = env_flag("MPCMMD_BETA_DUMP", p.beta_dump != 0);
+    h->groups = env_clamped("MPCMMD_GROUPS", h->groups, 1, kMaxG);
     if (h->groups > 1) {
       HIPC(hipEventCreateWithFlags(&h->gev_start, hipEventDisableTiming));
       for (int g = 0; g < h->groups; ++g) {
@@ -873,47 +777,6 @@ void* mpcmmd_get_stream(mpcmmd_handle* h) { return h ? (void*)h->stream : nullpt
 
 namespace {
 
-// CARLA per-solve setup (carla/optimizer/cem.py:248-264 mmd, 476-492 cvar):
-// R noisy initial states (compute_noisy_init_state(_baseline),
-// cem_helper.py:660-715; R = n^2 for mmd_opt, n for cvar) as rollout rows, and
-// the boundary vectors from the mean of their Frenet states
-// (global_to_frenet_vmap_1, cem_helper.py:348-388).  init_state is
-// init_state_global = (x, y, v, vdot, psi, psidot) (C/main_carla.py:352).
-void carla_rows(mpcmmd_handle* h, int cost_kind, int32_t idx_mpc, const float* is, const mpcmmd_path& path,
-                const mpcmmd_draws* draws, std::vector<float>& rows, double* bx, double* by) {
-  // compute_noisy_init_state / _baseline / _det (cem_helper.py:661-715): n^2, n or 1 rows
-  const int R = cost_kind == MPCMMD_COST_MMD_OPT ? h->M : cost_kind == MPCMMD_COST_DET ? 1 : h->S;
-  std::vector<float> eps;
-  if (draws && draws->init_eps) eps.assign(draws->init_eps, draws->init_eps + size_t(R) * 4);
-  else eps = host_normals(uint32_t(idx_mpc), h->cfg.seed, kStreamInitEps, 0, size_t(R) * 4);
-  const float x0 = is[0], y0 = is[1], v0 = is[2], vdot = is[3], psi0 = is[4], psidot = is[5];
-  const float vx = v0 * float(std::cos(double(psi0))), vy = v0 * float(std::sin(double(psi0)));
-  const float psi = float(std::atan2(double(vy), double(vx)));
-  const float mux = float(h->pc.init_mu_x), muy = float(h->pc.init_mu_y);
-  const float sgx = float(h->pc.init_sigma_x), sgy = float(h->pc.init_sigma_y);
-  rows.assign(size_t(h->R0) * 8, 0.0f);
-  PathView pv;
-  pv.P = path.num_path, pv.x = path.x_path, pv.y = path.y_path, pv.arc = path.arc_vec;
-  pv.Fxd = path.Fx_dot, pv.Fyd = path.Fy_dot, pv.kappa = path.kappa;
-  double sum[6] = {0, 0, 0, 0, 0, 0};
-  for (int r = 0; r < R; ++r) {
-    float* o = rows.data() + size_t(r) * 8;
-    o[0] = x0 + (eps[size_t(r) * 4] * sgx + mux);
-    o[1] = y0 + (eps[size_t(r) * 4 + 1] * sgy + muy);
-    o[2] = vx;
-    o[3] = vy;
-    o[4] = psi;
-    const float v = std::sqrt(vx * vx + vy * vy);
-    const FrenetState f = global_to_frenet(pv, o[0], o[1], v, vdot, psi, psidot);
-    const float vals[6] = {f.x, f.y, f.vx, f.vy, f.ax, f.ay};
-    for (int k = 0; k < 6; ++k) sum[k] += double(vals[k]);  // sequential (the oracle's cumsum order)
-  }
-  float m[6];
-  for (int k = 0; k < 6; ++k) m[k] = float(sum[k] / double(R));
-  bx[0] = m[0], bx[1] = m[2], bx[2] = m[4];
-  by[0] = m[1], by[1] = m[3], by[2] = m[5], by[3] = 0.0;
-}
-
 // mpcmmd_begin for n configurations (arrays with a leading configuration
 // axis); external draws only for n == 1 (the parity contract)
 int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc, const float* init_state,
@@ -982,48 +845,30 @@ int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t
     if (draws && draws->pop0) z0x.assign(draws->pop0, draws->pop0 + size_t(B) * 8);
     else if (h->pop0_normals.empty()) h->pop0_normals = host_normals(kFixedKey0, h->cfg.seed, kStreamPop0, 0, size_t(B) * 8);
     const std::vector<float>& z0 = draws && draws->pop0 ? z0x : h->pop0_normals;
-    std::vector<double> sc(size_t(G) * 4 * kNvar, 0.0);
-    std::vector<float> st0(size_t(G) * 8, 0.f), ob(size_t(G) * 2 * O * H), pop(size_t(G) * B * 8);
+    std::vector<double> sc(size_t(G) * 4 * kNvar);
+    std::vector<float> st0(size_t(G) * 8), ob(size_t(G) * 2 * O * H), pop(size_t(G) * B * 8);
     std::vector<float> rows0;  // CARLA noisy initial rows [R0][8]
+    const bool det = cost_kind == MPCMMD_COST_DET;  // the det projection's own KKT
+    const double* pkx = det ? h->det_kx.data() : h->pc.proj_kinv_x.data();
+    const double* pky = det ? h->det_ky.data() : h->pc.proj_kinv_y.data();
     for (int g = 0; g < G; ++g) {
       const float* is = init_state + size_t(g) * 6;
       // boundary vectors (cem_helper.py:152-167) and the per-solve KKT columns
       double bx[3] = {is[0], is[2], is[4]};
       double by[4] = {is[1], is[3], is[5], 0.0};
-      if (h->carla) carla_rows(h, cost_kind, idx_mpc[g], is, *path, draws, rows0, bx, by);
-      double* scg = sc.data() + size_t(g) * 4 * kNvar;
-      for (int k = 0; k < kNvar; ++k) {
-        for (int e = 0; e < 3; ++e) scg[0 * kNvar + k] += h->pc.guess_kinv_x[k * 14 + kNvar + e] * bx[e];
-        for (int e = 0; e < 4; ++e) scg[1 * kNvar + k] += h->pc.guess_kinv_y[k * 15 + kNvar + e] * by[e];
-        const bool det = cost_kind == MPCMMD_COST_DET;  // the det projection's own KKT
-        const double* pkx = det ? h->det_kx.data() : h->pc.proj_kinv_x.data();
-        const double* pky = det ? h->det_ky.data() : h->pc.proj_kinv_y.data();
-        for (int e = 0; e < 3; ++e) scg[2 * kNvar + k] += pkx[k * 14 + kNvar + e] * bx[e];
-        for (int e = 0; e < 4; ++e) scg[3 * kNvar + k] += pky[k * 15 + kNvar + e] * by[e];
+      if (h->carla) {
+        // compute_noisy_init_state / _baseline / _det (cem_helper.py:661-715): n^2, n or 1 rows
+        const int R = cost_kind == MPCMMD_COST_MMD_OPT ? h->M : det ? 1 : h->S;
+        const float* eps = draws ? draws->init_eps : nullptr;
+        std::vector<float> own;
+        if (!eps) own = host_normals(uint32_t(idx_mpc[g]), h->cfg.seed, kStreamInitEps, 0, size_t(R) * 4);
+        carla_rows(h->pc, R, h->R0, is, view_of(*path), eps ? eps : own.data(), rows0, bx, by);
       }
-      float* s0 = st0.data() + size_t(g) * 8;
-      s0[0] = is[0], s0[1] = is[1], s0[2] = is[2], s0[3] = is[3], s0[4] = atan2f(is[3], is[2]);
-      const float* xo = x_obs + size_t(g) * O * kNum;
-      const float* yo = y_obs + size_t(g) * O * kNum;
-      float* obg = ob.data() + size_t(g) * 2 * O * H;
-      for (int o = 0; o < O; ++o)
-        for (int t = 0; t < H; ++t) {
-          obg[size_t(o) * H + t] = xo[o * kNum + t];
-          obg[size_t(O) * H + o * H + t] = yo[o * kNum + t];
-        }
-      const float* mg = mean + size_t(g) * 8;
-      double cv[64], L[64];
-      for (int i = 0; i < 64; ++i) cv[i] = double(cov[size_t(g) * 64 + i]);
-      if (!chol8(cv, L)) throw std::invalid_argument("cov_param_init is not positive definite");
-      float* pg = pop.data() + size_t(g) * B * 8;
-      for (int b = 0; b < B; ++b)
-        for (int a = 0; a < 8; ++a) {
-          double s = double(mg[a]);
-          for (int c = 0; c <= a; ++c) s += L[a * 8 + c] * double(z0[size_t(b) * 8 + c]);
-          float v = float(s);
-          if (a < 4) v = fminf(fmaxf(v, 0.1f), 30.0f);
-          pg[size_t(b) * 8 + a] = v;
-        }
+      solve_columns(h->pc, pkx, pky, bx, by, sc.data() + size_t(g) * 4 * kNvar);
+      initial_state(is, st0.data() + size_t(g) * 8);
+      obstacle_transpose(x_obs + size_t(g) * O * kNum, y_obs + size_t(g) * O * kNum, O, H,
+                         ob.data() + size_t(g) * 2 * O * H);
+      initial_population(mean + size_t(g) * 8, cov + size_t(g) * 64, z0.data(), B, pop.data() + size_t(g) * B * 8);
     }
     upload_staged(h, "solve_c", sc.data(), sc.size() * 8);
     if (h->carla) {
@@ -1052,12 +897,7 @@ int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t
     h->ext_roll = draws && draws->roll;
     h->ext_res = draws && draws->resample;
     if (h->ext_roll) {
-      std::vector<float> r(size_t(T) * 3 * H * S);
-      for (int t = 0; t < T; ++t)
-        for (int k = 0; k < 3; ++k)
-          for (int s = 0; s < S; ++s)
-            for (int q = 0; q < H; ++q)
-              r[((size_t(t) * 3 + k) * H + q) * S + s] = draws->roll[((size_t(t) * 3 + k) * S + s) * H + q];
+      const std::vector<float> r = roll_transpose(draws->roll, T, S, H);
       upload_staged(h, "roll", r.data(), r.size() * 4);
     }
     if (h->ext_res) upload_staged(h, "resample", draws->resample, size_t(T) * (B - kElite) * 8 * 4);
@@ -1104,16 +944,7 @@ void read_result(mpcmmd_handle* h, int g, mpcmmd_result* out) {
     HIPC(hipMemcpy(st.data(), h->p.res_steer + (size_t(g) * T + h->last_t) * kNum, kNum * 4, hipMemcpyDeviceToHost));
     if (out->steering) std::memcpy(out->steering, st.data(), kNum * 4);
     HIPC(hipMemcpy(out->mean_param, h->p.mean + size_t(g) * 8, 8 * 4, hipMemcpyDeviceToHost));
-    if (out->v_best)
-      for (int i = 0; i < kNum; ++i) {  // v = sqrt((Pdot cx)^2 + (Pdot cy)^2), fp64 sums rounded once
-        double sx = 0.0, sy = 0.0;
-        for (int k = 0; k < kNvar; ++k) {
-          sx += h->pc.Pd[i * kNvar + k] * double(out->cx[k]);
-          sy += h->pc.Pd[i * kNvar + k] * double(out->cy[k]);
-        }
-        const float xd = float(sx), yd = float(sy);
-        out->v_best[i] = std::sqrt(xd * xd + yd * yd);
-      }
+    if (out->v_best) plan_speed(h->pc, out->cx, out->cy, out->v_best);
   }
   const int Tr = h->last_t + 1;
   if (out->elite_proj)
@@ -1160,11 +991,14 @@ int mpcmmd_iterate(mpcmmd_handle* h, int32_t t_begin, int32_t count) {
     };
     // graphs of a whole solve (count == T) or of single iterations (count ==
     // 1: all T captured at the first use, so no capture lands in a timed
-    // loop) on one stream -- the beta-CEM candidate groups of large mmd_opt
-    // batches fork onto other streams and are launched directly
-    const bool one_stream = h->cost != MPCMMD_COST_MMD_OPT || (h->p.Bt < 1024 && !h->groups_forced);
+    // loop), captured from the handle's stream.  mmd_opt launches of 64..256
+    // candidates run their beta-CEM candidate groups on the group streams
+    // inside the capture: run_beta_cem's event fork / join makes them parallel
+    // branches of the graph.  Launches of >= 1024 candidates, and any split
+    // forced by MPCMMD_GROUPS, are not captured: they are launched directly
+    const bool capturable = h->cost != MPCMMD_COST_MMD_OPT || (h->p.Bt < 1024 && !h->groups_forced);
     const bool whole = t_begin == 0 && count == h->T;
-    if (h->graphs && !h->prof && one_stream && (whole || count == 1)) {
+    if (h->graphs && !h->prof && capturable && (whole || count == 1)) {
       if (h->cost == MPCMMD_COST_MMD_OPT) ensure_sel0(h);  // host read-back: never inside a capture
       // key: ... and whether the first iteration's draws were drawn ahead (ai)
       auto key_of = [&](int tb, int cnt, int ai) {
@@ -1328,9 +1162,7 @@ int mpcmmd_global_to_frenet(const mpcmmd_path* path, int32_t count, const float*
   if (path->num_path < 2 || !path->x_path || !path->y_path || !path->arc_vec || !path->Fx_dot || !path->Fy_dot ||
       !path->kappa)
     return fail(MPCMMD_E_INVALID, "path: num_path >= 2 and six arrays");
-  PathView pv;
-  pv.P = path->num_path, pv.x = path->x_path, pv.y = path->y_path, pv.arc = path->arc_vec;
-  pv.Fxd = path->Fx_dot, pv.Fyd = path->Fy_dot, pv.kappa = path->kappa;
+  const PathView pv = view_of(*path);
   for (int i = 0; i < count; ++i) {
     const FrenetState f = global_to_frenet(pv, x[i], y[i], v[i], vdot[i], psi[i], psidot[i]);
     float* o = out + size_t(i) * 7;
@@ -1459,167 +1291,6 @@ int mpcmmd_host_constant(const mpcmmd_config* cfg, const char* name, double* dst
   } catch (const std::exception& e) {
     return fail(MPCMMD_E_INVALID, e.what());
   }
-}
-
-int mpcmmd_validate(const mpcmmd_validate_args* a) {
-  if (!a) return fail(MPCMMD_E_INVALID, "null argument");
-  const int K = a->num_cfg, O = a->num_obs, H = a->num_prime, R = a->num_rollouts;
-  if (K < 0 || R < 1 || !validate_shape_ok(O, H)) return fail(MPCMMD_E_INVALID, "validate: shape out of range");
-  if (a->noise != MPCMMD_NOISE_GAUSSIAN && a->noise != MPCMMD_NOISE_BETA) return fail(MPCMMD_E_INVALID, "noise");
-  if (a->variant != MPCMMD_VARIANT_STATIC && a->variant != MPCMMD_VARIANT_DYNAMIC)
-    return fail(MPCMMD_E_UNSUPPORTED,
-                "validate: static / dynamic variants (S/validation.py, D/validation.py); CARLA plans: "
-                "mpcmmd_validate_carla");
-  if (K == 0) return MPCMMD_OK;
-  if (!a->cx || !a->cy || !a->init_state || !a->x_obs || !a->y_obs || !a->keys || !a->count || !a->count_lane)
-    return fail(MPCMMD_E_INVALID, "null argument");
-  return guarded([&] {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) throw HipError("no HIP device visible");
-    if (a->device < 0 || a->device >= ndev) throw std::invalid_argument("device out of range");
-    HIPC(hipSetDevice(a->device));
-    const ProblemConsts pc = build_constants(H, a->variant);
-    std::vector<float> basis(2 * kNum * kNvar);
-    for (int i = 0; i < kNum * kNvar; ++i) {
-      basis[i] = float(pc.Pd[i]);
-      basis[kNum * kNvar + i] = float(pc.Pdd[i]);
-    }
-    std::vector<std::pair<void*, size_t>> bufs;
-    auto up = [&](const void* src, size_t bytes) -> void* {
-      void* d = nullptr;
-      HIPC(hipMalloc(&d, bytes));
-      bufs.push_back({d, bytes});
-      if (src) HIPC(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-      return d;
-    };
-    struct Free {
-      std::vector<std::pair<void*, size_t>>& b;
-      ~Free() {
-        for (auto& x : b) (void)hipFree(x.first);
-      }
-    } guard{bufs};
-    ValidateParams v{};
-    v.K = K, v.O = O, v.H = H, v.R = R, v.noise = a->noise;
-    v.noise_level = a->noise_level, v.acc_const = a->acc_const_noise, v.steer_const = a->steer_const_noise;
-    v.K_steer = pc.K_steer, v.y_lb = pc.y_lb, v.y_ub = pc.y_ub, v.seed = a->seed;
-    v.Pdot = (const float*)up(basis.data(), kNum * kNvar * 4);
-    v.Pddot = (const float*)up(basis.data() + kNum * kNvar, kNum * kNvar * 4);
-    v.cx = (const double*)up(a->cx, size_t(K) * 11 * 8);
-    v.cy = (const double*)up(a->cy, size_t(K) * 11 * 8);
-    v.init_state = (const double*)up(a->init_state, size_t(K) * 6 * 8);
-    v.x_obs = (const float*)up(a->x_obs, size_t(K) * O * 100 * 4);
-    v.y_obs = (const float*)up(a->y_obs, size_t(K) * O * 100 * 4);
-    v.draws = a->draws ? (const double*)up(a->draws, size_t(K) * 3 * R * H * 8) : nullptr;
-    v.keys = (const uint32_t*)up(a->keys, size_t(K) * 4);
-    v.count = (int32_t*)up(nullptr, size_t(K) * 4);
-    v.count_lane = (int32_t*)up(nullptr, size_t(K) * 4);
-    launch_validate(v, nullptr);
-    HIPC(hipGetLastError());
-    HIPC(hipDeviceSynchronize());
-    HIPC(hipMemcpy(a->count, v.count, size_t(K) * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(a->count_lane, v.count_lane, size_t(K) * 4, hipMemcpyDeviceToHost));
-    return MPCMMD_OK;
-  });
-}
-
-int mpcmmd_validate_carla(const mpcmmd_validate_carla_args* a) {
-  if (!a) return fail(MPCMMD_E_INVALID, "null argument");
-  const int K = a->num_cfg, O = a->num_obs, H = a->num_prime, R = a->num_rollouts, P = a->num_path;
-  if (K < 0 || K > 65535 || R < 1 || !validate_carla_shape_ok(O, H, P) || int64_t(R) * H >= (int64_t(1) << 31))
-    return fail(MPCMMD_E_INVALID, "validate_carla: shape out of range");
-  if (a->noise != MPCMMD_NOISE_GAUSSIAN && a->noise != MPCMMD_NOISE_BETA) return fail(MPCMMD_E_INVALID, "noise");
-  if (a->variant != MPCMMD_VARIANT_CARLA_TOWN05 && a->variant != MPCMMD_VARIANT_CARLA_TOWN10HD)
-    return fail(MPCMMD_E_INVALID, "validate_carla: a CARLA variant (static / dynamic optima: mpcmmd_validate)");
-  if (K == 0) return MPCMMD_OK;
-  if (!a->init_state || !a->v || !a->steer || !a->x_obs || !a->y_obs || !a->path || !a->keys || !a->count ||
-      !a->count_lane || !a->count_rows)
-    return fail(MPCMMD_E_INVALID, "null argument");
-  return guarded([&] {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) throw HipError("no HIP device visible");
-    if (a->device < 0 || a->device >= ndev) throw std::invalid_argument("device out of range");
-    HIPC(hipSetDevice(a->device));
-    int lds_max = 0;
-    HIPC(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, a->device));
-    if (validate_carla_lds(O, H, P) > size_t(lds_max))
-      return fail(MPCMMD_E_UNSUPPORTED, "validate_carla: the shape's workgroup needs " +
-                                            std::to_string(validate_carla_lds(O, H, P)) + " B of LDS, the device has " +
-                                            std::to_string(lds_max));
-    const ProblemConsts pc = build_constants(H, a->variant);
-    // the plan's controls (compute_controls, cem_helper.py: acc = diff([v, v_end]) / t) and the
-    // tick's initial state as carla_rows forms it
-    std::vector<float> acc(size_t(K) * H), steer(size_t(K) * H), st0(size_t(K) * 8, 0.0f);
-    for (int k = 0; k < K; ++k) {
-      const float* v = a->v + size_t(k) * kNum;
-      for (int h = 0; h < H; ++h) {
-        const float vn = h + 1 < kNum ? v[h + 1] : v[kNum - 1];
-        acc[size_t(k) * H + h] = (vn - v[h]) / 0.15f;  // prob.t (rollout.hpp: kDt)
-        steer[size_t(k) * H + h] = a->steer[size_t(k) * kNum + h];
-      }
-      const float* is = a->init_state + size_t(k) * 6;
-      const float v0 = is[2], psi0 = is[4];
-      const float vx = v0 * float(std::cos(double(psi0))), vy = v0 * float(std::sin(double(psi0)));
-      float* o = st0.data() + size_t(k) * 8;
-      o[0] = is[0], o[1] = is[1], o[2] = vx, o[3] = vy;
-      o[4] = float(std::atan2(double(vy), double(vx)));
-    }
-    std::vector<void*> bufs;
-    auto up = [&](const void* src, size_t bytes) -> void* {
-      void* d = nullptr;
-      HIPC(hipMalloc(&d, bytes));
-      bufs.push_back(d);
-      if (src) HIPC(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-      return d;
-    };
-    struct Free {
-      std::vector<void*>& b;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      ~Free() {
-        for (void* x : b) (void)hipFree(x);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-      }
-    } guard{bufs};
-    ValidateCarlaParams v{};
-    v.K = K, v.O = O, v.H = H, v.R = R, v.P = P, v.noise = a->noise, v.seed = a->seed;
-    v.sigma_acc = v.sigma_steer = a->noise_level;
-    v.K_steer = float(pc.K_steer * double(a->noise_level));
-    v.acc_const = a->acc_const_noise, v.steer_const = a->steer_const_noise;
-    v.y_lb = float(pc.y_lb), v.y_ub = float(pc.y_ub), v.wheel_base = float(pc.wheel_base);
-    v.obs_a2 = float(pc.a_obs * pc.a_obs), v.obs_b2 = float(pc.b_obs * pc.b_obs);
-    v.init_mu_x = float(pc.init_mu_x), v.init_mu_y = float(pc.init_mu_y);
-    v.init_sigma_x = float(pc.init_sigma_x), v.init_sigma_y = float(pc.init_sigma_y);
-    v.st0 = (const float*)up(st0.data(), st0.size() * 4);
-    v.acc = (const float*)up(acc.data(), acc.size() * 4);
-    v.steer = (const float*)up(steer.data(), steer.size() * 4);
-    v.x_obs = (const float*)up(a->x_obs, size_t(K) * O * kNum * 4);
-    v.y_obs = (const float*)up(a->y_obs, size_t(K) * O * kNum * 4);
-    v.path = (const float*)up(a->path, size_t(K) * 6 * P * 4);
-    v.draws = a->draws ? (const float*)up(a->draws, size_t(K) * 3 * R * H * 4) : nullptr;
-    v.init_eps = a->init_eps ? (const float*)up(a->init_eps, size_t(K) * R * 4 * 4) : nullptr;
-    v.keys = (const uint32_t*)up(a->keys, size_t(K) * 4);
-    // one allocation of the integer counters: count_oh | lane | count_rows | count | count_lane
-    const size_t n_oh = size_t(K) * O * H, n_lane = size_t(K) * 2 * H, n_all = n_oh + n_lane + size_t(3) * K;
-    int32_t* ctr = (int32_t*)up(nullptr, n_all * 4);
-    v.cnt_oh = ctr, v.cnt_lane = ctr + n_oh, v.count_rows = v.cnt_lane + n_lane;
-    v.count = v.count_rows + K, v.count_lane = v.count + K;
-    if (a->elapsed_ms) {
-      HIPC(hipEventCreate(&guard.e0));
-      HIPC(hipEventCreate(&guard.e1));
-      HIPC(hipEventRecord(guard.e0, nullptr));
-    }
-    HIPC(hipMemsetAsync(ctr, 0, n_all * 4, nullptr));
-    if (!launch_validate_carla(v, size_t(lds_max), nullptr)) throw std::logic_error("validate_carla: LDS check");
-    HIPC(hipGetLastError());
-    if (a->elapsed_ms) HIPC(hipEventRecord(guard.e1, nullptr));
-    HIPC(hipDeviceSynchronize());
-    if (a->elapsed_ms) HIPC(hipEventElapsedTime(a->elapsed_ms, guard.e0, guard.e1));
-    HIPC(hipMemcpy(a->count, v.count, size_t(K) * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(a->count_lane, v.count_lane, size_t(K) * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(a->count_rows, v.count_rows, size_t(K) * 4, hipMemcpyDeviceToHost));
-    if (a->count_oh) HIPC(hipMemcpy(a->count_oh, v.cnt_oh, n_oh * 4, hipMemcpyDeviceToHost));
-    return MPCMMD_OK;
-  });
 }
 
 int mpcmmd_obs_dynamic_traj(int32_t num_obs, const float* x0, const float* y0, const float* vx0, const float* vy0,

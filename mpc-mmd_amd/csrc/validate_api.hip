@@ -1,0 +1,149 @@
+// libmpcmmd: the two stand-alone Monte-Carlo validation entry points
+// (mpcmmd_validate, mpcmmd_validate_carla).  They use no handle: every call
+// allocates, uploads, launches one kernel and reads the counts back.
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "api_common.hpp"
+#include "kernels.hpp"
+#include "solve_host.hpp"
+
+using namespace mpcmmd;
+
+namespace {
+
+// the device visible and selected, or a throw
+void select_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) throw HipError("no HIP device visible");
+  if (device < 0 || device >= ndev) throw std::invalid_argument("device out of range");
+  HIPC(hipSetDevice(device));
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpcmmd_validate(const mpcmmd_validate_args* a) {
+  if (!a) return fail(MPCMMD_E_INVALID, "null argument");
+  const int K = a->num_cfg, O = a->num_obs, H = a->num_prime, R = a->num_rollouts;
+  if (K < 0 || R < 1 || !validate_shape_ok(O, H)) return fail(MPCMMD_E_INVALID, "validate: shape out of range");
+  if (a->noise != MPCMMD_NOISE_GAUSSIAN && a->noise != MPCMMD_NOISE_BETA) return fail(MPCMMD_E_INVALID, "noise");
+  if (a->variant != MPCMMD_VARIANT_STATIC && a->variant != MPCMMD_VARIANT_DYNAMIC)
+    return fail(MPCMMD_E_UNSUPPORTED,
+                "validate: static / dynamic variants (S/validation.py, D/validation.py); CARLA plans: "
+                "mpcmmd_validate_carla");
+  if (K == 0) return MPCMMD_OK;
+  if (!a->cx || !a->cy || !a->init_state || !a->x_obs || !a->y_obs || !a->keys || !a->count || !a->count_lane)
+    return fail(MPCMMD_E_INVALID, "null argument");
+  return guarded([&] {
+    select_device(a->device);
+    const ProblemConsts pc = build_constants(H, a->variant);
+    const std::vector<float> basis = pack_basis(pc);  // P, Pdot, Pddot
+    Scratch dev;
+    ValidateParams v{};
+    v.K = K, v.O = O, v.H = H, v.R = R, v.noise = a->noise;
+    v.noise_level = a->noise_level, v.acc_const = a->acc_const_noise, v.steer_const = a->steer_const_noise;
+    v.K_steer = pc.K_steer, v.y_lb = pc.y_lb, v.y_ub = pc.y_ub, v.seed = a->seed;
+    v.Pdot = (const float*)dev.up(basis.data() + kNum * kNvar, kNum * kNvar * 4);
+    v.Pddot = (const float*)dev.up(basis.data() + 2 * kNum * kNvar, kNum * kNvar * 4);
+    v.cx = (const double*)dev.up(a->cx, size_t(K) * 11 * 8);
+    v.cy = (const double*)dev.up(a->cy, size_t(K) * 11 * 8);
+    v.init_state = (const double*)dev.up(a->init_state, size_t(K) * 6 * 8);
+    v.x_obs = (const float*)dev.up(a->x_obs, size_t(K) * O * 100 * 4);
+    v.y_obs = (const float*)dev.up(a->y_obs, size_t(K) * O * 100 * 4);
+    v.draws = a->draws ? (const double*)dev.up(a->draws, size_t(K) * 3 * R * H * 8) : nullptr;
+    v.keys = (const uint32_t*)dev.up(a->keys, size_t(K) * 4);
+    v.count = (int32_t*)dev.up(nullptr, size_t(K) * 4);
+    v.count_lane = (int32_t*)dev.up(nullptr, size_t(K) * 4);
+    launch_validate(v, nullptr);
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipMemcpy(a->count, v.count, size_t(K) * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(a->count_lane, v.count_lane, size_t(K) * 4, hipMemcpyDeviceToHost));
+    return MPCMMD_OK;
+  });
+}
+
+int mpcmmd_validate_carla(const mpcmmd_validate_carla_args* a) {
+  if (!a) return fail(MPCMMD_E_INVALID, "null argument");
+  const int K = a->num_cfg, O = a->num_obs, H = a->num_prime, R = a->num_rollouts, P = a->num_path;
+  if (K < 0 || K > 65535 || R < 1 || !validate_carla_shape_ok(O, H, P) || int64_t(R) * H >= (int64_t(1) << 31))
+    return fail(MPCMMD_E_INVALID, "validate_carla: shape out of range");
+  if (a->noise != MPCMMD_NOISE_GAUSSIAN && a->noise != MPCMMD_NOISE_BETA) return fail(MPCMMD_E_INVALID, "noise");
+  if (a->variant != MPCMMD_VARIANT_CARLA_TOWN05 && a->variant != MPCMMD_VARIANT_CARLA_TOWN10HD)
+    return fail(MPCMMD_E_INVALID, "validate_carla: a CARLA variant (static / dynamic optima: mpcmmd_validate)");
+  if (K == 0) return MPCMMD_OK;
+  if (!a->init_state || !a->v || !a->steer || !a->x_obs || !a->y_obs || !a->path || !a->keys || !a->count ||
+      !a->count_lane || !a->count_rows)
+    return fail(MPCMMD_E_INVALID, "null argument");
+  return guarded([&] {
+    select_device(a->device);
+    int lds_max = 0;
+    HIPC(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, a->device));
+    if (validate_carla_lds(O, H, P) > size_t(lds_max))
+      return fail(MPCMMD_E_UNSUPPORTED, "validate_carla: the shape's workgroup needs " +
+                                            std::to_string(validate_carla_lds(O, H, P)) + " B of LDS, the device has " +
+                                            std::to_string(lds_max));
+    const ProblemConsts pc = build_constants(H, a->variant);
+    // the plan's controls and the tick's initial state as carla_rows forms it
+    std::vector<float> acc, steer, st0(size_t(K) * 8, 0.0f);
+    plan_controls(a->v, a->steer, K, H, acc, steer);
+    for (int k = 0; k < K; ++k) {
+      const float* is = a->init_state + size_t(k) * 6;
+      float* o = st0.data() + size_t(k) * 8;
+      o[0] = is[0], o[1] = is[1];
+      carla_velocity_heading(is[2], is[4], &o[2], &o[3], &o[4]);
+    }
+    struct Events {  // declared before the buffers: destroyed after they are freed
+      hipEvent_t e0 = nullptr, e1 = nullptr;
+      ~Events() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+      }
+    } ev;
+    Scratch dev;
+    ValidateCarlaParams v{};
+    v.K = K, v.O = O, v.H = H, v.R = R, v.P = P, v.noise = a->noise, v.seed = a->seed;
+    v.sigma_acc = v.sigma_steer = a->noise_level;
+    v.K_steer = float(pc.K_steer * double(a->noise_level));
+    v.acc_const = a->acc_const_noise, v.steer_const = a->steer_const_noise;
+    v.y_lb = float(pc.y_lb), v.y_ub = float(pc.y_ub), v.wheel_base = float(pc.wheel_base);
+    v.obs_a2 = float(pc.a_obs * pc.a_obs), v.obs_b2 = float(pc.b_obs * pc.b_obs);
+    v.init_mu_x = float(pc.init_mu_x), v.init_mu_y = float(pc.init_mu_y);
+    v.init_sigma_x = float(pc.init_sigma_x), v.init_sigma_y = float(pc.init_sigma_y);
+    v.st0 = (const float*)dev.up(st0.data(), st0.size() * 4);
+    v.acc = (const float*)dev.up(acc.data(), acc.size() * 4);
+    v.steer = (const float*)dev.up(steer.data(), steer.size() * 4);
+    v.x_obs = (const float*)dev.up(a->x_obs, size_t(K) * O * kNum * 4);
+    v.y_obs = (const float*)dev.up(a->y_obs, size_t(K) * O * kNum * 4);
+    v.path = (const float*)dev.up(a->path, size_t(K) * 6 * P * 4);
+    v.draws = a->draws ? (const float*)dev.up(a->draws, size_t(K) * 3 * R * H * 4) : nullptr;
+    v.init_eps = a->init_eps ? (const float*)dev.up(a->init_eps, size_t(K) * R * 4 * 4) : nullptr;
+    v.keys = (const uint32_t*)dev.up(a->keys, size_t(K) * 4);
+    // one allocation of the integer counters: count_oh | lane | count_rows | count | count_lane
+    const size_t n_oh = size_t(K) * O * H, n_lane = size_t(K) * 2 * H, n_all = n_oh + n_lane + size_t(3) * K;
+    int32_t* ctr = (int32_t*)dev.up(nullptr, n_all * 4);
+    v.cnt_oh = ctr, v.cnt_lane = ctr + n_oh, v.count_rows = v.cnt_lane + n_lane;
+    v.count = v.count_rows + K, v.count_lane = v.count + K;
+    if (a->elapsed_ms) {
+      HIPC(hipEventCreate(&ev.e0));
+      HIPC(hipEventCreate(&ev.e1));
+      HIPC(hipEventRecord(ev.e0, nullptr));
+    }
+    HIPC(hipMemsetAsync(ctr, 0, n_all * 4, nullptr));
+    if (!launch_validate_carla(v, size_t(lds_max), nullptr)) throw std::logic_error("validate_carla: LDS check");
+    HIPC(hipGetLastError());
+    if (a->elapsed_ms) HIPC(hipEventRecord(ev.e1, nullptr));
+    HIPC(hipDeviceSynchronize());
+    if (a->elapsed_ms) HIPC(hipEventElapsedTime(a->elapsed_ms, ev.e0, ev.e1));
+    HIPC(hipMemcpy(a->count, v.count, size_t(K) * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(a->count_lane, v.count_lane, size_t(K) * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(a->count_rows, v.count_rows, size_t(K) * 4, hipMemcpyDeviceToHost));
+    if (a->count_oh) HIPC(hipMemcpy(a->count_oh, v.cnt_oh, n_oh * 4, hipMemcpyDeviceToHost));
+    return MPCMMD_OK;
+  });
+}
+
+}  // extern "C"

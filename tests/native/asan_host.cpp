@@ -1,17 +1,28 @@
 // Host-code sanitizer harness ("run the CPU-side C++ under
 // ASan/UBSan").  Built by `make -C mpc-mmd_amd asan` with
 // -fsanitize=address,undefined from the library's own host sources
-// (csrc/host_constants.cpp), no GPU and no HIP runtime.  Exercises every
-// host-only entry: the batch-invariant constants of each variant and horizon
-// (mpcmmd_host_constant's builders) and the dynamic-obstacle QP trajectories
-// (mpcmmd_obs_dynamic_traj's builder), then prints one line per quantity
-// ("name count sum sumabs") for tests/test_asan_host.py to compare with the
-// product library's values.
+// (csrc/host_constants.cpp, carla_host.cpp, solve_host.cpp), no GPU and no HIP
+// runtime.  Exercises every host-only entry: the batch-invariant constants of
+// each variant and horizon (mpcmmd_host_constant's builders) and the
+// dynamic-obstacle QP trajectories (mpcmmd_obs_dynamic_traj's builder), then
+// prints one line per quantity ("name count sum sumabs") for
+// tests/test_asan_host.py to compare with the product library's values.
+//
+// Given a file name, it also writes there the inputs and results of the path
+// helpers (carla_host.cpp) and of every function of solve_host.cpp at the
+// smallest shapes where their indexing can go wrong, one array per line
+// ("name type count values..."), for tests/test_solve_host.py to hold against
+// the oracle.  Without a file name the same cases run, unrecorded.
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "../../mpc-mmd_amd/csrc/host_constants.hpp"
+#include "../../mpc-mmd_amd/csrc/layout.hpp"
+#include "../../mpc-mmd_amd/csrc/solve_host.hpp"
 
 using namespace mpcmmd;
 
@@ -24,7 +35,185 @@ static void emit(const char* tag, int H, int variant, const char* name, const st
   std::printf("%s %d %d %s %zu %.17g %.17g\n", tag, H, variant, name, v.size(), s, a);
 }
 
-int main() {
+static FILE* g_rec = nullptr;
+
+static void put(const std::string& name, const float* v, size_t n) {
+  if (!g_rec) return;
+  std::fprintf(g_rec, "%s f32 %zu", name.c_str(), n);
+  for (size_t i = 0; i < n; ++i) std::fprintf(g_rec, " %.9g", double(v[i]));
+  std::fprintf(g_rec, "\n");
+}
+static void put(const std::string& name, const double* v, size_t n) {
+  if (!g_rec) return;
+  std::fprintf(g_rec, "%s f64 %zu", name.c_str(), n);
+  for (size_t i = 0; i < n; ++i) std::fprintf(g_rec, " %.17g", v[i]);
+  std::fprintf(g_rec, "\n");
+}
+static void put(const std::string& name, const int32_t* v, size_t n) {
+  if (!g_rec) return;
+  std::fprintf(g_rec, "%s i32 %zu", name.c_str(), n);
+  for (size_t i = 0; i < n; ++i) std::fprintf(g_rec, " %d", v[i]);
+  std::fprintf(g_rec, "\n");
+}
+template <class T>
+static void put(const std::string& name, const std::vector<T>& v) {
+  put(name, v.data(), v.size());
+}
+
+// deterministic test inputs: uniform in [-1, 1), exact in fp32
+static uint32_t g_lcg = 12345u;
+static uint32_t rnd_u() {
+  g_lcg = g_lcg * 1664525u + 1013904223u;
+  return g_lcg >> 8;
+}
+static float rnd() { return float(int32_t(rnd_u() & 0xFFFF) - 32768) / 32768.0f; }
+static std::vector<float> rnd_vec(size_t n, float scale = 1.0f, float shift = 0.0f) {
+  std::vector<float> v(n);
+  for (float& x : v) x = rnd() * scale + shift;
+  return v;
+}
+
+// carla_host.cpp: a short path through smoothing, parameters and Frenet states
+struct TestPath {
+  std::vector<float> x, y, Fxd, Fyd, Fxdd, Fydd, arc, kappa;
+  PathView view() const {
+    return path_view(int(x.size()), x.data(), y.data(), arc.data(), Fxd.data(), Fyd.data(), kappa.data());
+  }
+};
+static TestPath path_case(int P) {
+  const std::string c = "path.P" + std::to_string(P) + "/";
+  std::vector<float> xw(P), yw(P);
+  for (int i = 0; i < P; ++i) {
+    xw[i] = 2.0f * float(i) + 0.25f * rnd();
+    yw[i] = 0.02f * float(i) * float(i) + 0.25f * rnd();
+  }
+  TestPath p;
+  for (auto* v : {&p.x, &p.y, &p.Fxd, &p.Fyd, &p.Fxdd, &p.Fydd, &p.arc, &p.kappa}) v->assign(P, 0.0f);
+  path_smoothing(P, xw.data(), yw.data(), 0.1f, p.x.data(), p.y.data());
+  float arc_length = 0.0f;
+  path_parameters(P, p.x.data(), p.y.data(), p.Fxd.data(), p.Fyd.data(), p.Fxdd.data(), p.Fydd.data(), p.arc.data(),
+                  p.kappa.data(), &arc_length);
+  const int N = 8;
+  std::vector<float> pts(size_t(N) * 6), fr(size_t(N) * 7);  // x, y, v, vdot, psi, psidot
+  const PathView pv = p.view();
+  for (int i = 0; i < N; ++i) {
+    float* q = &pts[size_t(i) * 6];
+    q[0] = float(P) * (rnd() + 1.0f), q[1] = 3.0f * rnd(), q[2] = 5.0f * (rnd() + 1.0f);
+    q[3] = rnd(), q[4] = 3.0f * rnd(), q[5] = 0.5f * rnd();
+    const FrenetState f = global_to_frenet(pv, q[0], q[1], q[2], q[3], q[4], q[5]);
+    const float o[7] = {f.x, f.y, f.vx, f.vy, f.ax, f.ay, f.psi};
+    for (int k = 0; k < 7; ++k) fr[size_t(i) * 7 + k] = o[k];
+  }
+  put(c + "x_wp", xw), put(c + "y_wp", yw), put(c + "x", p.x), put(c + "y", p.y);
+  put(c + "Fx_dot", p.Fxd), put(c + "Fy_dot", p.Fyd), put(c + "Fx_ddot", p.Fxdd), put(c + "Fy_ddot", p.Fydd);
+  put(c + "arc_vec", p.arc), put(c + "kappa", p.kappa), put(c + "arc_length", &arc_length, 1);
+  put(c + "points", pts), put(c + "frenet", fr);
+  return p;
+}
+
+// what mpcmmd_create_batch / mpcmmd_begin compute per handle and per
+// configuration, for a static handle of horizon H with O obstacles
+static void begin_case(int H, int O) {
+  const int B = 20, T = 1, S = 3;
+  const std::string c = "begin.H" + std::to_string(H) + ".O" + std::to_string(O) + "/";
+  const ProblemConsts pc = build_constants(H, 0);
+  put(c + "basis", pack_basis(pc));
+  put(c + "guess_g", pack_guess_g(pc));
+  put(c + "proj_m", pack_proj_m(pc.proj_kinv_x, pc.proj_kinv_y));
+  const std::vector<float> is = {0.5f + rnd(), 1.75f, 5.0f + rnd(), 0.25f * rnd(), 0.5f * rnd(), 0.5f * rnd()};
+  const double bx[3] = {is[0], is[2], is[4]}, by[4] = {is[1], is[3], is[5], 0.0};
+  std::vector<double> sc(4 * kNvar);
+  solve_columns(pc, pc.proj_kinv_x.data(), pc.proj_kinv_y.data(), bx, by, sc.data());
+  std::vector<float> st0(8, -1.0f);
+  initial_state(is.data(), st0.data());
+  const std::vector<float> xo = rnd_vec(size_t(O) * kNum, 50.0f, 60.0f), yo = rnd_vec(size_t(O) * kNum, 2.0f);
+  std::vector<float> ob(size_t(2) * O * H);
+  obstacle_transpose(xo.data(), yo.data(), O, H, ob.data());
+  // two populations: one around the reference's initial mean, one whose speeds meet both clips
+  const std::vector<float> z = rnd_vec(size_t(B) * 8, 3.0f);
+  std::vector<float> cov(64), w = rnd_vec(8);
+  for (int i = 0; i < 8; ++i)
+    for (int j = 0; j < 8; ++j) cov[i * 8 + j] = (i == j ? (i < 4 ? 20.0f : 100.0f) : 0.0f) + w[i] * w[j];
+  const float means[2][8] = {{15, 15, 15, 15, 0, 0, 0, 0}, {0.5f, 29.0f, 2.0f, 27.0f, 1.75f, -1.75f, 0.5f, 0}};
+  std::vector<float> pop(size_t(2) * B * 8);
+  for (int g = 0; g < 2; ++g) initial_population(means[g], cov.data(), z.data(), B, pop.data() + size_t(g) * B * 8);
+  const std::vector<float> roll = rnd_vec(size_t(T) * 3 * S * H);
+  put(c + "init_state", is), put(c + "solve_c", sc), put(c + "st0", st0);
+  put(c + "x_obs", xo), put(c + "y_obs", yo), put(c + "obs", ob);
+  put(c + "z", z), put(c + "cov", cov), put(c + "mean", &means[0][0], 16), put(c + "pop", pop);
+  put(c + "roll", roll), put(c + "roll_t", roll_transpose(roll.data(), T, S, H));
+  // a covariance that is not positive definite throws (and leaks nothing: the leak check runs at exit)
+  cov[3 * 8 + 3] = -1.0f;
+  int32_t threw = 0;
+  try {
+    initial_population(means[0], cov.data(), z.data(), B, pop.data());
+  } catch (const std::invalid_argument&) {
+    threw = 1;
+  }
+  put(c + "not_pd_threw", &threw, 1);
+  // a result's speeds and a validated plan's controls at this horizon
+  const std::vector<float> cx = rnd_vec(kNvar, 20.0f, 30.0f), cy = rnd_vec(kNvar, 2.0f);
+  std::vector<float> vb(kNum);
+  plan_speed(pc, cx.data(), cy.data(), vb.data());
+  const int K = 2;
+  const std::vector<float> v = rnd_vec(size_t(K) * kNum, 5.0f, 10.0f), steer = rnd_vec(size_t(K) * kNum, 0.3f);
+  std::vector<float> acc, steer_h;
+  plan_controls(v.data(), steer.data(), K, H, acc, steer_h);
+  put(c + "cx", cx), put(c + "cy", cy), put(c + "v_best", vb);
+  put(c + "plan_v", v), put(c + "plan_steer", steer), put(c + "plan_acc", acc), put(c + "plan_steer_h", steer_h);
+}
+
+// mpcmmd_carla_begin's rows and KKT columns for R = 1 (det), n (cvar), n^2 (mmd_opt)
+static void carla_case(int n, int H, int O, const TestPath& path) {
+  const ProblemConsts pc = build_constants(H, 2);
+  std::vector<double> det_kx, det_ky;
+  det_projection_kinv(pc, O, det_kx, det_ky);
+  const int M = n * n;
+  for (int R : {1, n, M}) {
+    const std::string c = "carla.n" + std::to_string(n) + ".R" + std::to_string(R) + "/";
+    const std::vector<float> is = {1.0f + rnd(), 0.3f * rnd(), 6.0f + rnd(), 0.2f * rnd(), 0.1f * rnd(), 0.02f * rnd()};
+    const std::vector<float> eps = rnd_vec(size_t(R) * 4, 2.0f);
+    std::vector<float> rows;
+    double bx[3], by[4];
+    carla_rows(pc, R, M, is.data(), path.view(), eps.data(), rows, bx, by);
+    const bool det = R == 1;
+    std::vector<double> sc(4 * kNvar);
+    solve_columns(pc, det ? det_kx.data() : pc.proj_kinv_x.data(), det ? det_ky.data() : pc.proj_kinv_y.data(), bx, by,
+                  sc.data());
+    float vh[3];
+    carla_velocity_heading(is[2], is[4], &vh[0], &vh[1], &vh[2]);
+    put(c + "init_state", is), put(c + "eps", eps), put(c + "rows", rows), put(c + "bx", bx, 3), put(c + "by", by, 4);
+    put(c + "solve_c", sc), put(c + "velocity_heading", vh, 3);
+    if (det) put(c + "proj_m_det", pack_proj_m(det_kx, det_ky));
+  }
+}
+
+// the first-selection tables and the beta_z image of an n^2-row mother set:
+// mother row 0 has no pair, row 1's pairs all carry one sigma
+static void beta_case(int n) {
+  const int M = n * n, np = kBetaSamples * n;
+  const std::string c = "beta.n" + std::to_string(n) + "/";
+  std::vector<int32_t> sel(np);
+  std::vector<float> sig(kBetaSamples);
+  for (int s = 0; s < kBetaSamples; ++s) sig[s] = s < 10 ? 1.0f : 0.25f * float(1 + s % 7);
+  for (int i = 0; i < np; ++i) sel[i] = i / n < 10 ? 1 + i % 3 : 2 + int(rnd_u() % uint32_t(M - 2));
+  const Sel0Tables t = first_selection_tables(sel.data(), sig.data(), n, M);
+  put(c + "sel", sel), put(c + "sig", sig), put(c + "rp0", t.rp), put(c + "rpair0", t.pairs), put(c + "rperm", t.rperm);
+  int32_t threw = 0;
+  sel[np - 1] = M;  // one past the last mother row
+  try {
+    (void)first_selection_tables(sel.data(), sig.data(), n, M);
+  } catch (const std::runtime_error&) {
+    threw = 1;
+  }
+  put(c + "range_threw", &threw, 1);
+  const int M1 = M + 1, R = kBetaSamples - kBetaElite;
+  std::vector<float> z(size_t(R) * M1);
+  for (size_t i = 0; i < z.size(); ++i) z[i] = float(i + 1);  // distinct and non-zero
+  put(c + "beta_z", beta_z_image(z.data(), M));
+}
+
+int main(int argc, char** argv) {
   for (int variant = 0; variant < 4; ++variant) {
     for (int H : {2, 8, 20, 30, 50, 60, 100}) {
       if (variant >= 2 && H > 100) continue;
@@ -52,5 +241,18 @@ int main() {
   std::vector<double> xs(xt.begin(), xt.end()), ys(yt.begin(), yt.end());
   emit("dyn", 0, 1, "x_traj", xs);
   emit("dyn", 0, 1, "y_traj", ys);
+
+  if (argc > 1 && !(g_rec = std::fopen(argv[1], "w"))) {
+    std::perror(argv[1]);
+    return 2;
+  }
+  const TestPath p4 = path_case(4), p50 = path_case(50);
+  begin_case(2, 1);
+  begin_case(100, 32);
+  carla_case(2, 2, 1, p4);
+  carla_case(4, 100, 32, p50);
+  carla_case(6, 100, 32, p50);
+  for (int n : {2, 4, 6}) beta_case(n);
+  if (g_rec) std::fclose(g_rec);
   return 0;
 }

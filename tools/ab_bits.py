@@ -1,8 +1,10 @@
 """Bit comparison of two library builds on the bench workloads (GPU box):
     python tools/ab_bits.py LIB_A LIB_B [workload ...]
 Each build runs one full solve (T = 20 iterations) of every workload in its
-own process (MPCMMD_LIB), every output array of mpcmmd_finish is saved, and
-the two sets are compared bit for bit."""
+own process (MPCMMD_LIB), every output array of mpcmmd_finish and every device
+buffer the library's host arithmetic fills (mpcmmd_begin's uploads, the beta
+tables, the first-selection tables) is saved, and the two sets are compared
+bit for bit."""
 import os
 import subprocess
 import sys
@@ -23,11 +25,18 @@ for name in {names!r}:
                               num_batch=w["num_batch"], maxiter_cem=20, device=0, seed=0, variant=w.get("variant", "static"))
     h = _native.Handle(cfg)
     h.begin(w["cost"], inst["idx_mpc"], inst["init"], inst["mean"], inst["cov"], inst["xo"], inst["yo"], inst["v_des"])
+    # what begin's host arithmetic uploaded, before the iterations overwrite it
+    for buf, dt in (("solve_c", np.float64), ("st0", np.float32), ("obs", np.float32), ("pop", np.float32),
+                    ("mean", np.float32), ("cov", np.float32)):
+        out[name + "/" + buf] = h.read(buf, dt).copy()
     h.iterate(0, 20)
     res = h.finish(trace=True)
     for k, v in res.items():
         out[name + "/" + k] = np.asarray(v)
-    out[name + "/pop"] = h.read("pop").copy()
+    out[name + "/pop_end"] = h.read("pop").copy()
+    if w["cost"] == "mmd_opt":  # the beta tables and the first selection's tables (integers: no NaN aliasing)
+        for buf in ("beta_z0", "beta_z", "sel0", "sig0", "rp0", "rpair0", "rperm"):
+            out[name + "/" + buf] = h.read(buf, np.int32).copy()
     h.close()
 np.savez("{path}", **out)
 '''
