@@ -21,8 +21,10 @@
 // the host splits the batch into groups, each on its own stream, so the
 // kernels of different groups (bound by different units: MFMA, exp, fp64
 // FMA latency, LDS) run side by side.  Every supported size n <= 64
-// (M = n^2 <= 4096) takes the same kernels; the LDS-resident pieces are sized
-// at launch (ker_lds, dir_lds, elite_lds).
+// (M = n^2 <= 4096) takes these per-iteration kernels, their LDS-resident
+// pieces sized at launch (ker_lds, dir_lds, elite_lds) -- except handles of
+// <= 512 candidates at n <= 16 (M <= 256), whose 20 beta-iterations run in one
+// launch of the fused k_bcem_small (bcem_small_ok), the same phase bodies.
 //
 // The covariance of the beta-CEM is rank <= 10 plus 0.05 I
 // (jnp.cov of 11 elites, compute_beta.py:61).  Its Cholesky factor is never
@@ -137,7 +139,7 @@ DEVI double quad_sum(double v) {
 // launch sizing
 constexpr int kXcds = 8;   // workgroups are dealt round-robin to the 8 XCDs by linear id
 constexpr int kCUs = 256;  // MI355X compute units (launch sizing only)
-constexpr int kKerWaves = 16;  // waves per k_bkernel workgroup
+constexpr int kKerWaves = 16;  // waves per k_bkernel workgroup (and of k_bcem_small, which runs its body)
 constexpr int kDirWaves = 4;   // waves per k_bdirect / k_bdirect_pairs workgroup
 constexpr int kLptBins = 128;  // pair counts per distinct row (<= 100 samples)
 // the series of a K_mixed row sum (k_bmoment's records, summed by k_bkernel)
@@ -192,7 +194,7 @@ HDI KerLds ker_lds(int M, int n, size_t scratch) {
   L.total = take.o;
   return L;
 }
-HDI size_t ker_sample_bytes(int n, int nw = kKerWaves) { return size_t(nw) * n * kFeatStride * 4; }
+HDI size_t ker_sample_bytes(int n) { return size_t(kKerWaves) * n * kFeatStride * 4; }
 HDI size_t ker_tab_bytes(int U) { return ((size_t(U) * (U - 1) / 2 * 4 + 15) & ~size_t(15)) + size_t(U) * kFeatStride * 4; }
 constexpr size_t kKerTabBytes = 55 * 1024;  // the table of a union of <= 144 rows
 // scratch: the series records of every mother row (up to kKerRecBytes;
@@ -200,8 +202,8 @@ constexpr size_t kKerTabBytes = 55 * 1024;  // the table of a union of <= 144 ro
 // kKerTabBytes) from the second beta-iteration on (the first one's 100 fresh
 // samples select nearly every mother row)
 constexpr size_t kKerRecBytes = 64 * 1024;
-HDI size_t ker_scratch(int M, int n, int tb, int nw = kKerWaves) {
-  size_t sc = ker_sample_bytes(n, nw);
+HDI size_t ker_scratch(int M, int n, int tb) {
+  size_t sc = ker_sample_bytes(n);
   size_t rec = size_t(M) * kMomStride * 4;
   if (rec > kKerRecBytes) rec = kKerRecBytes;
   if (rec > sc) sc = rec;

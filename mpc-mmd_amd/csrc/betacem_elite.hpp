@@ -249,125 +249,92 @@ DEVI double rsq_nr(double d) {
   return y;
 }
 
-// NB blocks blk0, blk0 + bstride, ... of candidate b on the calling wave, their
-// pivot chains interleaved (independent: the same bits as one block per
-// wave); blocks >= nblk compute on the last block and store nothing.  xl: the
-// wave's 32 NB doubles of LDS.
-template <int NB>
-DEVI void bgen_wave(const Params& p, int b, int blk0, int bstride, double* xl) {
+// Block blk (< nblk) of candidate b on the calling wave.  xl: the wave's 32
+// doubles of LDS.
+DEVI void bgen_wave(const Params& p, int b, int blk, double* xl) {
   const int M = p.M, M1 = M + 1, nblk = (M1 + 15) / 16, Pp = pos_pad(M);
   const int lane = tidx() & 63, r = lane & 15, h = lane >> 4;
   double* gen = p.gen + size_t(b) * Pp * kGenStride;
   double* gm = p.genm + size_t(b) * Pp;
-  int j0[NB];
-  bool live[NB];
-  d4 A[NB];
-  double U[NB][3];
+  const int j0 = blk * 16;
+  d4 A;
+  double U[3];
+  const double* Gb = p.phib + (size_t(b) * nblk + blk) * 66;
 #pragma unroll
-  for (int t = 0; t < NB; ++t) {
-    const int blk = blk0 + t * bstride;
-    live[t] = blk < nblk;
-    const int bc = live[t] ? blk : nblk - 1;
-    j0[t] = bc * 16;
-    const double* Gb = p.phib + (size_t(b) * nblk + bc) * 66;
+  for (int i = 0; i < 4; ++i) {
+    const int a = h + 4 * i;
+    A[i] = a < 11 && r < 11 ? Gb[sym11i(min(a, 10), min(r, 10))] : 0.0;
+  }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int a = h + 4 * i;
-      A[t][i] = a < 11 && r < 11 ? Gb[sym11i(min(a, 10), min(r, 10))] : 0.0;
-    }
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      const int f = 4 * s + h;  // feature 11 is the mean's slot: zero here
-      U[t][s] = f < 11 && j0[t] + r < M1 ? gen[gen_uplane(Pp) + size_t(j0[t] + r) * kGenRow + f] : 0.0;
-    }
+  for (int s = 0; s < 3; ++s) {
+    const int f = 4 * s + h;  // feature 11 is the mean's slot: zero here
+    U[s] = f < 11 && j0 + r < M1 ? gen[gen_uplane(Pp) + size_t(j0 + r) * kGenRow + f] : 0.0;
   }
   // sweep: A_kk <- -1/d, A_ik = A_ki <- A_ik / d, A_ij <- A_ij - A_ik A_kj / d
 #pragma unroll
   for (int k = 0; k < 11; ++k) {
     if (r == k) {
 #pragma unroll
-      for (int t = 0; t < NB; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) xl[32 * t + h + 4 * i] = A[t][i];
+      for (int i = 0; i < 4; ++i) xl[h + 4 * i] = A[i];
     }
     wave_sync();
-    double d[NB], cr[NB], ci[NB][4];
+    const double d = xl[k], cr = xl[r];
+    double ci[4];
 #pragma unroll
-    for (int t = 0; t < NB; ++t) {
-      d[t] = xl[32 * t + k];
-      cr[t] = xl[32 * t + r];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) ci[t][i] = xl[32 * t + h + 4 * i];
-    }
+    for (int i = 0; i < 4; ++i) ci[i] = xl[h + 4 * i];
     wave_sync();
+    const double id = rcp_nr(d);
 #pragma unroll
-    for (int t = 0; t < NB; ++t) {
-      const double id = rcp_nr(d[t]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int a = h + 4 * i;
-        A[t][i] = a == k ? (r == k ? -id : cr[t] * id) : (r == k ? ci[t][i] * id : A[t][i] - (ci[t][i] * cr[t]) * id);
-      }
+    for (int i = 0; i < 4; ++i) {
+      const int a = h + 4 * i;
+      A[i] = a == k ? (r == k ? -id : cr * id) : (r == k ? ci[i] * id : A[i] - (ci[i] * cr) * id);
     }
   }
   const d4 zero = d4{0.0, 0.0, 0.0, 0.0};
-  d4 V[NB], G[NB];
 #pragma unroll
-  for (int t = 0; t < NB; ++t) {
+  for (int i = 0; i < 4; ++i) A[i] = -A[i];
+  d4 V = zero, G = zero;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) A[t][i] = -A[t][i];
-    V[t] = zero;
-    G[t] = zero;
+  for (int s = 0; s < 3; ++s) V = mfma64(A[s], U[s], V);
 #pragma unroll
-    for (int s = 0; s < 3; ++s) V[t] = mfma64(A[t][s], U[t][s], V[t]);
+  for (int s = 0; s < 3; ++s) G = mfma64(U[s], V[s], G);
 #pragma unroll
-    for (int s = 0; s < 3; ++s) G[t] = mfma64(U[t][s], V[t][s], G[t]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (h + 4 * i == r) G[t][i] = G[t][i] + kRidge;
-  }
+  for (int i = 0; i < 4; ++i)
+    if (h + 4 * i == r) G[i] = G[i] + kRidge;
 #pragma unroll
   for (int k = 0; k < 16; ++k) {
     if (r == k) {
 #pragma unroll
-      for (int t = 0; t < NB; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          xl[32 * t + h + 4 * i] = G[t][i];
-          xl[32 * t + 16 + h + 4 * i] = V[t][i];
-        }
-    }
-    wave_sync();
-    double d[NB], gr[NB], gi[NB][4], vi[NB][4];
-#pragma unroll
-    for (int t = 0; t < NB; ++t) {
-      d[t] = xl[32 * t + k];
-      gr[t] = xl[32 * t + r];
-#pragma unroll
       for (int i = 0; i < 4; ++i) {
-        gi[t][i] = xl[32 * t + h + 4 * i];
-        vi[t][i] = xl[32 * t + 16 + h + 4 * i];
+        xl[h + 4 * i] = G[i];
+        xl[16 + h + 4 * i] = V[i];
       }
     }
     wave_sync();
+    const double d = xl[k], gr = xl[r];
+    double gi[4], vi[4];
 #pragma unroll
-    for (int t = 0; t < NB; ++t) {
-      const double rl = rsq_nr(d[t]);
-      const double lr = r > k ? gr[t] * rl : 0.0;
-      double wk[4];
+    for (int i = 0; i < 4; ++i) {
+      gi[i] = xl[h + 4 * i];
+      vi[i] = xl[16 + h + 4 * i];
+    }
+    wave_sync();
+    const double rl = rsq_nr(d);
+    const double lr = r > k ? gr * rl : 0.0;
+    double wk[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const double li = h + 4 * i > k ? gi[t][i] * rl : 0.0;
-        wk[i] = vi[t][i] * rl;
-        G[t][i] = G[t][i] - li * lr;
-        V[t][i] = V[t][i] - wk[i] * lr;
-      }
-      if (live[t] && r == k && j0[t] + k < M1) {
-        double* g = gen + size_t(j0[t] + k) * kGenRow + kGenW;
+    for (int i = 0; i < 4; ++i) {
+      const double li = h + 4 * i > k ? gi[i] * rl : 0.0;
+      wk[i] = vi[i] * rl;
+      G[i] = G[i] - li * lr;
+      V[i] = V[i] - wk[i] * lr;
+    }
+    const int j = j0 + k;  // the pivot's position
+    if (r == k && j < M1) {
+      double* g = gen + size_t(j) * kGenRow + kGenW;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) g[h + 4 * i] = h + 4 * i < 11 ? wk[i] : 0.0;  // whole rows: slot 11 is 0
-        if (h == 0) gm[j0[t] + k] = d[t] * rl;  // L_jj
-      }
+      for (int i = 0; i < 3; ++i) g[h + 4 * i] = h + 4 * i < 11 ? wk[i] : 0.0;  // whole rows: slot 11 is 0
+      if (h == 0) gm[j] = d * rl;  // L_jj
     }
   }
 }

@@ -89,16 +89,15 @@ DEVI float series_sum(const float4 (&q)[3], double na) {
 static_assert(kMomR == 12 && kMom == 12, "record layout: P_0..P_11 in float4s 0..2, R in float4 3");
 
 // The body of k_bkernel for part `part` of candidate `cand` (of `split`),
-// NW waves (k_bkernel: 16; the small-batch fused kernel k_bcem_small: 8)
+// kKerWaves waves (k_bkernel and the small-batch fused kernel k_bcem_small).
 // mom_l / feat_l: LDS copies of the candidate's series records and feature
 // rows (k_bcem_small, which keeps them for its 20 beta-iterations), else null
 // (read from global memory).  kList: also append the flagged pairs to the
 // candidate's list (k_bdirect_pairs).  kFlat: the K_red table lookups spread
 // over every thread (k_bcem_small) instead of a wave per sample (k_bkernel)
-template <int NW, bool kList, bool kFlat>
+template <bool kList, bool kFlat>
 DEVI void bkernel_body(const Params& p, int tb, int cand, int part, int split, int scratch, char* smem,
                        const float4* mom_l = nullptr, const float4* feat_l = nullptr) {
-  constexpr int kKerWaves = NW;
   constexpr int NT = 64 * kKerWaves, Q = kFeatStride / 4;
   const int b = p.b0 + cand, M = p.M, n = p.n;
   const int tid = tidx(), lane = tid & 63;
@@ -370,7 +369,7 @@ DEVI int bdirect_total(const Params& p, int b, int kparts) {
 }
 
 // The body of k_bdirect for part `part` of candidate `cand` with `total` > 0
-// flagged pairs, NW waves (k_bdirect: 4; k_bcem_small: 8)
+// flagged pairs, NW waves (k_bdirect: kDirWaves = 4; k_bcem_small: 16)
 template <int NV4, int NW>
 DEVI void bdirect_body(const Params& p, int tb, int split, int lpt, int cand, int part, int total, char* smem) {
   constexpr int kDirWaves = NW;

@@ -28,18 +28,20 @@ namespace {
 // and chunk), selection by bselect_wave, kernel sums / K_red by bkernel_body,
 // direct row sums by bdirect_body, the QPs by bqp_solve (a quad each), elites by
 // belite_body, generators by bgen_wave, sigma_best by bsigma_body.
-// W = 16 waves (1024 threads, <= 128 VGPRs) for n <= 16, else 8 (the QPs of
-// n > 16 need up to 256 VGPRs): small_waves.
-HDI size_t small_sel_bytes(int R) { return size_t(64 * R + 8) * 8 + 64 * 4 + 128 * 4; }  // one wave's select LDS
-HDI size_t small_lds(int M, int n, int R, int W) {
-  size_t b = size_t(W) * small_sel_bytes(R) + size_t(kNew) * ygen_stride(M) * 4;  // + the staged sample rows
-  const size_t k = ker_lds(M, n, ker_scratch(M, n, 1, W)).total;
-  const size_t d = dir_lds(M, n).total, e = elite_lds(M + 1, W).total;
+// Only for n <= 16 (M <= 256, bcem_small_ok), where every phase fits 128
+// VGPRs (the QPs of n > 16 need up to 256): kSmallWaves = kKerWaves = 16 waves
+// (1024 threads), and the selection is k_bselect's (R, G) = (1, 32) of n <= 24.
+constexpr int kSmallWaves = kKerWaves, kSmallThreads = 64 * kSmallWaves;
+constexpr int kSmallSelR = 1, kSmallSelG = 32;
+constexpr size_t kSmallCandBytes = size_t(64 * kSmallSelR + 8) * 8;     // select_walk's cand
+constexpr size_t kSmallSelBytes = kSmallCandBytes + 64 * 4 + 128 * 4;  // one wave's select LDS: cand, lm, scratch
+HDI size_t small_lds(int M, int n) {
+  size_t b = kSmallWaves * kSmallSelBytes + size_t(kNew) * ygen_stride(M) * 4;  // + the staged sample rows
+  const size_t k = ker_lds(M, n, ker_scratch(M, n, 1)).total;  // (>= kKerTabBytes: covers bgen_wave's pivot columns)
+  const size_t d = dir_lds(M, n).total, e = elite_lds(M + 1, kSmallWaves).total;
   const size_t q = (size_t(kBetaSamples) * tri_stride(n) + kQpZeros) * 4;  // the QPs' K_red and zeros
-  const size_t g = size_t(W) * 4 * 32 * 8;                        // bgen_wave<4>'s pivot columns
   const size_t gl = ((gen_lds_bytes(M) + 15) & ~size_t(15)) + tblk_lds_bytes(M);  // the sampler's copy + T blocks
   b = b > q ? b : q;
-  b = b > g ? b : g;
   b = b > gl ? b : gl;
   b = b > k ? b : k;
   b = b > d ? b : d;
@@ -48,7 +50,7 @@ HDI size_t small_lds(int M, int n, int R, int W) {
 }
 
 // the persistent LDS copies (k_bcem_small's persist): after the phases' space
-HDI size_t small_persist_off(int M, int n, int R, int W) { return (small_lds(M, n, R, W) + 15) & ~size_t(15); }
+HDI size_t small_persist_off(int M, int n) { return (small_lds(M, n) + 15) & ~size_t(15); }
 HDI size_t small_persist_bytes(int M) { return size_t(M) * (kMomStride + kFeatStride) * 4; }
 
 // phase stamps of beta-iteration 5 (MPCMMD_STAMPW; rows 32768 + workgroup,
@@ -59,9 +61,9 @@ HDI size_t small_persist_bytes(int M) { return size_t(M) * (kMomStride + kFeatSt
       (p).dbgw[size_t(32768 + blockIdx.x) * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); \
   } while (0)
 
-template <int NQ, int R, int G, int NP, int NV4, int GNB, int W>
-__global__ __launch_bounds__(64 * W) void k_bcem_small(Params p0, int persist) {
-  constexpr int kSmallWaves = W, kSmallThreads = 64 * W;
+// NQ: select_walk's keys per lane (M <= 64 NQ); NP: bqp_solve's padded size
+template <int NQ, int NP>
+__global__ __launch_bounds__(kSmallThreads) void k_bcem_small(Params p0, int persist) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int cand = blockIdx.x;
   const int tid = tidx();
@@ -73,7 +75,7 @@ __global__ __launch_bounds__(64 * W) void k_bcem_small(Params p0, int persist) {
   const float4* feat_l = nullptr;
   if (persist) {
     const int M = p0.M, b = p0.b0 + cand;
-    float4* pm = reinterpret_cast<float4*>(smem + small_persist_off(M, p0.n, R, W));
+    float4* pm = reinterpret_cast<float4*>(smem + small_persist_off(M, p0.n));
     float4* pf = pm + M * (kMomStride / 4);
     const float4* gm = reinterpret_cast<const float4*>(p0.bmom + size_t(b) * M * kMomStride);
     const float4* gf = reinterpret_cast<const float4*>(p0.featr + size_t(b) * M * kFeatStride);
@@ -122,17 +124,17 @@ __global__ __launch_bounds__(64 * W) void k_bcem_small(Params p0, int persist) {
       // bselect_wave's walk (samples first_sample(tb) = 11 .. 99: the elites'
       // selections were carried) on the staged rows
       const int ys = ygen_stride(M);
-      const float* Yl = reinterpret_cast<const float*>(smem + size_t(kSmallWaves) * small_sel_bytes(R));
+      const float* Yl = reinterpret_cast<const float*>(smem + kSmallWaves * kSmallSelBytes);
       {
         const float4* src = reinterpret_cast<const float4*>(p.ygen + size_t(b) * kBzCols * ys);
-        float4* dst = reinterpret_cast<float4*>(smem + size_t(kSmallWaves) * small_sel_bytes(R));
+        float4* dst = reinterpret_cast<float4*>(smem + kSmallWaves * kSmallSelBytes);
         for (int i = tid; i < kNew * (ys >> 2); i += kSmallThreads) dst[i] = src[i];
       }
       __syncthreads();
-      char* sw = smem + size_t(w) * small_sel_bytes(R);
+      char* sw = smem + size_t(w) * kSmallSelBytes;
       unsigned long long* cand_l = reinterpret_cast<unsigned long long*>(sw);
-      uint32_t* lm = reinterpret_cast<uint32_t*>(sw + size_t(64 * R + 8) * 8);
-      int* scr = reinterpret_cast<int*>(sw + size_t(64 * R + 8) * 8 + 64 * 4);
+      uint32_t* lm = reinterpret_cast<uint32_t*>(sw + kSmallCandBytes);
+      int* scr = reinterpret_cast<int*>(sw + kSmallCandBytes + 64 * 4);
       {
         int32_t* sel = p.bsel + size_t(b) * kBetaSamples * n;
         float* sig = p.bsig + size_t(b) * kBetaSamples;
@@ -142,8 +144,8 @@ __global__ __launch_bounds__(64 * W) void k_bcem_small(Params p0, int persist) {
         };
         const int s_lo = first_sample(tb), lane = tid & 63;
         if (s_lo + w < kBetaSamples) {
-          select_walk<NQ, R, G>(row, [&](int s) { return sel + s * n; }, s_lo + w, kBetaSamples, kSmallWaves, M, n,
-                                cand_l, lm, scr);
+          select_walk<NQ, kSmallSelR, kSmallSelG>(row, [&](int s) { return sel + s * n; }, s_lo + w, kBetaSamples,
+                                                  kSmallWaves, M, n, cand_l, lm, scr);
           for (int s2 = s_lo + w + lane * kSmallWaves; lane < 16 && s2 < kBetaSamples; s2 += 16 * kSmallWaves)
             sig[s2] = row(s2)(M);  // tb >= 1: rows are clipped when written
         }
@@ -158,13 +160,13 @@ __global__ __launch_bounds__(64 * W) void k_bcem_small(Params p0, int persist) {
     // by rows (bdirect_body): a candidate's direct pairs share its M rows
     // several times over, and the pair-list form (direct_pairs_wave) measured
     // no faster here (CARLA n = 10: 24.2 vs 24.3 ms per solve)
-    bkernel_body<kSmallWaves, false, true>(p, tb, cand, 0, 1, int(ker_scratch(M, n, tb, kSmallWaves)), smem, mom_l, feat_l);
+    bkernel_body<false, true>(p, tb, cand, 0, 1, int(ker_scratch(M, n, tb)), smem, mom_l, feat_l);
     __syncthreads();
     if (tb == 5) SMALL_STAMP(p, 3);
     if (tb > 0) {
       const int total = bdirect_total(p, b, 1);  // block-uniform
       if (total > 0) {
-        bdirect_body<NV4, kSmallWaves>(p, tb, 1, 1, cand, 0, total, smem);
+        bdirect_body<1, kSmallWaves>(p, tb, 1, 1, cand, 0, total, smem);  // M <= 256: one float4 per lane
         __syncthreads();
       }
     }
@@ -194,8 +196,8 @@ __global__ __launch_bounds__(64 * W) void k_bcem_small(Params p0, int persist) {
     // generator level 2, a wave per 16-position block
     {
       const int nblk = (M + 1 + 15) / 16;
-      double* xl = reinterpret_cast<double*>(smem) + 32 * GNB * w;
-      for (int blk = w; blk < nblk; blk += kSmallWaves * GNB) bgen_wave<GNB>(p, b, blk, kSmallWaves, xl);
+      double* xl = reinterpret_cast<double*>(smem) + 32 * w;
+      for (int blk = w; blk < nblk; blk += kSmallWaves) bgen_wave(p, b, blk, xl);
     }
     __syncthreads();
     if (tb == 5) SMALL_STAMP(p, 7);
@@ -208,35 +210,25 @@ __global__ __launch_bounds__(64 * W) void k_bcem_small(Params p0, int persist) {
 
 }  // namespace
 
-// waves per workgroup: 16 while every phase fits 128 VGPRs (the QPs of n <=
-// 16, NP <= 16), else 8 (256 VGPRs)
-constexpr int kSmallW512 = 8;  // waves at 256 < M <= 512 (an experiment edits it: 16)
-HDI int small_waves(int M) { return M <= 256 ? 16 : (M <= 512 ? kSmallW512 : 8); }
-
 // M <= 256 (n <= 16): at n = 22 the per-iteration kernels, which spread each
 // phase over the whole chip, measured faster (CARLA n = 22: 63.0 vs 70.9 ms
-// per tick); the M > 256 instantiations stay for MPCMMD_FUSED experiments
+// per tick), and the kernel is built for no larger size
 bool bcem_small_ok(const Params& p) {
-  return p.gen_wave && p.M <= 256 && p.nb <= 512 && small_lds(p.M, p.n, 1, small_waves(p.M)) <= kLdsBudget;
+  return p.gen_wave && p.M <= 256 && p.nb <= 512 && small_lds(p.M, p.n) <= kLdsBudget;
 }
 
 void launch_bcem_small(const Params& p, hipStream_t s) {
-  const int n = p.n, M = p.M, W = small_waves(M);
-  const dim3 grid(p.nb), block(64 * W);
-  const size_t lp = small_persist_off(M, n, 1, W) + small_persist_bytes(M);
+  const int n = p.n, M = p.M;
+  const dim3 grid(p.nb), block(kSmallThreads);
+  const size_t lp = small_persist_off(M, n) + small_persist_bytes(M);
   const int persist = lp <= kLdsBudget;  // the records and features stay in LDS when they fit
-  const size_t lds = persist ? lp : small_lds(M, n, 1, W);
+  const size_t lds = persist ? lp : small_lds(M, n);
   if (M <= 64)
-    hipLaunchKernelGGL((k_bcem_small<1, 1, 32, 8, 1, 1, 16>), grid, block, lds, s, p, persist);
+    hipLaunchKernelGGL((k_bcem_small<1, 8>), grid, block, lds, s, p, persist);
   else if (M <= 128)
-    hipLaunchKernelGGL((k_bcem_small<2, 1, 32, 12, 1, 1, 16>), grid, block, lds, s, p, persist);
-  else if (M <= 256)
-    hipLaunchKernelGGL((k_bcem_small<4, 1, 32, 16, 1, 1, 16>), grid, block, lds, s, p, persist);
-  else if (M <= 512)
-    hipLaunchKernelGGL((k_bcem_small<8, 1, 32, 24, 2, 16 / kSmallW512, kSmallW512>), grid, block, lds, s,
-                       p, persist);
+    hipLaunchKernelGGL((k_bcem_small<2, 12>), grid, block, lds, s, p, persist);
   else
-    hipLaunchKernelGGL((k_bcem_small<12, 1, 32, 24, 3, 2, 8>), grid, block, lds, s, p, persist);
+    hipLaunchKernelGGL((k_bcem_small<4, 16>), grid, block, lds, s, p, persist);
 }
 
 }  // namespace mpcmmd

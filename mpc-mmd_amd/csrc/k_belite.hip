@@ -128,7 +128,7 @@ __global__ __launch_bounds__(64 * kGenWaveWaves) void k_bgen_wave(Params p) {
   const int nblk = (p.M + 1 + 15) / 16;
   const int w = tidx() >> 6, gw = blockIdx.x * kGenWaveWaves + w;
   if (gw >= p.nb * nblk) return;  // whole waves; no workgroup barrier below
-  bgen_wave<1>(p, p.b0 + gw / nblk, gw % nblk, 0, xl[w]);
+  bgen_wave(p, p.b0 + gw / nblk, gw % nblk, xl[w]);
 }
 
 __global__ __launch_bounds__(kThreads) void k_bsigma(Params p, int tb) {

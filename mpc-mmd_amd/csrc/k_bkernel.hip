@@ -14,16 +14,16 @@ template <bool kList>
 __global__ __launch_bounds__(64 * kKerWaves) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_bkernel(Params p, int tb, int split, int scratch) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int cand = blockIdx.x / split, part = blockIdx.x - cand * split;
-  bkernel_body<kKerWaves, kList, false>(p, tb, cand, part, split, scratch, smem);
+  bkernel_body<kList, false>(p, tb, cand, part, split, scratch, smem);
 }
 
-template <int NV4, int NW>
-__global__ __launch_bounds__(64 * NW) void k_bdirect(Params p, int tb, int kparts, int split, int lpt) {
+template <int NV4>
+__global__ __launch_bounds__(64 * kDirWaves) void k_bdirect(Params p, int tb, int kparts, int split, int lpt) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int cand = blockIdx.x / split, part = blockIdx.x - cand * split;
   const int total = bdirect_total(p, p.b0 + cand, kparts);
   if (total == 0) return;  // block-uniform
-  bdirect_body<NV4, NW>(p, tb, split, lpt, cand, part, total, smem);
+  bdirect_body<NV4, kDirWaves>(p, tb, split, lpt, cand, part, total, smem);
 }
 
 // k_bdirect_pairs, workgroup = (candidate, part), kDirWaves waves each
@@ -91,15 +91,8 @@ void launch_bkernel(const Params& p, int tb, hipStream_t s) {
 
 template <int NV4>
 void launch_bdirect_v(const Params& p, int tb, int split, hipStream_t s) {
-  if (p.dir_waves >= 16)
-    hipLaunchKernelGGL((k_bdirect<NV4, 16>), dim3(p.nb * split), dim3(64 * 16), dir_lds(p.M, p.n).total, s, p, tb,
-                       ker_split(p.nb, p.ker_target), split, 1);
-  else if (p.dir_waves >= 8)
-    hipLaunchKernelGGL((k_bdirect<NV4, 8>), dim3(p.nb * split), dim3(64 * 8), dir_lds(p.M, p.n).total, s, p, tb,
-                       ker_split(p.nb, p.ker_target), split, 1);
-  else
-    hipLaunchKernelGGL((k_bdirect<NV4, kDirWaves>), dim3(p.nb * split), dim3(64 * kDirWaves), dir_lds(p.M, p.n).total,
-                       s, p, tb, ker_split(p.nb, p.ker_target), split, 1);
+  hipLaunchKernelGGL((k_bdirect<NV4>), dim3(p.nb * split), dim3(64 * kDirWaves), dir_lds(p.M, p.n).total, s, p, tb,
+                     ker_split(p.nb, p.ker_target), split, 1);
 }
 
 template <int NV4>

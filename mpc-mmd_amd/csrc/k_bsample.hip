@@ -191,41 +191,30 @@ void launch_bsel0(const Params& p, hipStream_t s) {
 // took 1.5 ms off a 49.5 ms solve)
 int sel_waves(int nb, int cap) { return std::max(4, std::min(nb <= 128 ? cap : 16, 16384 / std::max(1, nb))); }
 
-template <int NQ>
-void launch_bselect_q(const Params& p, int tb, hipStream_t s) {
-  const dim3 grid(p.nb, sel_waves(p.nb, p.sel_cap));
-  if (p.n <= 24)
-    hipLaunchKernelGGL((k_bselect<NQ, 1, 32>), grid, dim3(64), 0, s, p, tb);
-  else if (p.n <= 48)
-    hipLaunchKernelGGL((k_bselect<NQ, 2, 64>), grid, dim3(64), 0, s, p, tb);
-  else
-    hipLaunchKernelGGL((k_bselect<NQ, 2, 0>), grid, dim3(64), 0, s, p, tb);
+template <int NQ, int R, int G>
+void launch_bselect_i(const Params& p, int tb, hipStream_t s) {
+  hipLaunchKernelGGL((k_bselect<NQ, R, G>), dim3(p.nb, sel_waves(p.nb, p.sel_cap)), dim3(64), 0, s, p, tb);
 }
 
+// k_bselect<NQ, R, G> by n (betacem_select.hpp): NQ the instantiated keys per
+// lane that cover ceil(n^2 / 64); (R, G) = (1, 32) for n <= 24, (2, 64) for
+// n <= 48, else (2, 0).  The two follow n together, so these 13 instances are
+// all a supported size (n <= 64) reaches.
 void launch_bselect(const Params& p, int tb, hipStream_t s) {
-  const int nq = (p.M + 63) >> 6;
-  switch (nq) {
-#define MPCMMD_SEL_CASE(q) \
-  case q:                  \
-    return launch_bselect_q<q>(p, tb, s);
-    MPCMMD_SEL_CASE(1)
-    MPCMMD_SEL_CASE(2)
-    MPCMMD_SEL_CASE(4)
-    MPCMMD_SEL_CASE(8)
-    MPCMMD_SEL_CASE(16)
-#undef MPCMMD_SEL_CASE
-    default:
-      break;
-  }
-  if (nq <= 4) return launch_bselect_q<4>(p, tb, s);
-  if (nq <= 8) return launch_bselect_q<8>(p, tb, s);
-  if (nq <= 12) return launch_bselect_q<12>(p, tb, s);
-  if (nq <= 16) return launch_bselect_q<16>(p, tb, s);
-  if (nq <= 24) return launch_bselect_q<24>(p, tb, s);
-  if (nq <= 32) return launch_bselect_q<32>(p, tb, s);
-  if (nq <= 40) return launch_bselect_q<40>(p, tb, s);
-  if (nq <= 48) return launch_bselect_q<48>(p, tb, s);
-  return launch_bselect_q<64>(p, tb, s);
+  const int n = p.n;
+  if (n <= 8) return launch_bselect_i<1, 1, 32>(p, tb, s);
+  if (n <= 11) return launch_bselect_i<2, 1, 32>(p, tb, s);
+  if (n <= 16) return launch_bselect_i<4, 1, 32>(p, tb, s);
+  if (n <= 22) return launch_bselect_i<8, 1, 32>(p, tb, s);
+  if (n <= 24) return launch_bselect_i<12, 1, 32>(p, tb, s);
+  if (n <= 27) return launch_bselect_i<12, 2, 64>(p, tb, s);
+  if (n <= 32) return launch_bselect_i<16, 2, 64>(p, tb, s);
+  if (n <= 39) return launch_bselect_i<24, 2, 64>(p, tb, s);
+  if (n <= 45) return launch_bselect_i<32, 2, 64>(p, tb, s);
+  if (n <= 48) return launch_bselect_i<40, 2, 64>(p, tb, s);
+  if (n <= 50) return launch_bselect_i<40, 2, 0>(p, tb, s);
+  if (n <= 55) return launch_bselect_i<48, 2, 0>(p, tb, s);
+  return launch_bselect_i<64, 2, 0>(p, tb, s);
 }
 
 }  // namespace mpcmmd

@@ -51,7 +51,6 @@ struct Params {
   int32_t dir_pairs;       // 1: k_bdirect_pairs (a wave per 8 listed pairs); 0: k_bdirect (rows sorted in LDS)
   int32_t qp_small;        // k_bqp at 64 threads (16 QPs) per workgroup for launches of < 2 workgroups per CU
   int32_t sel_cap;         // k_bselect: at most this many single-wave workgroups per candidate (default 64)
-  int32_t dir_waves;       // waves per k_bdirect workgroup (4, 8 or 16)
   int32_t ker_target;      // k_bkernel parts: enough for this many workgroups per launch (default 128)
   int32_t dir_target;      // k_bdirect parts: enough for this many workgroups per launch (default 2048)
   int32_t mom_rows;        // 1 (default): k_bmoment_rows (16 lanes per distance row, 4 rows per wave); 0: a wave
@@ -264,7 +263,7 @@ void launch_belite(const Params& p, int tb, hipStream_t s);
 void launch_bgen(const Params& p, int tb, hipStream_t s);  // + k_bsigma on the last beta-iteration
 void launch_mmdfinal(const Params& p, int t, hipStream_t s);
 // the 20 beta-iterations of every candidate of [b0, b0 + nb) in one launch, a
-// workgroup per candidate (small batches, n <= 24; bit-identical to the
+// workgroup per candidate (small batches, n <= 16; bit-identical to the
 // per-iteration kernels above)
 bool bcem_small_ok(const Params& p);
 void launch_bcem_small(const Params& p, hipStream_t s);

@@ -696,7 +696,6 @@ int mpcmmd_create_batch(const mpcmmd_config* cfg, int32_t max_configs, mpcmmd_ha
     p.dir_pairs = env_flag("MPCMMD_DIR_PAIRS", true);
     p.qp_small = env_flag("MPCMMD_QP_SMALL", true);
     p.sel_cap = env_clamped("MPCMMD_SEL_CAP", 64, 1, kNoMax);
-    p.dir_waves = env_int("MPCMMD_DIR_WAVES", 4);
     // parts per candidate only below 128 candidates per launch (B = 100: 8 -> 2 parts)
     p.ker_target = env_clamped("MPCMMD_KER_TARGET", 128, 1, kNoMax);
     p.dir_target = env_clamped("MPCMMD_DIR_TARGET", 2048, 1, kNoMax);

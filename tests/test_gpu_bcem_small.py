@@ -78,7 +78,6 @@ def test_direct_pairs_same_bits(native, monkeypatch, case):
     LDS): the same per-lane terms and the same reduction tree for every slot,
     so the direct row sums (brow) and every output carry the same bits."""
     kind, n = case.split("-")[:2]
-    fused = case.endswith("fused")
     n = int(n)
     T = 2
     carla = None
@@ -91,7 +90,7 @@ def test_direct_pairs_same_bits(native, monkeypatch, case):
     runs = []
     for pairs in ("0", "1"):
         monkeypatch.setenv("MPCMMD_DIR_PAIRS", pairs)
-        runs.append(_run(native, monkeypatch, fused, "mmd_opt", n, B, H, O, T, carla=carla, keys=("brow",)))
+        runs.append(_run(native, monkeypatch, False, "mmd_opt", n, B, H, O, T, carla=carla, keys=("brow",)))
     (ref, rr), (got, rg) = runs
     for t in range(T):
         for k in ref[t]:

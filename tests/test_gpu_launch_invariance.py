@@ -37,7 +37,7 @@ F32 = np.float32
 BS, BL = 24, 521   # 521 = 21 * 24 + 17: every small row at many packing positions and group offsets
 
 KNOBS = ("MPCMMD_GROUPS", "MPCMMD_SMALL_GROUPS", "MPCMMD_SEL_CAP", "MPCMMD_KER_TARGET", "MPCMMD_DIR_TARGET",
-         "MPCMMD_DIR_PAIRS", "MPCMMD_DIR_WAVES", "MPCMMD_QP_SMALL", "MPCMMD_GENWAVE", "MPCMMD_FUSED")
+         "MPCMMD_DIR_PAIRS", "MPCMMD_QP_SMALL", "MPCMMD_GENWAVE", "MPCMMD_FUSED")
 
 
 def _same_rows(what, big, small):
@@ -226,21 +226,18 @@ def _same_run(what, got, ref):
         _same(f"{what}: result {k}", np.asarray(rg[k]), np.asarray(v))
 
 
-PAIRS0 = "MPCMMD_DIR_PAIRS=0,MPCMMD_DIR_WAVES="
-
-
 @pytest.mark.parametrize("n,B,knob", [(17, 100, k) for k in (
     "MPCMMD_GROUPS=1", "MPCMMD_GROUPS=3", "MPCMMD_GROUPS=4", "MPCMMD_QP_SMALL=0", "MPCMMD_SEL_CAP=1",
     "MPCMMD_SEL_CAP=16", "MPCMMD_KER_TARGET=1", "MPCMMD_KER_TARGET=100000", "MPCMMD_DIR_TARGET=1",
-    "MPCMMD_DIR_TARGET=100000", PAIRS0 + "4", PAIRS0 + "8", PAIRS0 + "16")] + [(33, 64, k) for k in (
-        "MPCMMD_GROUPS=1", "MPCMMD_GROUPS=4", PAIRS0 + "16")])
+    "MPCMMD_DIR_TARGET=100000", "MPCMMD_DIR_PAIRS=0")] + [(33, 64, k) for k in (
+        "MPCMMD_GROUPS=1", "MPCMMD_GROUPS=4", "MPCMMD_DIR_PAIRS=0")])
 def test_knob_bits(native, monkeypatch, n, B, knob):
     """mmd_opt, static, H = 10, O = 3, two outer iterations; n = 17 at B = 100
-    and n = 33 at B = 64.  Every setting but MPCMMD_DIR_WAVES 8 / 16 selects a
-    launch geometry that a default run reaches at some batch size (candidate
-    groups, k_bqp's workgroup size, k_bselect's waves, the parts of k_bkernel
-    and of the direct sums, the row-sorted k_bdirect at 4 waves); the 8- and
-    16-wave k_bdirect run only under that knob.  Per outer iteration the
+    and n = 33 at B = 64.  Every setting selects a launch geometry that a
+    default run reaches at some batch size (candidate groups, k_bqp's
+    workgroup size, k_bselect's waves, the parts of k_bkernel and of the
+    direct sums, the row-sorted k_bdirect -- MPCMMD_DIR_PAIRS=0 -- at two and
+    at five float4s per lane).  Per outer iteration the
     beta-CEM outputs, the row sums left in brow, the costs and elite sets,
     and the finished result carry the bits of the run with no knob set."""
     ref = _reference(native, monkeypatch, n, B)

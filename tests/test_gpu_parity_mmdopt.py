@@ -103,7 +103,12 @@ def test_mother_features(native, noise):
     (48, 20, 10, 3, "static", [0, 19], (0, 1, 19)), (64, 20, 10, 3, "static", [0, 19], (0, 1, 19)),
     # a large launch at the benchmark's n (nb = 300 > 256: k_bkernel<false>, the row-sorted k_bdirect in 8
     # parts, k_bqp at 128 threads, 16 select waves); candidates off every multiple of 16 / 64
-    (22, 300, 10, 3, "static", [1, 37, 150, 299], (0, 1, 19))])
+    (22, 300, 10, 3, "static", [1, 37, 150, 299], (0, 1, 19)),
+    # the first n of the k_bselect instances (launch_bselect's table) that no case above reaches: 12 keys per
+    # lane with the 32-group window, 32 keys with the 64-lane window, 48 keys with the bisection (last in
+    # the list: the ids of the cases above carry their position)
+    (24, 20, 10, 3, "static", [0, 19], None), (40, 20, 10, 3, "static", [0, 19], (0, 1, 19)),
+    (51, 20, 10, 3, "static", [0, 19], (0, 1, 19))])
 def test_beta_cem_lockstep(native, n, B, H, O, variant, check, qp_iters):
     ora, nat, xo, yo, draws, st, acc, steer = _run_mother(native, n, B, H, O, "gaussian", 2, variant)
     p = ora.prob
