@@ -13,12 +13,13 @@ from parity import DEFAULT_COV, DEFAULT_INIT, DEFAULT_MEAN, make_pair
 pytestmark = pytest.mark.gpu
 
 
-def _run(native, monkeypatch, fused, cost, n, B, H, O, T, xo=None, yo=None, carla=None, keys=()):
+def _run(native, monkeypatch, fused, cost, n, B, H, O, T, xo=None, yo=None, carla=None, keys=(), draws=None):
     monkeypatch.setenv("MPCMMD_FUSED", "1" if fused else "0")
     if carla is None:
         ora, nat, xo_, yo_ = make_pair(native, cost, n=n, O=O, H=H, B=B, T=T)
         xo, yo = (xo_, yo_) if xo is None else (xo, yo)
-        nat.begin(cost, 7, DEFAULT_INIT, DEFAULT_MEAN, DEFAULT_COV, xo, yo, 15.0)
+        # draws: None (the internal streams) or a function of the oracle's problem that returns the Draws
+        nat.begin(cost, 7, DEFAULT_INIT, DEFAULT_MEAN, DEFAULT_COV, xo, yo, 15.0, draws and draws(ora.prob))
     else:
         init, xo, yo, path, variant = carla
         nat = native.Handle(native.make_config(n, O, 0.1, H, "gaussian", 0.0, 0.0, num_batch=B, maxiter_cem=T,
@@ -43,6 +44,36 @@ def test_fused_bits_static(native, monkeypatch, n, B, H, O):
     T = 3
     ref, rr = _run(native, monkeypatch, False, "mmd_opt", n, B, H, O, T)
     got, rg = _run(native, monkeypatch, True, "mmd_opt", n, B, H, O, T)
+    for t in range(T):
+        for k in ref[t]:
+            if k == "tr":
+                assert all(np.array_equal(a, b) for a, b in zip(got[t][k], ref[t][k])), f"iteration {t}: elites"
+            else:
+                assert np.array_equal(got[t][k], ref[t][k], equal_nan=True), f"iteration {t}: {k} differs"
+    for k, v in rr.items():
+        assert np.array_equal(np.asarray(rg[k]), np.asarray(v), equal_nan=True), k
+
+
+@pytest.mark.parametrize("n,layout", [(6, "even_odd"), (10, "even_odd"), (10, "three_quarters"), (16, "even_odd")])
+def test_fused_bits_static_ties(native, monkeypatch, n, layout):
+    """test_fused_bits_static on the two-level beta draws of
+    test_beta_iterations_two_level_ties (tie_patterns.two_level_z0, beta_z[0] =
+    0): every first sample and the 89 samples of beta-iteration 1 carry exact
+    ties, which select_walk inside k_bcem_small must break as k_bselect does
+    (window ties at n = 6 and 10, emit_top's tie branch at n = 10
+    three-quarters and n = 16)."""
+    import oracle
+    import tie_patterns as tp
+    B, H, O, T = 32, 10, 3, 2
+
+    def draws(prob):
+        rng = np.random.default_rng(100 + n)
+        d = oracle.Draws.random(prob, rng, idx_mpc=7, seed=0, with_beta_cem=True)
+        d.beta_z0 = tp.two_level_z0(n * n, rng, layout)
+        d.beta_z[0] = 0.0
+        return d
+    ref, rr = _run(native, monkeypatch, False, "mmd_opt", n, B, H, O, T, draws=draws)
+    got, rg = _run(native, monkeypatch, True, "mmd_opt", n, B, H, O, T, draws=draws)
     for t in range(T):
         for k in ref[t]:
             if k == "tr":
