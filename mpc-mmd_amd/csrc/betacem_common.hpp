@@ -34,9 +34,10 @@
 // Same factor as chol(cov) in exact arithmetic, O(M r^2) instead of O(M^3).
 //
 // This header: what every beta-CEM file shares (the thread index, sizes,
-// small wave / quad helpers, launch sizing, the LDS layouts).  The phase
-// bodies that both the per-iteration kernels and the fused k_bcem_small run
-// are in betacem_{sample,select,kernel,qp,elite}.hpp; the kernels and their
+// launch sizing, the LDS layouts; the wave / quad helpers are lanes.hpp's).
+// The phase bodies that both the per-iteration kernels and the fused
+// k_bcem_small run are in betacem_{sample,select,kernel,qp,elite}.hpp; the
+// kernels and their
 // launchers in k_mother, k_bdist, k_bsample, k_bkernel, k_bqp, k_belite and
 // k_bcem_small.hip.
 #pragma once
@@ -81,60 +82,9 @@ HDI int first_sample(int tb) { return tb > 0 ? kBetaElite : 0; }
 #define kconst __attribute__((address_space(4)))
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-// Intra-wave LDS hand-off: a wave's LDS operations execute in order, so only
-// the compiler must be kept from reordering them (no memory-counter waits).
-DEVI void wave_sync() {
-  __builtin_amdgcn_wave_barrier();
-  __asm__ volatile("" ::: "memory");
-}
-
-// sum over each row of 16 lanes (every lane of the row holds it)
-DEVI double row16_sum(double v) {
-  v += dpp_d<0xB1>(v);
-  v += dpp_d<0x4E>(v);
-  v += dpp_d<0x124>(v);
-  return v + dpp_d<0x128>(v);
-}
-
 // fp64 MFMA (v_mfma_f64_16x16x4_f64; layouts: betacem_sample.hpp)
 typedef double d4 __attribute__((ext_vector_type(4)));
 DEVI d4 mfma64(double a, double b, d4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-
-// value of quad lane l (0..3) in every lane of the quad; l is a constant
-// after unrolling, so the switch folds
-DEVI float quad_bcast(float v, int l) {
-  const int b = __float_as_int(v);
-  switch (l & 3) {
-    case 0: return __int_as_float(dpp_full<0x00>(b));
-    case 1: return __int_as_float(dpp_full<0x55>(b));
-    case 2: return __int_as_float(dpp_full<0xAA>(b));
-    default: return __int_as_float(dpp_full<0xFF>(b));
-  }
-}
-DEVI double quad_bcast(double v, int l) {
-  const long long b = __double_as_longlong(v);
-  int lo = int(b), hi = int(b >> 32);
-  switch (l & 3) {
-    case 0: lo = dpp_full<0x00>(lo), hi = dpp_full<0x00>(hi); break;
-    case 1: lo = dpp_full<0x55>(lo), hi = dpp_full<0x55>(hi); break;
-    case 2: lo = dpp_full<0xAA>(lo), hi = dpp_full<0xAA>(hi); break;
-    default: lo = dpp_full<0xFF>(lo), hi = dpp_full<0xFF>(hi); break;
-  }
-  return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned>(lo));
-}
-// sum over the quad, bit-identical in its 4 lanes
-DEVI float quad_sum(float v) {
-  v = v + __int_as_float(dpp_full<0xB1>(__float_as_int(v)));  // quad_perm(1,0,3,2)
-  return v + __int_as_float(dpp_full<0x4E>(__float_as_int(v)));  // quad_perm(2,3,0,1)
-}
-DEVI double quad_sum(double v) {
-  auto sw = [](double x, auto f) {
-    const long long b = __double_as_longlong(x);
-    return __longlong_as_double((static_cast<long long>(f(int(b >> 32))) << 32) | static_cast<unsigned>(f(int(b))));
-  };
-  v = v + sw(v, [](int x) { return dpp_full<0xB1>(x); });
-  return v + sw(v, [](int x) { return dpp_full<0x4E>(x); });
-}
 
 // launch sizing
 constexpr int kXcds = 8;   // workgroups are dealt round-robin to the 8 XCDs by linear id

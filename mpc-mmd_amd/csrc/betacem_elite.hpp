@@ -363,7 +363,7 @@ DEVI void bsigma_body(const Params& p, int tb, int b, double* red) {
     }
 #pragma unroll
     for (int a = 0; a < 11; ++a) {
-      part[a] = wave_sum(part[a]);
+      part[a] = wave_total(part[a]);
     }
     __syncthreads();
     if ((tid & 63) == 0 && tid < kThreads)

@@ -43,33 +43,6 @@ namespace mpcmmd {
 
 namespace {
 
-DEVI float dpp_f_ror8(float v) { return __int_as_float(dpp_i<0x128>(__float_as_int(v))); }
-
-// v[j] per lane -> lanes 8 j + 4..7 hold the 64-lane sum of v[j] (row_ror:4
-// moves lane i - 4 into lane i, so the 8-lane group's total lands in its upper quad)
-DEVI float transpose_sum8(const float (&v)[8]) {
-  const int lane = tidx() & 63;
-  float a[4], c2[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {  // lanes 0-31: slots 0..3, lanes 32-63: slots 4..7
-    float x = v[i], y = v[4 + i];
-    permlane_swap<32>(x, y);
-    a[i] = x + y;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {  // lane bit 4 picks slot 4 h + 2 b4 + i
-    float x = a[i], y = a[2 + i];
-    permlane_swap<16>(x, y);
-    c2[i] = x + y;
-  }
-  const bool b3 = lane & 8;  // lane bit 3 picks slot 4 h + 2 b4 + b3 = lane >> 3
-  const float y0 = dpp_f_ror8(c2[0]), y1 = dpp_f_ror8(c2[1]);
-  float x = b3 ? c2[1] + y1 : c2[0] + y0;
-  x += __int_as_float(dpp_i<0xB1>(__float_as_int(x)));
-  x += __int_as_float(dpp_i<0x4E>(__float_as_int(x)));
-  return x + __int_as_float(dpp_i<0x124>(__float_as_int(x)));
-}
-
 // 1 / (k + 1) for the Horner steps of the series
 __constant__ double kInvK[kMom] = {1.0,       1.0 / 2,  1.0 / 3,  1.0 / 4,  1.0 / 5,  1.0 / 6,
                                    1.0 / 7,   1.0 / 8,  1.0 / 9,  1.0 / 10, 1.0 / 11, 1.0 / 12};
@@ -361,6 +334,28 @@ DEVI void bkernel_body(const Params& p, int tb, int cand, int part, int split, i
   MPCMMD_STAMPW(p, 4);
 }
 
+// The per-lane part of a direct row sum: the lane's columns x (float4s
+// lane + 64 t of the distance row) as exp2(D * cs), cs = -log2 e / sigma
+// (packed scale, v_exp_f32; pad columns: +inf * cs = -inf -> 0), summed in
+// two packed accumulators (the float4's column pairs) that are added at the
+// end.  k_bdirect (do_row) and k_bdirect_pairs (direct_pairs_wave) both take
+// their terms from here and reduce them by transpose_sum8: the same bits.
+template <int NV4>
+DEVI float pair_terms(const float4 (&x)[NV4], float cs) {
+  const f2 c2 = {cs, cs};
+  f2 a0, a1;
+#pragma unroll
+  for (int t = 0; t < NV4; ++t) {
+    const f2 t0 = f2{x[t].x, x[t].y} * c2, t1 = f2{x[t].z, x[t].w} * c2;
+    const f2 e0 = {__builtin_amdgcn_exp2f(t0.x), __builtin_amdgcn_exp2f(t0.y)};
+    const f2 e1 = {__builtin_amdgcn_exp2f(t1.x), __builtin_amdgcn_exp2f(t1.y)};
+    a0 = t == 0 ? e0 : a0 + e0;
+    a1 = t == 0 ? e1 : a1 + e1;
+  }
+  a0 += a1;
+  return a0.x + a0.y;
+}
+
 // flagged pairs of candidate b (k_bkernel's parts): k_bdirect's work
 DEVI int bdirect_total(const Params& p, int b, int kparts) {
   int total = 0;
@@ -508,23 +503,9 @@ DEVI void bdirect_body(const Params& p, int tb, int split, int lpt, int cand, in
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
           v[jj] = 0.0f;
-          if (j0 + jj < cc) {
-            const float cn = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cl), j0 + jj));
-            const f2 c2 = {cn, cn};
-            f2 a0, a1;
-#pragma unroll
-            for (int t = 0; t < NV4; ++t) {
-              const f2 t0 = f2{x[t].x, x[t].y} * c2, t1 = f2{x[t].z, x[t].w} * c2;
-              const f2 e0 = {__builtin_amdgcn_exp2f(t0.x), __builtin_amdgcn_exp2f(t0.y)};
-              const f2 e1 = {__builtin_amdgcn_exp2f(t1.x), __builtin_amdgcn_exp2f(t1.y)};
-              a0 = t == 0 ? e0 : a0 + e0;
-              a1 = t == 0 ? e1 : a1 + e1;
-            }
-            a0 += a1;
-            v[jj] = a0.x + a0.y;
-          }
+          if (j0 + jj < cc) v[jj] = pair_terms<NV4>(x, readlane(cl, j0 + jj));
         }
-        const float sum = transpose_sum8(v);
+        const float sum = transpose_sum8(v, tidx() & 63);
         // lane group j = lane >> 3 takes pair j0 + j
         const int jg = j0 + (lane >> 3);
         const int pj = __shfl(pl, jg, 64);
@@ -566,10 +547,9 @@ DEVI void bdirect_body(const Params& p, int tb, int split, int lpt, int cand, in
 // -- CARLA, where about half of all pairs are direct at every beta-iteration
 // -- costs more than the sums).  A wave takes PJ listed pairs, issues all
 // their distance-row loads (lane L: float4s L + 64 t of row sel[i]) before the
-// first exponential, forms each pair's per-lane terms exactly as
-// bdirect_body's do_row (packed scale, v_exp_f32, the same pairwise order),
-// and reduces the PJ slots by one transpose_sum8, whose tree is the same for
-// every slot: the bits of bdirect_body.
+// first exponential, forms each pair's per-lane terms by pair_terms, as
+// bdirect_body's do_row does, and reduces the PJ slots by one transpose_sum8,
+// whose tree is the same for every slot: the bits of bdirect_body.
 // Groups g0, g0 + gs, .. of PJ listed pairs of candidate b (cnt pairs) on the
 // calling wave.
 template <int NV4, int PJ>
@@ -603,21 +583,8 @@ DEVI void direct_pairs_wave(const Params& p, int b, int cnt, int g0, int gs) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = 0.0f;
 #pragma unroll
-    for (int j = 0; j < PJ; ++j) {
-      const f2 c2 = {cs[j], cs[j]};
-      f2 a0, a1;
-#pragma unroll
-      for (int t = 0; t < NV4; ++t) {
-        const f2 t0 = f2{x[j][t].x, x[j][t].y} * c2, t1 = f2{x[j][t].z, x[j][t].w} * c2;
-        const f2 e0 = {__builtin_amdgcn_exp2f(t0.x), __builtin_amdgcn_exp2f(t0.y)};
-        const f2 e1 = {__builtin_amdgcn_exp2f(t1.x), __builtin_amdgcn_exp2f(t1.y)};
-        a0 = t == 0 ? e0 : a0 + e0;
-        a1 = t == 0 ? e1 : a1 + e1;
-      }
-      a0 += a1;
-      v[j] = a0.x + a0.y;
-    }
-    const float sum = transpose_sum8(v);  // slot j's total in lanes 8 j + 4..7
+    for (int j = 0; j < PJ; ++j) v[j] = pair_terms<NV4>(x[j], cs[j]);
+    const float sum = transpose_sum8(v, tidx() & 63);  // slot j's total in lanes 8 j + 4..7
     const int j = lane >> 3;
     int pj = pi[0];
 #pragma unroll

@@ -170,22 +170,6 @@ DEVI bool emit_window(const uint32_t* key, uint32_t T, int n, int32_t* out, unsi
   return true;
 }
 
-// wave minimum (VALU: quad / row butterflies, then the row broadcasts into
-// lane 63; rows a broadcast does not write keep the identity)
-template <int CTRL, int ROWS = 0xF>
-DEVI uint32_t dpp_umin_src(uint32_t v) {
-  return uint32_t(__builtin_amdgcn_update_dpp(-1, int(v), CTRL, ROWS, 0xF, false));
-}
-DEVI uint32_t wave_min_u32(uint32_t v) {
-  v = min(v, dpp_umin_src<0xB1>(v));
-  v = min(v, dpp_umin_src<0x4E>(v));
-  v = min(v, dpp_umin_src<0x124>(v));
-  v = min(v, dpp_umin_src<0x128>(v));
-  v = min(v, dpp_umin_src<0x142, 0xA>(v));
-  v = min(v, dpp_umin_src<0x143, 0xC>(v));
-  return uint32_t(__builtin_amdgcn_readlane(int(v), 63));
-}
-
 // A threshold T0 with #{keys >= T0} >= n and few keys above it: the n-th
 // largest of the G group maxima (groups of 64 / G lanes; each of the n groups
 // whose maximum is >= T0 holds a key >= T0).  For the top 22 of 484 keys in
@@ -197,7 +181,7 @@ DEVI uint32_t group_max_threshold(const uint32_t* key, int n, uint32_t* lm) {
   uint32_t m = key[0];
 #pragma unroll
   for (int q = 1; q < NQ; ++q) m = max(m, key[q]);
-  if constexpr (G == 32) m = max(m, uint32_t(__builtin_amdgcn_update_dpp(0, int(m), 0xB1, 0xF, 0xF, false)));
+  if constexpr (G == 32) m = max(m, dpp_old<0xB1>(m, 0u));
   if (lane % (64 / G) == 0) lm[lane / (64 / G)] = m;
   wave_sync();
   int gt = 0;

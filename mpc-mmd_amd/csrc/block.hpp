@@ -7,7 +7,7 @@ namespace mpcmmd {
 
 // sum over the workgroup (blockDim.x multiple of 64); scratch: >= 16 doubles
 DEVI double block_sum(double v, double* scratch) {
-  v = wave_sum(v);
+  v = wave_total(v);
   const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
   __syncthreads();
   if ((threadIdx.x & 63) == 0) scratch[w] = v;
@@ -18,7 +18,7 @@ DEVI double block_sum(double v, double* scratch) {
   return s;
 }
 DEVI int block_sum(int v, int* scratch) {
-  v = wave_sum(v);
+  v = wave_total(v);
   const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
   __syncthreads();
   if ((threadIdx.x & 63) == 0) scratch[w] = v;
@@ -81,8 +81,8 @@ DEVI void bitonic_sort_reg(unsigned long long* k, int N) {
 // block_sum of a double and an int together (one pair of barriers for both;
 // each total in block_sum's order, so the same bits)
 DEVI void block_sum2(double& v, int& c, double* sd, int* si) {
-  v = wave_sum(v);
-  c = wave_sum(c);
+  v = wave_total(v);
+  c = wave_total(c);
   const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
   __syncthreads();
   if ((threadIdx.x & 63) == 0) {
@@ -113,26 +113,18 @@ struct ReduceScratch {
 // largest 64-bit word over each group of 8 lanes (quad butterflies, then
 // row_half_mirror pairs the two quads), in every lane of the group
 DEVI unsigned long long max8_u64(unsigned long long v) {
-  auto step = [](unsigned long long a, auto dpp) {
-    const unsigned long long b = (static_cast<unsigned long long>(unsigned(dpp(int(a >> 32)))) << 32) |
-                                 unsigned(dpp(int(a)));
-    return b > a ? b : a;
-  };
-  v = step(v, [](int x) { return dpp_i<0xB1>(x); });
-  v = step(v, [](int x) { return dpp_i<0x4E>(x); });
-  return step(v, [](int x) { return dpp_i<0x141>(x); });
+  auto mx = [](unsigned long long a, unsigned long long b) { return b > a ? b : a; };
+  v = mx(v, dpp<0xB1>(v));
+  v = mx(v, dpp<0x4E>(v));
+  return mx(v, dpp<0x141>(v));
 }
 
 // smallest 64-bit word over each group of 8 lanes, in every lane of the group
 DEVI unsigned long long min8_u64(unsigned long long v) {
-  auto step = [](unsigned long long a, auto dpp) {
-    const unsigned long long b = (static_cast<unsigned long long>(unsigned(dpp(int(a >> 32)))) << 32) |
-                                 unsigned(dpp(int(a)));
-    return b < a ? b : a;
-  };
-  v = step(v, [](int x) { return dpp_i<0xB1>(x); });
-  v = step(v, [](int x) { return dpp_i<0x4E>(x); });
-  return step(v, [](int x) { return dpp_i<0x141>(x); });
+  auto mn = [](unsigned long long a, unsigned long long b) { return b < a ? b : a; };
+  v = mn(v, dpp<0xB1>(v));
+  v = mn(v, dpp<0x4E>(v));
+  return mn(v, dpp<0x141>(v));
 }
 
 // The K smallest of B <= blockDim.x distinct 64-bit words (one per thread,

@@ -19,12 +19,12 @@ DEVI void cost_norms(const Params& p, float v_des, int lane, const float (&y)[2]
   const int t0 = lane, t1 = lane + 64;
   // neighbours for the diffs
   const float st_d0 = __shfl_down(st[0], 1, kWave);
-  const float st_f1 = readlane_f(st[1], 0);
+  const float st_f1 = readlane(st[1], 0);
   const float st_n1 = __shfl_down(st[1], 1, kWave);
   const float st_n0 = lane < 63 ? st_d0 : st_f1;
   const float sv[2] = {st_n0 - st[0], st_n1 - st[1]};  // valid for t < 99
   const float sv_d0 = __shfl_down(sv[0], 1, kWave);
-  const float sv_f1 = readlane_f(sv[1], 0);
+  const float sv_f1 = readlane(sv[1], 0);
   const float sv_n1 = __shfl_down(sv[1], 1, kWave);
   const float sv_n0 = lane < 63 ? sv_d0 : sv_f1;
   const float sa[2] = {sv_n0 - sv[0], sv_n1 - sv[1]};  // valid for t < 98
@@ -59,9 +59,9 @@ DEVI void cost_norms(const Params& p, float v_des, int lane, const float (&y)[2]
   }
   // the eleven wave totals at once (lanes 4 k .. 4 k + 3 hold total k)
   const double nv[11] = {n_des, n_st, n_sv, n_sa, n_v, n_sp, n_svp, n_ydd, n_xdd, n_des2, n_cen};
-  const double z = wave_totals16_d(nv);
+  const double z = wave_totals16(nv);
 #pragma unroll
-  for (int k = 0; k < 11; ++k) nk[k] = sqrt(readlane_d(z, 4 * k));
+  for (int k = 0; k < 11; ++k) nk[k] = sqrt(readlane(z, 4 * k));
 }
 
 // compute_cost's total of candidate e from its norms (cem_helper.py:254-262)

@@ -43,11 +43,6 @@ DEVI float interp_jnp(float x, const float* xp, const float* fp, int P) {
 constexpr int kFrenetBatch = 8;
 HDI int frenet_quarter(int P) { return (((P + 3) / 4) + kFrenetBatch - 1) / kFrenetBatch * kFrenetBatch; }
 
-DEVI int quad_min_i(int v) {
-  v = min(v, __shfl_xor(v, 1));
-  return min(v, __shfl_xor(v, 2));
-}
-
 DEVI void frenet_point_quad(float x, float y, const float2* pxy, const float* arc, const float* Fxd, const float* Fyd,
                             int P, int Pq, float& s, float& d) {
   constexpr int kNone = 0x7fffffff;

@@ -117,40 +117,6 @@ __global__ __launch_bounds__(kDistThreads) void k_bdist(Params p) {
 // registers, instead of re-reading it in k_bdirect.
 constexpr int kMomRowsPerBlock = 4;
 
-// wave totals of 16 per-lane values: lane l ends with the total of v[l >> 2].
-// Each butterfly step halves the values a lane carries (permlane32 / permlane16
-// swaps, then row_mirror and row_half_mirror DPP with the kept half chosen by
-// the lane bit the pairing flips, then the quad), ~35 VALU for all 16 totals
-// instead of a 7-step reduction per value.
-DEVI float wave_totals16(const float (&v)[16]) {
-  const int lane = tidx() & 63;
-  float w[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {  // lanes < 32 keep values 0..7, lanes >= 32 values 8..15
-    float a = v[i], b = v[i + 8];
-    permlane_swap<32>(a, b);
-    w[i] = a + b;
-  }
-  float x[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {  // odd rows keep the upper four
-    float a = w[i], b = w[i + 4];
-    permlane_swap<16>(a, b);
-    x[i] = a + b;
-  }
-  const bool b3 = lane & 8, b2 = lane & 4;
-  float y[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {  // row_mirror pairs l with l ^ 15 (bit 3 flipped)
-    const float keep = b3 ? x[i + 2] : x[i], send = b3 ? x[i] : x[i + 2];
-    y[i] = keep + __int_as_float(dpp_i<0x140>(__float_as_int(send)));
-  }
-  // row_half_mirror pairs l with l ^ 7 (bit 2 flipped)
-  float z = (b2 ? y[1] : y[0]) + __int_as_float(dpp_i<0x141>(__float_as_int(b2 ? y[0] : y[1])));
-  z += __int_as_float(dpp_i<0xB1>(__float_as_int(z)));
-  return z + __int_as_float(dpp_i<0x4E>(__float_as_int(z)));
-}
-
 // one distance row (global row index gw over the launch's candidates) held in x
 // Its first-iteration pairs: rpair0[q0 .. q1), lane L's record of the first 64
 // (pr) loaded with the row, ahead of it.
@@ -166,6 +132,28 @@ DEVI RowPairs load_row_pairs(const Params& p, int r) {
   rp.q1 = p.rp0[r + 1];
   rp.pr = p.rpair0[max(min(rp.q0 + lane, rp.q1 - 1), 0)];  // a row without pairs reads a valid record, unused
   return rp;
+}
+
+// The per-lane part of a first-iteration direct row sum (bmoment_row and
+// bmoment_row16): the lane's NV float4s of the row as exp2(D * cs), cs =
+// -log2 e / sigma (pad columns: +inf * cs = -inf -> 0), added in sequence to
+// one packed accumulator.  Not betacem_kernel.hpp's pair_terms, which keeps
+// two accumulators and adds them at the end (half the length of the add
+// chain): that is the order of the later iterations' sums (k_bdirect and
+// k_bdirect_pairs, bit-equal to each other), this the order of the first
+// iteration's.  Both stay, since moving either to the other's order changes
+// the bits of its row sums.
+template <int NV>
+DEVI float row_terms(const float4 (&x)[NV], float cs) {
+  const f2 c2 = {cs, cs};
+  f2 acc = {0.0f, 0.0f};
+#pragma unroll
+  for (int t = 0; t < NV; ++t) {
+    const f2 t0 = f2{x[t].x, x[t].y} * c2, t1 = f2{x[t].z, x[t].w} * c2;
+    acc += f2{__builtin_amdgcn_exp2f(t0.x), __builtin_amdgcn_exp2f(t0.y)};
+    acc += f2{__builtin_amdgcn_exp2f(t1.x), __builtin_amdgcn_exp2f(t1.y)};
+  }
+  return acc.x + acc.y;
 }
 
 template <int NV4>
@@ -228,17 +216,9 @@ DEVI void bmoment_row(const Params& p, int gw, const float4 (&x)[NV4], const Row
       const int j = __builtin_ctzll(todo);
       todo &= todo - 1;
       const int i = __builtin_amdgcn_readlane(il, j);
-      const float sg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sl), j));
+      const float sg = readlane(sl, j);
       const float cs = kNegLog2e / sg;
-      const f2 c2 = {cs, cs};
-      f2 acc2 = {0.0f, 0.0f};
-#pragma unroll
-      for (int t = 0; t < NV4; ++t) {  // pad columns: +inf * cs = -inf -> 0
-        const f2 t0 = f2{x[t].x, x[t].y} * c2, t1 = f2{x[t].z, x[t].w} * c2;
-        acc2 += f2{__builtin_amdgcn_exp2f(t0.x), __builtin_amdgcn_exp2f(t0.y)};
-        acc2 += f2{__builtin_amdgcn_exp2f(t1.x), __builtin_amdgcn_exp2f(t1.y)};
-      }
-      const float sum = wave_total(acc2.x + acc2.y);
+      const float sum = wave_total(row_terms<NV4>(x, cs));
       if (lane == 0) rowsum[i] = sum;
     }
   }
@@ -294,44 +274,6 @@ __global__ __launch_bounds__(64 * kMomRowsPerBlock) void k_bmoment(Params p) {
 // two quad pairings: lane l ends with slot l of the record).  Same values as
 // bmoment_row up to the summation order of the moments and direct sums.
 // Columns j = 4 (l + 16 t) + c, l = lane & 15.
-DEVI float row16_max(float v) {
-  v = fmaxf(v, dpp_keep_f<0xB1>(v));
-  v = fmaxf(v, dpp_keep_f<0x4E>(v));
-  v = fmaxf(v, dpp_keep_f<0x124>(v));
-  return fmaxf(v, dpp_keep_f<0x128>(v));
-}
-DEVI float row16_total(float v) {
-  v += __int_as_float(dpp_i<0xB1>(__float_as_int(v)));
-  v += __int_as_float(dpp_i<0x4E>(__float_as_int(v)));
-  v += __int_as_float(dpp_i<0x124>(__float_as_int(v)));
-  return v + __int_as_float(dpp_i<0x128>(__float_as_int(v)));
-}
-// 16 per-lane values -> lane l (of each 16-lane row) holds the row total of v[l & 15]
-DEVI float row16_totals16(const float (&v)[16]) {
-  const int lane = tidx() & 15;
-  const bool b3 = lane & 8, b2 = lane & 4, b1 = lane & 2, b0 = lane & 1;
-  float y[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {  // row_mirror: l <-> 15 - l (bit 3 flipped)
-    const float keep = b3 ? v[i + 8] : v[i], send = b3 ? v[i] : v[i + 8];
-    y[i] = keep + __int_as_float(dpp_i<0x140>(__float_as_int(send)));
-  }
-  float z[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {  // row_half_mirror: l <-> l ^ 7 (bit 2 flipped)
-    const float keep = b2 ? y[i + 4] : y[i], send = b2 ? y[i] : y[i + 4];
-    z[i] = keep + __int_as_float(dpp_i<0x141>(__float_as_int(send)));
-  }
-  float w[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {  // quad_perm(2,3,0,1): l <-> l ^ 2
-    const float keep = b1 ? z[i + 2] : z[i], send = b1 ? z[i] : z[i + 2];
-    w[i] = keep + __int_as_float(dpp_i<0x4E>(__float_as_int(send)));
-  }
-  const float keep = b0 ? w[1] : w[0], send = b0 ? w[0] : w[1];  // quad_perm(1,0,3,2): l <-> l ^ 1
-  return keep + __int_as_float(dpp_i<0xB1>(__float_as_int(send)));
-}
-
 template <int NV>
 DEVI void bmoment_row16(const Params& p, int g, bool live, const float4 (&x)[NV], int q0, int q1) {
   const int l = tidx() & 15, grp = (tidx() & 63) >> 4;
@@ -407,15 +349,7 @@ DEVI void bmoment_row16(const Params& p, int g, bool live, const float4 (&x)[NV]
       const int src = 16 * grp + j;
       const float sg = __int_as_float(__shfl(__float_as_int(sl), src));
       const float cs = kNegLog2e / sg;
-      const f2 c2 = {cs, cs};
-      f2 acc2 = {0.0f, 0.0f};
-#pragma unroll
-      for (int t = 0; t < NV; ++t) {  // pad columns: +inf * cs = -inf -> 0
-        const f2 t0 = f2{x[t].x, x[t].y} * c2, t1 = f2{x[t].z, x[t].w} * c2;
-        acc2 += f2{__builtin_amdgcn_exp2f(t0.x), __builtin_amdgcn_exp2f(t0.y)};
-        acc2 += f2{__builtin_amdgcn_exp2f(t1.x), __builtin_amdgcn_exp2f(t1.y)};
-      }
-      const float sum = row16_total(acc2.x + acc2.y);
+      const float sum = row16_total(row_terms<NV>(x, cs));
       // every pair of the row with this sigma (the first iteration's samples
       // share sigma = 0.01, the clip, about half of them) takes the same sum
       const bool same = todo && __float_as_uint(sl) == __float_as_uint(sg);

@@ -53,19 +53,19 @@ __global__ __launch_bounds__(256) void k_bqp_wave(Params p, int tb) {
   // Cholesky, column j
 #pragma unroll
   for (int j = 0; j < NP; ++j) {
-    const float djj = readlane_f(A[j], j);
+    const float djj = readlane(A[j], j);
     const float y = rsqrt_nr(djj);
     const float lij = A[j] * y;
     A[j] = lane > j ? lij : (lane == j ? djj * y : 0.0f);
     if (lane == j) rdiag = y;
 #pragma unroll
-    for (int k = j + 1; k < NP; ++k) A[k] = fmaf(-A[j], readlane_f(A[j], k), A[k]);
+    for (int k = j + 1; k < NP; ++k) A[k] = fmaf(-A[j], readlane(A[j], k), A[k]);
   }
   // forward: L y = (g, 1)
   float y1 = float(gd), y2 = real ? 1.0f : 0.0f;
 #pragma unroll
   for (int j = 0; j < NP; ++j) {
-    const float t1 = readlane_f(y1 * rdiag, j), t2 = readlane_f(y2 * rdiag, j);
+    const float t1 = readlane(y1 * rdiag, j), t2 = readlane(y2 * rdiag, j);
     y1 = lane == j ? t1 : fmaf(-A[j], t1, y1);
     y2 = lane == j ? t2 : fmaf(-A[j], t2, y2);
   }
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void k_bqp_wave(Params p, int tb) {
   double kb = bd;
 #pragma unroll 8
   for (int k = 0; k < NP; ++k) {
-    const double bk = double(readlane_f(bf, k));
+    const double bk = double(readlane(bf, k));
     if (k != lane && real && k < n) {
       const int e = k < lane ? lane * (lane - 1) / 2 + k : k * (k - 1) / 2 + lane;
       kb = fma(double(kr[e]), bk, kb);

@@ -48,9 +48,9 @@ DEVI float eval_row(const float (&r)[kNv], const double (&c)[kNv]) {
 
 // the 11 wave totals of s (fp64), rounded to fp32, in every lane
 DEVI void totals11(const double (&s)[kNv], float (&out)[kNv]) {
-  const double z = wave_totals16_d(s);
+  const double z = wave_totals16(s);
 #pragma unroll
-  for (int k = 0; k < kNv; ++k) out[k] = float(readlane_d(z, 4 * k));
+  for (int k = 0; k < kNv; ++k) out[k] = float(readlane(z, 4 * k));
 }
 
 // out[k] = fp32( sum_t M[t][k] r[t] ) over the wave's 100 points
@@ -81,7 +81,7 @@ DEVI float unwrap_corr(float dd) {
 // alpha = unwrap(atan2) along the 100 points; lane owns t0 = lane, t1 = lane + 64
 DEVI void unwrap2(float& a0, float& a1, int lane, bool v1) {
   const float prev0 = __shfl_up(a0, 1, kWave);
-  const float last0 = readlane_f(a0, 63);
+  const float last0 = readlane(a0, 63);
   const float up1 = __shfl_up(a1, 1, kWave);  // shuffles outside any divergent branch
   const float prev1 = lane == 0 ? last0 : up1;
   const float ph0 = lane == 0 ? 0.0f : unwrap_corr(a0 - prev0);
@@ -94,14 +94,14 @@ DEVI void unwrap2(float& a0, float& a1, int lane, bool v1) {
   while (m0) {
     const int i = __builtin_ctzll(m0);
     m0 &= m0 - 1;
-    acc = acc + readlane_f(ph0, i);
+    acc = acc + readlane(ph0, i);
     cs0 = lane >= i ? acc : cs0;
   }
   cs1 = acc;
   while (m1) {
     const int i = __builtin_ctzll(m1);
     m1 &= m1 - 1;
-    acc = acc + readlane_f(ph1, i);
+    acc = acc + readlane(ph1, i);
     cs1 = lane >= i ? acc : cs1;
   }
   if (lane > 0) a0 = a0 + cs0;
@@ -139,13 +139,9 @@ DEVI Polar obs_polar(float wc, float ws, const Params& p) {
   return Polar{ca, sa, c2 / c1};
 }
 
-// jnp.maximum(lo, v), NaN propagating
+// jnp.maximum(lo, v) for a lower bound lo that is no NaN: a NaN v propagates
+// (v_max_f32 alone returns the non-NaN operand)
 DEVI float max_nan(float lo, float v) { return v != v ? v : fmaxf(lo, v); }
-
-DEVI unsigned long long readlane_u64(unsigned long long v, int l) {
-  const unsigned lo = __builtin_amdgcn_readlane(int(unsigned(v)), l), hi = __builtin_amdgcn_readlane(int(unsigned(v >> 32)), l);
-  return (unsigned long long)hi << 32 | lo;
-}
 
 DEVI unsigned long long shfl_up_u64(unsigned long long v, int d) {
   const int lo = __shfl_up(int(unsigned(v)), d, kWave), hi = __shfl_up(int(unsigned(v >> 32)), d, kWave);
@@ -469,7 +465,7 @@ __global__ __launch_bounds__(256) void k_front(Params p, int t) {
   float rox[kNv], roy[kNv];
   if (kDet) {
     constexpr unsigned long long kEven = 0x5555555555555555ull;
-    const unsigned long long up = shfl_up_u64(nonfin, 1), m63 = readlane_u64(nonfin, 63);
+    const unsigned long long up = shfl_up_u64(nonfin, 1), m63 = readlane(nonfin, 63);
     const unsigned long long prev0 = lane == 0 ? 0ull : (up & kEven);           // point t0 - 1 (t0 = 0: the 1)
     const unsigned long long prev1 = lane == 0 ? (m63 & kEven) : ((up >> 1) & kEven);  // point t1 - 1
     double sx[kNv], sy[kNv];
@@ -499,11 +495,11 @@ __global__ __launch_bounds__(256) void k_front(Params p, int t) {
   }
   {
     const double nv[4] = {n_acc, n_vel, n_lane, n_obs};
-    const double z = wave_totals16_d(nv);
-    n_acc = readlane_d(z, 0);
-    n_vel = readlane_d(z, 4);
-    n_lane = readlane_d(z, 8);
-    n_obs = readlane_d(z, 12);
+    const double z = wave_totals16(nv);
+    n_acc = readlane(z, 0);
+    n_vel = readlane(z, 4);
+    n_lane = readlane(z, 8);
+    n_obs = readlane(z, 12);
   }
   float rn = (float(sqrt(n_acc)) + float(sqrt(n_vel))) + float(sqrt(n_lane));
   if (kDet) rn = rn + float(sqrt(n_obs));
@@ -541,7 +537,7 @@ __global__ __launch_bounds__(256) void k_front(Params p, int t) {
   for (int q = 0; q < 2; ++q) v[q] = sqrtf(xd[q] * xd[q] + yd[q] * yd[q]);
   {
     const float d0 = __shfl_down(v[0], 1, kWave);
-    const float first1 = readlane_f(v[1], 0);
+    const float first1 = readlane(v[1], 0);
     const float n1 = __shfl_down(v[1], 1, kWave);
     const float nxt0 = lane < 63 ? d0 : first1;
     const float nxt1 = (t1 == kN - 1) ? v[1] : n1;

@@ -20,13 +20,6 @@ namespace mpcmmd {
 
 namespace {
 
-// Intra-wave LDS hand-off: one wave's LDS operations execute in order, so
-// only the compiler must be kept from reordering them.
-DEVI void wave_sync_lds() {
-  __builtin_amdgcn_wave_barrier();
-  __asm__ volatile("" ::: "memory");
-}
-
 constexpr int kMaxSortN = 4096;
 constexpr int kN = 100;
 
@@ -176,7 +169,7 @@ __global__ __launch_bounds__(1024) void k_select(Params p, int t, int ahead_t, i
       for (int q = 0; q < kElite; ++q) s += wgt[q] * double(pe[q][c]);
       mean32[c] = float((1.0 - 0.6) * double(mean0) + 0.6 * s / sw);  // mean0 = cf.mean[c]
     }
-    wave_sync_lds();
+    wave_sync();
     const int a = tid >> 3, c = tid & 7;
     const double ma = double(mean32[a]), mc = double(mean32[c]);
     double s = 0.0;
@@ -185,7 +178,7 @@ __global__ __launch_bounds__(1024) void k_select(Params p, int t, int ahead_t, i
     cvs[a][c] = double(v);
     cf.cov[a * 8 + c] = v;
     if (tid < 8) cf.mean[tid] = mean32[tid];
-    wave_sync_lds();
+    wave_sync();
   }
   if (tid < 64) {
     // Cholesky (lower) of the fp32 covariance, in fp64: lane i < 8 holds row
@@ -204,11 +197,11 @@ __global__ __launch_bounds__(1024) void k_select(Params p, int t, int ahead_t, i
     for (int j = 0; j < 8; ++j) {
       double Ljk[8];
 #pragma unroll
-      for (int k = 0; k < j; ++k) Ljk[k] = readlane_d(Lr[k], j);
+      for (int k = 0; k < j; ++k) Ljk[k] = readlane(Lr[k], j);
       double d = c[j];
 #pragma unroll
       for (int k = 0; k < j; ++k) d -= Lr[k] * Lr[k];
-      const double piv = readlane_d(sqrt(d), j);
+      const double piv = readlane(sqrt(d), j);
       if (i == j) Lr[j] = piv;
       if (i > j) {
         double sm = c[j];

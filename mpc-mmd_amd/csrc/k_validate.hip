@@ -24,7 +24,9 @@ constexpr int kValMaxObs = 32;
 constexpr int kValMaxH = 100;
 
 // uniform-free Beta(a, b) straight from the Philox attempt streams
-// (rng.hpp: gamma_attempt), log-space ratio as beta_draw_tab
+// (rng.hpp: gamma_attempt), log-space ratio as beta_draw_tab.  The values
+// are log of gamma_direct's g (rng.hpp); the loop stays here with a log at
+// each exit, the form k_validate's instruction stream was measured in
 DEVI void log_gamma_direct(double alpha, uint32_t k0, uint32_t k1, uint32_t stream, uint32_t elem, double& lg,
                            double& lub) {
   const MtConst mc = mt_const(alpha);
@@ -54,13 +56,6 @@ DEVI double beta_direct(double a, double b, uint32_t k0, uint32_t k1, uint32_t s
   if (la > lb) return 1.0 / (1.0 + exp(lb - la));
   const double ea = exp(la - lb);
   return ea / (ea + 1.0);
-}
-
-// standard normal e of stream (k0, k1, stream): block e/4 of philox_normals4
-DEVI double philox_normal(uint32_t k0, uint32_t k1, uint32_t stream, uint32_t e) {
-  double z[4];
-  philox_normals4(k0, k1, stream, 0u, e >> 2, z);
-  return z[e & 3];
 }
 
 __global__ __launch_bounds__(kValThreads) void k_validate(ValidateParams v) {

@@ -50,29 +50,7 @@ HDI size_t vc_lds_words(int O, int H, int P) {
 
 // standard normal e of stream (k0, k1, stream), rounded as oracle/rng.py philox_normals
 DEVI float vc_normal(uint32_t k0, uint32_t k1, uint32_t stream, uint32_t e) {
-  double z[4];
-  philox_normals4(k0, k1, stream, 0u, e >> 2, z);
-  return float(z[e & 3]);
-}
-
-// G' and the boost log-uniform of Gamma(alpha) straight from the Philox
-// attempt stream (rng.hpp: gamma_attempt; gamma_parts_tab without the table)
-DEVI void vc_gamma(double alpha, uint32_t k0, uint32_t k1, uint32_t stream, uint32_t elem, double& g, double& lub) {
-  const MtConst mc = mt_const(alpha);
-  g = mc.d;
-  lub = 0.0;
-  for (int k = 0; k < kGammaMaxAttempts; ++k) {
-    const GammaAttempt ga = gamma_attempt(k0, k1, stream, elem, k);
-    const double v = 1.0 + mc.c * ga.x;
-    if (v > 0.0) {
-      const double v3 = v * v * v;
-      if (mt_accept(ga.x, ga.u, ga.lu, mc.d, v3)) {
-        g = mc.d * v3;
-        lub = ga.lw;
-        return;
-      }
-    }
-  }
+  return float(philox_normal(k0, k1, stream, e));
 }
 
 // Beta(2|u|, 5|u|) of control u with the CARLA combine (beta_combine_cr), as
@@ -81,8 +59,8 @@ DEVI float vc_beta(float u, uint32_t k0, uint32_t k1, uint32_t sa, uint32_t sb, 
   const float fu = fabsf(u);
   const double a = double(2.0f * fu), b = double(5.0f * fu);
   double ga, ua, gb, ub;
-  vc_gamma(a, k0, k1, sa, elem, ga, ua);
-  vc_gamma(b, k0, k1, sb, elem, gb, ub);
+  gamma_direct(a, k0, k1, sa, elem, ga, ua);
+  gamma_direct(b, k0, k1, sb, elem, gb, ub);
   return beta_combine_cr(a, b, 2.0, 5.0, ga, ua, gb, ub);
 }
 
@@ -158,16 +136,8 @@ __global__ __launch_bounds__(kVcThreads) void k_validate_carla(ValidateCarlaPara
         n1 = vc_beta(s, k0, k1, kStreamVcGammaSteerA, kStreamVcGammaSteerB, el);
       }
     }
-    float ap, sp;
-    if (v.noise == 0) {
-      ap = (v.sigma_acc * fabsf(a)) * n0;
-      sp = (v.sigma_steer * fabsf(s)) * n1;
-    } else {
-      ap = v.sigma_acc * (2.0f * n0 - 1.0f);
-      sp = v.K_steer * (2.0f * n1 - 1.0f);
-    }
-    const float an = (a + ap) + v.acc_const * n2;
-    const float sn = (s + sp) + v.steer_const * n2;
+    float an, sn;
+    noisy_from(v, a, s, n0, n1, n2, an, sn);
     ta[h * kVcStride + rr] = an;
     tt[h * kVcStride + rr] = float(tan(double(sn)));
   }

@@ -84,6 +84,13 @@ HDI void philox_normals4(uint32_t k0, uint32_t k1, uint32_t stream, uint32_t wor
   out[3] = r1 * sin(t1);
 }
 
+// standard normal e of stream (k0, k1, stream): element e & 3 of block e / 4
+HDI double philox_normal(uint32_t k0, uint32_t k1, uint32_t stream, uint32_t e) {
+  double z[4];
+  philox_normals4(k0, k1, stream, 0u, e >> 2, z);
+  return z[e & 3];
+}
+
 // Marsaglia-Tsang acceptance of attempt (x, u, log u) for d, v3 = (1 + c x)^3:
 // the squeeze u < 1 - 0.0331 x^4 first, the exact log test only when it
 // fails (Marsaglia & Tsang 2000; oracle/rng.py:_log_gamma_parts applies the
@@ -126,6 +133,38 @@ HDI GammaAttempt gamma_attempt(uint32_t k0, uint32_t k1, uint32_t stream, uint32
   return a;
 }
 
+// The Marsaglia-Tsang constants of alpha' = alpha (+1 when alpha < 1)
+struct MtConst {
+  double d, c;
+};
+HDI MtConst mt_const(double alpha) {
+  const double a1 = alpha < 1.0 ? alpha + 1.0 : alpha;
+  const double d = a1 - 1.0 / 3.0;
+  return MtConst{d, 1.0 / sqrt(9.0 * d)};
+}
+
+// G' of Gamma(alpha') and the boost log-uniform (G = G' U^(1/alpha) for alpha
+// < 1) straight from the Philox attempt stream: the first accepted attempt
+// (d and 0 if none of kGammaMaxAttempts is)
+DEVI void gamma_direct(double alpha, uint32_t k0, uint32_t k1, uint32_t stream, uint32_t elem, double& g,
+                       double& lub) {
+  const MtConst mc = mt_const(alpha);
+  g = mc.d;
+  lub = 0.0;
+  for (int k = 0; k < kGammaMaxAttempts; ++k) {
+    const GammaAttempt ga = gamma_attempt(k0, k1, stream, elem, k);
+    const double v = 1.0 + mc.c * ga.x;
+    if (v > 0.0) {
+      const double v3 = v * v * v;
+      if (mt_accept(ga.x, ga.u, ga.lu, mc.d, v3)) {
+        g = mc.d * v3;
+        lub = ga.lw;
+        return;
+      }
+    }
+  }
+}
+
 // Attempt table of one outer iteration: the Philox-derived (x, u, log u,
 // +-log w) of attempts 0..kGammaTabAttempts-1 for every (stream, row r, step h).
 // The squeeze test u < 1 - 0.0331 x^4 does not depend on alpha, so it is
@@ -140,16 +179,8 @@ constexpr int kGammaTabAttempts = 4;
 constexpr int kGammaTabStreams = 4;  // acc A, acc B, steer A, steer B
 HDI size_t gamma_tab_size(int S, int H) { return size_t(kGammaTabStreams) * kGammaTabAttempts * 4 * S * H; }
 
-// G' for alpha' = alpha (+1 when alpha < 1) and the boost log-uniform,
-// from the table (attempts < kGammaTabAttempts) then Philox directly.
-struct MtConst {
-  double d, c;
-};
-HDI MtConst mt_const(double alpha) {
-  const double a1 = alpha < 1.0 ? alpha + 1.0 : alpha;
-  const double d = a1 - 1.0 / 3.0;
-  return MtConst{d, 1.0 / sqrt(9.0 * d)};
-}
+// gamma_direct's G' and boost log-uniform from the table (attempts <
+// kGammaTabAttempts), then Philox directly.
 // One tabulated attempt (fields x, log u, +-log w; the uniform u itself is
 // only needed by the squeeze, whose decision the sign of log w holds):
 // Marsaglia-Tsang acceptance with the stored squeeze decision

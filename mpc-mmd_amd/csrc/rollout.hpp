@@ -66,8 +66,10 @@ DEVI void noisy_control(const Params& p, const Cfg& cf, int t, int r, int h, flo
 
 // The same perturbation from the step's noise values already in registers:
 // gaussian n0, n1 = the acc / steer normals, beta n0, n1 = the two Beta
-// draws; n2 = the const-noise normal (identical arithmetic to noisy_control)
-DEVI void noisy_from(const Params& p, float a, float s, float n0, float n1, float n2, float& an, float& sn) {
+// draws; n2 = the const-noise normal (identical arithmetic to noisy_control).
+// Prm: Params or ValidateCarlaParams (the same noise fields)
+template <class Prm>
+DEVI void noisy_from(const Prm& p, float a, float s, float n0, float n1, float n2, float& an, float& sn) {
   float ap, sp;
   if (p.noise == 0) {
     ap = (p.sigma_acc * fabsf(a)) * n0;

@@ -10,34 +10,28 @@ namespace mpcmmd {
 // for 8, the permlane swaps for 16 and 32.
 template <int S>
 DEVI unsigned long long xor_partner(unsigned long long a) {
-  int lo = int(a), hi = int(a >> 32);
   const int lane = threadIdx.x & 63;
   if constexpr (S == 1) {
-    lo = dpp_i<0xB1>(lo);
-    hi = dpp_i<0xB1>(hi);
+    return dpp<0xB1>(a);
   } else if constexpr (S == 2) {
-    lo = dpp_i<0x4E>(lo);
-    hi = dpp_i<0x4E>(hi);
+    return dpp<0x4E>(a);
   } else if constexpr (S == 4) {  // row_shl:4 (lane + 4) or row_shr:4 (lane - 4)
-    const int l1 = dpp_i<0x104>(lo), h1 = dpp_i<0x104>(hi);
-    const int l2 = dpp_i<0x114>(lo), h2 = dpp_i<0x114>(hi);
+    const int lo = lo_word(a), hi = hi_word(a);
+    const int l1 = dpp<0x104>(lo), h1 = dpp<0x104>(hi);
+    const int l2 = dpp<0x114>(lo), h2 = dpp<0x114>(hi);
     const bool up = (lane & 4) != 0;
-    lo = up ? l2 : l1;
-    hi = up ? h2 : h1;
+    return from_words<unsigned long long>(up ? l2 : l1, up ? h2 : h1);
   } else if constexpr (S == 8) {  // row_ror:8
-    lo = dpp_i<0x128>(lo);
-    hi = dpp_i<0x128>(hi);
+    return dpp<0x128>(a);
   } else {
     static_assert(S == 16 || S == 32, "xor stride");
-    float xl = __int_as_float(lo), yl = xl, xh = __int_as_float(hi), yh = xh;
+    int xl = lo_word(a), yl = xl, xh = hi_word(a), yh = xh;
     permlane_swap<S>(xl, yl);
     permlane_swap<S>(xh, yh);
     // after the swap y holds the partner where the lane's S-bit is 0, x where it is 1
     const bool first = (lane & S) == 0;
-    lo = __float_as_int(first ? yl : xl);
-    hi = __float_as_int(first ? yh : xh);
+    return from_words<unsigned long long>(first ? yl : xl, first ? yh : xh);
   }
-  return (static_cast<unsigned long long>(static_cast<unsigned>(hi)) << 32) | static_cast<unsigned>(lo);
 }
 
 // one compare-exchange stage of the bitonic network at stride S (in-wave)
