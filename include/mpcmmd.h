@@ -426,6 +426,88 @@ typedef struct mpcmmd_validate_carla_args {
 } mpcmmd_validate_carla_args;
 int mpcmmd_validate_carla(const mpcmmd_validate_carla_args* args);
 
+/* Monte-Carlo risk statistics of saved optima on the GPU: the optimizer's own
+ * cost terms (costs.py:121-234, kernel_computation.py:67-87) evaluated on the
+ * num_rollouts noisy rollouts of mpcmmd_validate instead of the solve's n
+ * samples.  The plan inputs, the draws layout and -- with draws == NULL -- the
+ * Philox streams and element indices are mpcmmd_validate's: the same (keys,
+ * seed) rolls the same points in both calls.  ABI version unchanged; detect
+ * the entry point by its symbol.
+ *
+ * Per configuration k (R = num_rollouts, H = num_prime, O = num_obs, S =
+ * num_sigma) three channels c of per-rollout costs, from the fp64 rollout
+ * whose point at step h is the state before step h (h < H):
+ *   obs[r]     = max over (o, h) of max(0, f_bar), f_bar = -(x - x_obs)^2 / 4.25^2
+ *                - (y - y_obs)^2 / 2.75^2 + 1 in fp64
+ *   lane_lb[r] = max over h of max(0, -y + y_lb)
+ *   lane_ub[r] = max over h of max(0,  y - y_ub)
+ * each rounded once to fp32, the optimizer's dtype.  With costs_in
+ * [num_cfg][3][R] the rollouts are skipped (the plan pointers may be NULL) and
+ * the statistics are taken of the given samples.
+ *
+ * Outputs per (k, c), all fp32 unless noted:
+ *   count_pos  int32 #{r : !(c[r] <= 0)} (a NaN counts)
+ *   var        the linear quantile at alpha with fp32 weights (jnp.quantile):
+ *              pos = fp32(alpha) fp32(R - 1), lo = floor, hi = ceil, hw = pos -
+ *              lo, lw = 1 - hw, var = v[lo] lw + v[hi] hw in fp32 without
+ *              contraction on the ascending order with -0 == +0 and NaN last
+ *              (mpcmmd_quantile_position gives lo, hi, lw, hw).  At R = n this
+ *              is bit for bit the cvar reducer's VaR.
+ *   cvar       mean of the samples >= var that are not NaN (fp64 sum / their
+ *              count), 0 if there are none.  When fewer than (1 - alpha) R
+ *              samples are positive, var = 0 and this is the mean of all
+ *              samples, as in the reference.
+ *   mean, max  fp64 sum / R; the largest value in the total order (NaN if any)
+ *   mmd [S]    1000 ((1/R^2) sum_ij e(|c_i - c_j| / sigma) - (2/R) sum_i
+ *              e(|c_i| / sigma)), e(x) = exp(-x) evaluated as exp2(d (-log2 e /
+ *              sigma)) in fp32 and summed in fp64: compute_mmd with beta = 1/R
+ *              against the Dirac at 0, at each bandwidth sigma[k][s]
+ *   costs      [num_cfg][3][R] the per-rollout costs, or NULL (not copied)
+ *   elapsed_ms [3] HIP-event times of the rollout, statistics and MMD stages,
+ *              or NULL
+ * Nothing accumulates through floating-point atomics: a call repeated returns
+ * the same bits, and a configuration's results do not depend on the batch.
+ *
+ * Limits: 1 <= num_obs <= 32, 2 <= num_prime <= 100, 1 <= num_rollouts <= 2^20,
+ * num_cfg <= 65535, 0 <= alpha <= 1, 0 <= num_sigma <= 8, every sigma finite
+ * and > 0: anything else is MPCMMD_E_INVALID before any HIP call.  A CARLA
+ * variant is MPCMMD_E_UNSUPPORTED; num_cfg == 0 returns MPCMMD_OK without
+ * touching a device.  Synchronous, needs no handle, allocates its own device
+ * buffers. */
+typedef struct mpcmmd_validate_risk_args {
+  int32_t num_cfg, num_obs, num_prime, num_rollouts;
+  int32_t noise;            /* MPCMMD_NOISE_* */
+  int32_t variant;          /* MPCMMD_VARIANT_STATIC / _DYNAMIC */
+  double noise_level, acc_const_noise, steer_const_noise;
+  uint32_t seed;
+  int32_t device;
+  const double* cx;         /* [num_cfg][11] */
+  const double* cy;
+  const double* init_state; /* [num_cfg][6] */
+  const float* x_obs;       /* [num_cfg][num_obs][100] */
+  const float* y_obs;
+  const double* draws;      /* [num_cfg][3][R][H] or NULL */
+  const uint32_t* keys;     /* [num_cfg] */
+  float alpha;              /* quantile level (the optimizer's alpha_quant = 0.98) */
+  int32_t num_sigma;
+  const float* sigma;       /* [num_cfg][num_sigma] */
+  const float* costs_in;    /* [num_cfg][3][R] or NULL */
+  int32_t* count_pos;       /* [num_cfg][3] out */
+  float* var;               /* [num_cfg][3] out */
+  float* cvar;              /* [num_cfg][3] out */
+  float* mean;              /* [num_cfg][3] out */
+  float* max;               /* [num_cfg][3] out */
+  float* mmd;               /* [num_cfg][3][num_sigma] out */
+  float* costs;             /* [num_cfg][3][R] out, or NULL */
+  float* elapsed_ms;        /* [3] out, or NULL */
+} mpcmmd_validate_risk_args;
+int mpcmmd_validate_risk(const mpcmmd_validate_risk_args* args);
+
+/* The linear quantile's position among n >= 1 ascending samples, 0 <= alpha <=
+ * 1 (else MPCMMD_E_INVALID): indices lo, hi and fp32 weights w_lo, w_hi of
+ * quantile = v[lo] w_lo + v[hi] w_hi.  Host only, no GPU needed. */
+int mpcmmd_quantile_position(int32_t n, float alpha, int32_t* lo, int32_t* hi, float* w_lo, float* w_hi);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,54 +9,17 @@
 // (obstacle, step) and per step the rollouts inside an obstacle ellipse
 // (compute_f_bar_temp :103-110, count_nonzero) or across a lane bound
 // (compute_lane_bar :112-120).  The counts are integer LDS atomics, so the
-// result does not depend on the thread order.
+// result does not depend on the thread order.  The controls, the noise draw
+// and the bicycle step are validate_step.hpp's, shared with k_validate_risk.hip.
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
 #include "kernels.hpp"
 #include "rng.hpp"
+#include "validate_step.hpp"
 
 namespace mpcmmd {
 namespace {
-
-constexpr int kValThreads = 1024;
-constexpr int kValMaxObs = 32;
-constexpr int kValMaxH = 100;
-
-// uniform-free Beta(a, b) straight from the Philox attempt streams
-// (rng.hpp: gamma_attempt), log-space ratio as beta_draw_tab.  The values
-// are log of gamma_direct's g (rng.hpp); the loop stays here with a log at
-// each exit, the form k_validate's instruction stream was measured in
-DEVI void log_gamma_direct(double alpha, uint32_t k0, uint32_t k1, uint32_t stream, uint32_t elem, double& lg,
-                           double& lub) {
-  const MtConst mc = mt_const(alpha);
-  lg = log(mc.d);
-  lub = 0.0;
-  for (int k = 0; k < kGammaMaxAttempts; ++k) {
-    const GammaAttempt g = gamma_attempt(k0, k1, stream, elem, k);
-    const double v = 1.0 + mc.c * g.x;
-    if (v > 0.0) {
-      const double v3 = v * v * v;
-      if (mt_accept(g.x, g.u, g.lu, mc.d, v3)) {
-        lg = log(mc.d * v3);
-        lub = g.lw;
-        return;
-      }
-    }
-  }
-}
-
-DEVI double beta_direct(double a, double b, uint32_t k0, uint32_t k1, uint32_t sa, uint32_t sb, uint32_t elem) {
-  double ga, ua, gb, ub;
-  log_gamma_direct(a, k0, k1, sa, elem, ga, ua);
-  log_gamma_direct(b, k0, k1, sb, elem, gb, ub);
-  if (a == 0.0 && b == 0.0) return (ua * 5.0 > ub * 2.0) ? 1.0 : 0.0;
-  const double la = a < 1.0 ? ga + ua / a : ga;
-  const double lb = b < 1.0 ? gb + ub / b : gb;
-  if (la > lb) return 1.0 / (1.0 + exp(lb - la));
-  const double ea = exp(la - lb);
-  return ea / (ea + 1.0);
-}
 
 __global__ __launch_bounds__(kValThreads) void k_validate(ValidateParams v) {
   __shared__ double sacc[kValMaxH], ssteer[kValMaxH], sv[kValMaxH];
@@ -64,7 +27,7 @@ __global__ __launch_bounds__(kValThreads) void k_validate(ValidateParams v) {
   __shared__ int cnt[kValMaxObs * kValMaxH], clb[kValMaxH], cub[kValMaxH];
   const int k = blockIdx.x, tid = threadIdx.x;
   const int H = v.H, O = v.O, R = v.R;
-  const double dt = 0.15, wb = 2.5;  // prob.t, prob.wheel_base (cem.py:26,40)
+  const ValNoise vn{v.noise, v.noise_level, v.acc_const, v.steer_const, v.K_steer};
   const double* cx = v.cx + size_t(k) * 11;
   const double* cy = v.cy + size_t(k) * 11;
   for (int i = tid; i < O * H; i += kValThreads) {
@@ -73,25 +36,8 @@ __global__ __launch_bounds__(kValThreads) void k_validate(ValidateParams v) {
     syo[i] = v.y_obs[(size_t(k) * O + o) * 100 + h];
     cnt[i] = 0;
   }
-  double xd = 0.0, yd = 0.0, xdd = 0.0, ydd = 0.0;
-  if (tid < 100) {  // np.dot(prob.Pdot_jax, cx) etc. (validation.py:140-141)
-    for (int j = 0; j < 11; ++j) {
-      xd += double(v.Pdot[tid * 11 + j]) * cx[j];
-      yd += double(v.Pdot[tid * 11 + j]) * cy[j];
-      xdd += double(v.Pddot[tid * 11 + j]) * cx[j];
-      ydd += double(v.Pddot[tid * 11 + j]) * cy[j];
-    }
-    sv[tid] = sqrt(xd * xd + yd * yd);
-  }
   if (tid < H) clb[tid] = cub[tid] = 0;
-  __syncthreads();
-  if (tid < H) {  // compute_controls (:122-132): acc = diff([v, v_end]) / t, steer = atan(2.5 kappa)
-    const double vn = tid < 99 ? sv[tid + 1] : sv[99];
-    sacc[tid] = (vn - sv[tid]) / dt;
-    const double curv = (ydd * xd - yd * xdd) / pow(xd * xd + yd * yd, 1.5);
-    ssteer[tid] = atan(curv * wb);
-  }
-  __syncthreads();
+  val_controls(v.Pdot, v.Pddot, cx, cy, H, tid, sv, sacc, ssteer);
   const double* st = v.init_state + size_t(k) * 6;
   const uint32_t k0 = v.keys[k], k1 = v.seed;
   const double* dr = v.draws ? v.draws + size_t(k) * 3 * R * H : nullptr;
@@ -107,42 +53,9 @@ __global__ __launch_bounds__(kValThreads) void k_validate(ValidateParams v) {
       if (!(-y + v.y_lb <= 0.0)) atomicAdd(&clb[h], 1);  // :116-119
       if (!(y - v.y_ub <= 0.0)) atomicAdd(&cub[h], 1);
       if (h == H - 1) break;
-      // noisy controls (:73-92)
-      const uint32_t e = uint32_t(r) * uint32_t(H) + uint32_t(h);
-      double na, ns, nc;
-      if (dr) {
-        na = dr[(0 * size_t(R) + r) * H + h];
-        ns = dr[(1 * size_t(R) + r) * H + h];
-        nc = dr[(2 * size_t(R) + r) * H + h];
-      } else if (v.noise == 0) {
-        na = philox_normal(k0, k1, kStreamValAcc, e);
-        ns = philox_normal(k0, k1, kStreamValSteer, e);
-        nc = philox_normal(k0, k1, kStreamValConst, e);
-      } else {
-        const double fa = fabs(sacc[h]), fs = fabs(ssteer[h]);
-        na = beta_direct(2.0 * fa, 5.0 * fa, k0, k1, kStreamValGammaAccA, kStreamValGammaAccB, e);
-        ns = beta_direct(2.0 * fs + 1e-5, 5.0 * fs + 1e-5, k0, k1, kStreamValGammaSteerA, kStreamValGammaSteerB, e);
-        nc = philox_normal(k0, k1, kStreamValConst, e);
-      }
-      double ap, sp;
-      if (v.noise == 0) {
-        ap = v.noise_level * fabs(sacc[h]) * na;
-        sp = v.noise_level * fabs(ssteer[h]) * ns;
-      } else {  // na, ns are the Beta draws
-        ap = v.noise_level * (2.0 * na - 1.0);
-        sp = v.K_steer * v.noise_level * (2.0 * ns - 1.0);
-      }
-      const double an = sacc[h] + ap + v.acc_const * nc;
-      const double sn = ssteer[h] + sp + v.steer_const * nc;
-      // compute_rollout_one_step (:21-40)
-      double sp_ = sqrt(vx * vx + vy * vy);
-      sp_ = sp_ + an * dt;
-      const double psidot = sp_ * tan(sn) / wb;
-      psi = psi + psidot * dt;
-      vx = sp_ * cos(psi);
-      vy = sp_ * sin(psi);
-      x = x + vx * dt;
-      y = y + vy * dt;
+      double an, sn;
+      val_noisy_controls(vn, dr, R, H, r, h, k0, k1, sacc[h], ssteer[h], an, sn);
+      val_bicycle_step(an, sn, x, y, vx, vy, psi);
     }
   }
   __syncthreads();

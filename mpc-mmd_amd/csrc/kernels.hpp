@@ -218,6 +218,33 @@ struct ValidateParams {
 bool validate_shape_ok(int O, int H);
 void launch_validate(const ValidateParams& v, hipStream_t s);
 
+// Monte-Carlo risk statistics of saved optima (k_validate_risk.hip): the
+// rollouts of k_validate reduced to three per-rollout costs (obs, lane_lb,
+// lane_ub), then their count / VaR / CVaR / mean / max and the uniform-weight
+// MMD against the Dirac at 0
+constexpr int kRiskTile = 1024;    // values per pair tile (and rollouts per k_vrisk_roll workgroup)
+constexpr int kRiskMaxSigma = 8;
+struct ValidateRiskParams {
+  ValidateParams roll;   // the plan inputs (count, count_lane unused)
+  int32_t K, R, S;       // configurations, samples per channel, bandwidths
+  int32_t lo, hi;        // the quantile's order statistics and fp32 weights (mpcmmd_quantile_position)
+  float w_lo, w_hi;
+  float* costs;          // [K][3][R] per-rollout costs (k_vrisk_roll's output, or the caller's samples)
+  const float* sigma;    // [K][S]
+  int32_t* count_pos;    // [3K]
+  float* var;            // [3K]
+  float* cvar;           // [3K]
+  float* mean;           // [3K]
+  float* vmax;           // [3K]
+  float* u;              // [3K][R] the non-zero values of a channel, in index order
+  int32_t* np;           // [3K] their count P (Z = R - P zeros)
+  double* part;          // [3K][tiles][S] pair sums of i-tile t against the j-tiles >= t (off-diagonal doubled)
+  float* mmd;            // [3K][S]
+};
+void launch_vrisk_roll(const ValidateRiskParams& v, hipStream_t s);
+void launch_vrisk_stats(const ValidateRiskParams& v, hipStream_t s);
+void launch_vrisk_mmd(const ValidateRiskParams& v, hipStream_t s);
+
 // Monte-Carlo validation of CARLA plans (k_validate_carla.hip): the cvar risk
 // stage's rollouts / Frenet transform / bars with R fresh noise rows per tick,
 // reduced to collision counts instead of CVaR

@@ -1,6 +1,8 @@
-// libmpcmmd: the two stand-alone Monte-Carlo validation entry points
-// (mpcmmd_validate, mpcmmd_validate_carla).  They use no handle: every call
-// allocates, uploads, launches one kernel and reads the counts back.
+// libmpcmmd: the stand-alone Monte-Carlo validation entry points
+// (mpcmmd_validate, mpcmmd_validate_carla, mpcmmd_validate_risk).  They use no
+// handle: every call allocates, uploads, launches its kernels and reads the
+// results back.
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -142,6 +144,97 @@ int mpcmmd_validate_carla(const mpcmmd_validate_carla_args* a) {
     HIPC(hipMemcpy(a->count_lane, v.count_lane, size_t(K) * 4, hipMemcpyDeviceToHost));
     HIPC(hipMemcpy(a->count_rows, v.count_rows, size_t(K) * 4, hipMemcpyDeviceToHost));
     if (a->count_oh) HIPC(hipMemcpy(a->count_oh, v.cnt_oh, n_oh * 4, hipMemcpyDeviceToHost));
+    return MPCMMD_OK;
+  });
+}
+
+int mpcmmd_validate_risk(const mpcmmd_validate_risk_args* a) {
+  if (!a) return fail(MPCMMD_E_INVALID, "null argument");
+  const int K = a->num_cfg, O = a->num_obs, H = a->num_prime, R = a->num_rollouts, S = a->num_sigma;
+  if (K < 0 || K > 65535 || R < 1 || R > (1 << 20) || !validate_shape_ok(O, H))
+    return fail(MPCMMD_E_INVALID, "validate_risk: shape out of range");
+  if (S < 0 || S > kRiskMaxSigma) return fail(MPCMMD_E_INVALID, "validate_risk: num_sigma out of [0, 8]");
+  if (!(a->alpha >= 0.0f && a->alpha <= 1.0f)) return fail(MPCMMD_E_INVALID, "validate_risk: alpha out of [0, 1]");
+  if (a->noise != MPCMMD_NOISE_GAUSSIAN && a->noise != MPCMMD_NOISE_BETA) return fail(MPCMMD_E_INVALID, "noise");
+  if (a->variant != MPCMMD_VARIANT_STATIC && a->variant != MPCMMD_VARIANT_DYNAMIC)
+    return fail(MPCMMD_E_UNSUPPORTED, "validate_risk: static / dynamic variants only");
+  if (K == 0) return MPCMMD_OK;
+  if (!a->costs_in &&
+      (!a->cx || !a->cy || !a->init_state || !a->x_obs || !a->y_obs || !a->keys))
+    return fail(MPCMMD_E_INVALID, "null argument");
+  if (!a->count_pos || !a->var || !a->cvar || !a->mean || !a->max || (S > 0 && (!a->sigma || !a->mmd)))
+    return fail(MPCMMD_E_INVALID, "null argument");
+  for (size_t i = 0; i < size_t(K) * S; ++i)
+    if (!(std::isfinite(a->sigma[i]) && a->sigma[i] > 0.0f))
+      return fail(MPCMMD_E_INVALID, "validate_risk: every sigma must be finite and > 0");
+  ValidateRiskParams v{};
+  v.K = K, v.R = R, v.S = S;
+  if (mpcmmd_quantile_position(R, a->alpha, &v.lo, &v.hi, &v.w_lo, &v.w_hi) != MPCMMD_OK)
+    return fail(MPCMMD_E_INVALID, "validate_risk: quantile position");
+  return guarded([&] {
+    select_device(a->device);
+    struct Events {  // declared before the buffers: destroyed after they are freed
+      hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+      ~Events() {
+        for (hipEvent_t x : e)
+          if (x) (void)hipEventDestroy(x);
+      }
+    } ev;
+    Scratch dev;
+    const size_t n3 = size_t(3) * K, nc = n3 * R, T = (size_t(R) + kRiskTile - 1) / kRiskTile;
+    v.costs = (float*)dev.up(a->costs_in, nc * 4);
+    if (!a->costs_in) {
+      const ProblemConsts pc = build_constants(H, a->variant);
+      const std::vector<float> basis = pack_basis(pc);  // P, Pdot, Pddot
+      ValidateParams& r = v.roll;
+      r.K = K, r.O = O, r.H = H, r.R = R, r.noise = a->noise;
+      r.noise_level = a->noise_level, r.acc_const = a->acc_const_noise, r.steer_const = a->steer_const_noise;
+      r.K_steer = pc.K_steer, r.y_lb = pc.y_lb, r.y_ub = pc.y_ub, r.seed = a->seed;
+      r.Pdot = (const float*)dev.up(basis.data() + kNum * kNvar, kNum * kNvar * 4);
+      r.Pddot = (const float*)dev.up(basis.data() + 2 * kNum * kNvar, kNum * kNvar * 4);
+      r.cx = (const double*)dev.up(a->cx, size_t(K) * 11 * 8);
+      r.cy = (const double*)dev.up(a->cy, size_t(K) * 11 * 8);
+      r.init_state = (const double*)dev.up(a->init_state, size_t(K) * 6 * 8);
+      r.x_obs = (const float*)dev.up(a->x_obs, size_t(K) * O * 100 * 4);
+      r.y_obs = (const float*)dev.up(a->y_obs, size_t(K) * O * 100 * 4);
+      r.draws = a->draws ? (const double*)dev.up(a->draws, size_t(K) * 3 * R * H * 8) : nullptr;
+      r.keys = (const uint32_t*)dev.up(a->keys, size_t(K) * 4);
+    }
+    // one allocation of the per-channel results: count_pos | np | var | cvar | mean | max
+    int32_t* res = (int32_t*)dev.up(nullptr, n3 * 6 * 4);
+    v.count_pos = res, v.np = res + n3;
+    v.var = (float*)(res + 2 * n3), v.cvar = v.var + n3, v.mean = v.cvar + n3, v.vmax = v.mean + n3;
+    if (S > 0) {
+      v.sigma = (const float*)dev.up(a->sigma, size_t(K) * S * 4);
+      v.u = (float*)dev.up(nullptr, nc * 4);
+      v.part = (double*)dev.up(nullptr, n3 * T * S * 8);
+      v.mmd = (float*)dev.up(nullptr, n3 * S * 4);
+    }
+    if (a->elapsed_ms)
+      for (hipEvent_t& x : ev.e) HIPC(hipEventCreate(&x));
+    auto stamp = [&](int i) {
+      if (a->elapsed_ms) HIPC(hipEventRecord(ev.e[i], nullptr));
+    };
+    stamp(0);
+    if (!a->costs_in) launch_vrisk_roll(v, nullptr);
+    HIPC(hipGetLastError());
+    stamp(1);
+    launch_vrisk_stats(v, nullptr);
+    HIPC(hipGetLastError());
+    stamp(2);
+    launch_vrisk_mmd(v, nullptr);
+    HIPC(hipGetLastError());
+    stamp(3);
+    HIPC(hipDeviceSynchronize());
+    if (a->elapsed_ms)
+      for (int i = 0; i < 3; ++i) HIPC(hipEventElapsedTime(a->elapsed_ms + i, ev.e[i], ev.e[i + 1]));
+    HIPC(hipMemcpy(a->count_pos, v.count_pos, n3 * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(a->var, v.var, n3 * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(a->cvar, v.cvar, n3 * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(a->mean, v.mean, n3 * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(a->max, v.vmax, n3 * 4, hipMemcpyDeviceToHost));
+    if (S > 0) HIPC(hipMemcpy(a->mmd, v.mmd, n3 * S * 4, hipMemcpyDeviceToHost));
+    if (a->costs) HIPC(hipMemcpy(a->costs, v.costs, nc * 4, hipMemcpyDeviceToHost));
     return MPCMMD_OK;
   });
 }

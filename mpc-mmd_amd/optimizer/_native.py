@@ -29,6 +29,7 @@ SYMBOLS = (
     "mpcmmd_max_configs", "mpcmmd_solve_batch", "mpcmmd_begin_batch", "mpcmmd_finish_batch",
     "mpcmmd_carla_begin", "mpcmmd_carla_solve", "mpcmmd_path_smoothing", "mpcmmd_path_parameters",
     "mpcmmd_global_to_frenet", "mpcmmd_set_graphs", "mpcmmd_handle_info", "mpcmmd_validate_carla",
+    "mpcmmd_validate_risk", "mpcmmd_quantile_position",
 )
 
 
@@ -87,6 +88,24 @@ class ValidateCarlaArgs(C.Structure):
                 ("count_oh", C.POINTER(C.c_int32)), ("elapsed_ms", C.POINTER(C.c_float))]
 
 
+class ValidateRiskArgs(C.Structure):
+    _fields_ = [("num_cfg", C.c_int32), ("num_obs", C.c_int32), ("num_prime", C.c_int32),
+                ("num_rollouts", C.c_int32), ("noise", C.c_int32), ("variant", C.c_int32),
+                ("noise_level", C.c_double), ("acc_const_noise", C.c_double), ("steer_const_noise", C.c_double),
+                ("seed", C.c_uint32), ("device", C.c_int32),
+                ("cx", C.POINTER(C.c_double)), ("cy", C.POINTER(C.c_double)),
+                ("init_state", C.POINTER(C.c_double)), ("x_obs", C.POINTER(C.c_float)),
+                ("y_obs", C.POINTER(C.c_float)), ("draws", C.POINTER(C.c_double)),
+                ("keys", C.POINTER(C.c_uint32)), ("alpha", C.c_float), ("num_sigma", C.c_int32),
+                ("sigma", C.POINTER(C.c_float)), ("costs_in", C.POINTER(C.c_float)),
+                ("count_pos", C.POINTER(C.c_int32)), ("var", C.POINTER(C.c_float)), ("cvar", C.POINTER(C.c_float)),
+                ("mean", C.POINTER(C.c_float)), ("max", C.POINTER(C.c_float)), ("mmd", C.POINTER(C.c_float)),
+                ("costs", C.POINTER(C.c_float)), ("elapsed_ms", C.POINTER(C.c_float))]
+
+
+RISK_CHANNELS = ("obs", "lane_lb", "lane_ub")
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -140,6 +159,8 @@ def lib():
     L.mpcmmd_host_constant.argtypes = [C.POINTER(Config), C.c_char_p, C.POINTER(C.c_double), C.c_size_t]
     L.mpcmmd_validate.argtypes = [C.POINTER(ValidateArgs)]
     L.mpcmmd_validate_carla.argtypes = [C.POINTER(ValidateCarlaArgs)]
+    L.mpcmmd_validate_risk.argtypes = [C.POINTER(ValidateRiskArgs)]
+    L.mpcmmd_quantile_position.argtypes = [C.c_int32, C.c_float, ip, ip, fp, fp]
     L.mpcmmd_obs_dynamic_traj.argtypes = [C.c_int32, fp, fp, fp, fp, fp, C.c_float, fp, fp]
     cargs = [vp, C.c_int32, C.c_int32, fp, fp, fp, fp, fp, C.c_float, C.POINTER(Path), C.POINTER(Draws)]
     L.mpcmmd_set_graphs.argtypes = [vp, C.c_int32]
@@ -265,6 +286,78 @@ def validate_carla(init_state, v, steer, x_obs, y_obs, paths, keys, num_prime, n
         out["count_oh"] = oh
     if timing:
         out["elapsed_ms"] = float(ms.value)
+    return out
+
+
+def quantile_position(n, alpha):
+    """mpcmmd_quantile_position: (lo, hi, w_lo, w_hi) of the linear quantile of n
+    ascending samples with fp32 weights (jnp.quantile).  No GPU needed."""
+    lo, hi, wl, wh = C.c_int32(), C.c_int32(), C.c_float(), C.c_float()
+    check(lib().mpcmmd_quantile_position(int(n), float(alpha), C.byref(lo), C.byref(hi), C.byref(wl), C.byref(wh)))
+    return lo.value, hi.value, np.float32(wl.value), np.float32(wh.value)
+
+
+def validate_risk(cx=None, cy=None, init_state=None, x_obs=None, y_obs=None, keys=None, num_prime=30,
+                  noise="gaussian", noise_level=0.1, acc_const_noise=0.0, steer_const_noise=0.0, num_rollouts=1000,
+                  variant="static", draws=None, seed=0, device=0, alpha=0.98, sigma=None, costs_in=None,
+                  return_costs=False, timing=False):
+    """mpcmmd_validate_risk over K configurations (include/mpcmmd.h): the plan
+    inputs of ``validate``; ``sigma`` [K,S] (or [S], shared) the MMD bandwidths;
+    ``costs_in`` [K,3,R] fp32 replaces the rollouts (the plan inputs may then be
+    None).  Returns a dict of count_pos (int32), var, cvar, mean, max, saa
+    [K,3] (channels RISK_CHANNELS), mmd [K,3,S], and the reference's lane sums
+    cvar_lane [K], mmd_lane [K,S]; with ``return_costs`` costs [K,3,R], with
+    ``timing`` elapsed_ms [3] (rollout, statistics, MMD stages)."""
+    d = lambda a, *shape: np.ascontiguousarray(np.asarray(a, np.float64).reshape(*shape))
+    f = lambda a, *shape: np.ascontiguousarray(np.asarray(a, np.float32).reshape(*shape))
+    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    H = int(num_prime)
+    cin = ks = dr = None
+    if costs_in is not None:
+        cin = np.ascontiguousarray(np.asarray(costs_in, np.float32))
+        if cin.ndim != 3 or cin.shape[1] != 3:
+            raise ValueError("costs_in must be [K, 3, R]")
+        K, _, R = cin.shape
+        O = 1
+        cx = cy = st = xo = yo = None
+    else:
+        R = int(num_rollouts)
+        cx = np.atleast_2d(np.asarray(cx, np.float64))
+        K = cx.shape[0]
+        cx, cy, st = d(cx, K, 11), d(cy, K, 11), d(init_state, K, 6)
+        xo = f(x_obs, K, -1, 100) if K else np.zeros((0, 1, 100), np.float32)
+        yo = f(y_obs, K, -1, 100) if K else np.zeros((0, 1, 100), np.float32)
+        O = xo.shape[1]
+        ks = np.ascontiguousarray(np.asarray(keys, np.int64).reshape(K).astype(np.uint32))
+        dr = None if draws is None else d(draws, K, 3, R, H)
+    if sigma is None:
+        sg = np.zeros((K, 0), np.float32)
+    else:
+        sg = np.asarray(sigma, np.float32)
+        sg = np.ascontiguousarray(np.broadcast_to(sg, (K, sg.shape[-1])) if sg.ndim == 1 else sg.reshape(K, -1))
+    S = sg.shape[1]
+    out = dict(count_pos=np.zeros((K, 3), np.int32))
+    out.update({k: np.zeros((K, 3), np.float32) for k in ("var", "cvar", "mean", "max")})
+    out["mmd"] = np.zeros((K, 3, S), np.float32)
+    costs = np.zeros((K, 3, R), np.float32) if return_costs else None
+    ms = (C.c_float * 3)()
+    args = ValidateRiskArgs(K, O, H, R, NOISE[noise], VARIANT[variant], float(noise_level), float(acc_const_noise),
+                            float(steer_const_noise), int(seed) & 0xFFFFFFFF, int(device), dp(cx), dp(cy), dp(st),
+                            _fptr(xo), _fptr(yo), dp(dr),
+                            None if ks is None else ks.ctypes.data_as(C.POINTER(C.c_uint32)), float(alpha), S,
+                            _fptr(sg) if S else None, _fptr(cin), ip(out["count_pos"]), _fptr(out["var"]),
+                            _fptr(out["cvar"]), _fptr(out["mean"]), _fptr(out["max"]),
+                            _fptr(out["mmd"]) if S else None, _fptr(costs),
+                            C.cast(ms, C.POINTER(C.c_float)) if timing else None)
+    check(lib().mpcmmd_validate_risk(C.byref(args)))
+    out["saa"] = (out["count_pos"].astype(np.float32) / np.float32(R)).astype(np.float32)
+    out["cvar_lane"] = (out["cvar"][:, 1] + out["cvar"][:, 2]).astype(np.float32)
+    out["mmd_lane"] = (out["mmd"][:, 1] + out["mmd"][:, 2]).astype(np.float32)
+    if return_costs:
+        out["costs"] = costs
+    if timing:
+        out["elapsed_ms"] = np.array(list(ms), np.float32)
     return out
 
 

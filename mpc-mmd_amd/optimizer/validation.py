@@ -134,6 +134,49 @@ def compute_stats_batch(prob, cx, cy, init_state, x_obs, y_obs, vx_obs, vy_obs, 
                             device=prob._cfg.device)
 
 
+def risk_stats_batch(prob, cx, cy, init_state, x_obs, y_obs, vx_obs, vy_obs, num_prime, noise_level, noise, keys,
+                     sigma=None, draws=None, num_rollouts=NUM_ROLLOUTS, x_obs_traj=None, y_obs_traj=None, rng="numpy",
+                     return_costs=False, timing=False):
+    """The optimizer's cost terms on the validation rollouts of every
+    configuration (``mpcmmd_validate_risk``): per channel (obs, lane_lb,
+    lane_ub) the count of positive samples, SAA, VaR / CVaR at
+    ``prob.alpha_quant``, mean, max, and the uniform-weight MMD at the
+    bandwidths ``sigma`` ([S] shared or [K, S]).  Inputs and draws as
+    ``compute_stats_batch``: the same ``keys`` (and ``rng``) roll the same
+    points.  Returns ``_native.validate_risk``'s dict."""
+    if rng not in RNGS:
+        raise ValueError(f"rng must be one of {RNGS}")
+    if x_obs_traj is None:
+        xt, yt = _tracks(prob, x_obs, y_obs, vx_obs, vy_obs)
+    else:
+        xt = np.asarray(x_obs_traj, np.float32).reshape(len(keys), prob.num_obs, 100)
+        yt = np.asarray(y_obs_traj, np.float32).reshape(len(keys), prob.num_obs, 100)
+    if draws is None and rng == "numpy":
+        cx2, cy2 = np.atleast_2d(cx), np.atleast_2d(cy)
+        draws = np.stack([reference_draws(prob, cx2[k], cy2[k], num_prime, noise, keys[k], num_rollouts)
+                          for k in range(len(keys))])
+    return _native.validate_risk(cx, cy, init_state, xt, yt, keys, num_prime, noise, noise_level,
+                                 prob.acc_const_noise, prob.steer_const_noise, num_rollouts, prob.variant, draws,
+                                 device=prob._cfg.device, alpha=prob.alpha_quant, sigma=sigma,
+                                 return_costs=return_costs, timing=timing)
+
+
+RISK_STATS = ("count_pos", "saa", "var", "cvar", "mean", "max", "mmd")
+
+
+def risk_arrays(cost, out):
+    """The ``risk_<cost>_<channel>_<stat>`` arrays of one cost's
+    ``validate_risk`` dict, plus the reference's lane sums
+    (``risk_<cost>_lane_cvar``, ``risk_<cost>_lane_mmd``)."""
+    r = {}
+    for c, ch in enumerate(_native.RISK_CHANNELS):
+        for st in RISK_STATS:
+            r[f"risk_{cost}_{ch}_{st}"] = np.asarray(out[st])[:, c]
+    r[f"risk_{cost}_lane_cvar"] = np.asarray(out["cvar_lane"])
+    r[f"risk_{cost}_lane_mmd"] = np.asarray(out["mmd_lane"])
+    return r
+
+
 # --------------------------------------------------------------------------
 # the validation script (S/validation.py:202-464, D/validation.py)
 
@@ -175,13 +218,17 @@ def common_configs(d_cvar, d_mmd_opt, num_obs):
 
 
 def validate_files(prob, d_cvar, d_mmd_opt, noise, noise_level, num_prime, num_obs, variant="static",
-                   stats_fn=None, num_rollouts=NUM_ROLLOUTS, rng="numpy"):
+                   stats_fn=None, num_rollouts=NUM_ROLLOUTS, rng="numpy", risk=False, risk_sigma=(), risk_fn=None):
     """coll_* arrays of one sweep point (S/validation.py:279-364): both costs'
     optima of every common configuration k, validated with key k.
     ``stats_fn(d, idx, keys)`` -> (count, count_lane) replaces the GPU call
-    (CPU tests)."""
+    (CPU tests).  With ``risk`` also the ``risk_<cost>_<channel>_<stat>``
+    arrays (``risk_arrays``) of both costs at the bandwidths ``risk_sigma``,
+    and ``risk_sigma`` itself; ``risk_fn(d, idx, keys)`` -> a
+    ``validate_risk`` dict replaces that GPU call."""
     rows = common_configs(d_cvar, d_mmd_opt, num_obs)
     keys = np.arange(len(rows))
+    sig = np.asarray(risk_sigma, np.float32).reshape(-1)
 
     def run(d, idx):
         if not len(idx):
@@ -199,12 +246,30 @@ def validate_files(prob, d_cvar, d_mmd_opt, noise, noise_level, num_prime, num_o
                                        rng=rng)
         return np.asarray(c, np.float64), np.asarray(l, np.float64)
 
+    def run_risk(d, idx):
+        if risk_fn is not None:
+            return risk_fn(d, idx, keys)
+        g = lambda name: np.asarray(d[name])[idx]
+        if variant == "dynamic":
+            return risk_stats_batch(prob, g("cx"), g("cy"), g("init_state"), None, None, None, None, num_prime,
+                                    noise_level, noise, keys, sigma=sig, num_rollouts=num_rollouts,
+                                    x_obs_traj=g("x_obs_traj"), y_obs_traj=g("y_obs_traj"), rng=rng)
+        return risk_stats_batch(prob, g("cx"), g("cy"), g("init_state"), g("x_obs"), g("y_obs"), g("vx_obs"),
+                                g("vy_obs"), num_prime, noise_level, noise, keys, sigma=sig,
+                                num_rollouts=num_rollouts, rng=rng)
+
     c_opt, l_opt = run(d_mmd_opt, [m for _, m in rows])
     c_cvar, l_cvar = run(d_cvar, [c for c, _ in rows])
     # np.append onto [] (S/validation.py:355-362) gives float64 arrays; the
     # mmd_random lists stay empty (their compute_stats is commented out, :336-342)
-    return dict(coll_cvar=c_cvar, coll_cvar_lane=l_cvar, coll_mmd_opt=c_opt, coll_mmd_opt_lane=l_opt,
-                coll_mmd_random=np.zeros(0), coll_mmd_random_lane=np.zeros(0))
+    out = dict(coll_cvar=c_cvar, coll_cvar_lane=l_cvar, coll_mmd_opt=c_opt, coll_mmd_opt_lane=l_opt,
+               coll_mmd_random=np.zeros(0), coll_mmd_random_lane=np.zeros(0))
+    if risk:
+        out["risk_sigma"] = sig
+        if len(rows):
+            out.update(risk_arrays("mmd_opt", run_risk(d_mmd_opt, [m for _, m in rows])))
+            out.update(risk_arrays("cvar", run_risk(d_cvar, [c for c, _ in rows])))
+    return out
 
 
 def main(argv=None):
@@ -221,6 +286,10 @@ def main(argv=None):
     ap.add_argument("--stats_root", default="./stats")
     ap.add_argument("--rng", default="numpy", choices=RNGS,
                     help="numpy: the reference's np.random.seed(k) draws (default); philox: the library's streams")
+    ap.add_argument("--risk", action="store_true",
+                    help="also write the risk_<cost>_<channel>_<stat> arrays (mpcmmd_validate_risk)")
+    ap.add_argument("--risk-sigma", type=float, nargs="+", default=[],
+                    help="MMD bandwidths of --risk (e.g. 0.01, mmd_random's)")
     a = ap.parse_args(argv)
     from .cem import CEM
     for noise in a.noises:
@@ -236,7 +305,7 @@ def main(argv=None):
                         if a.variant == "static":
                             load("mmd_random")  # the static script requires the file (:243-245), unused
                         out = validate_files(prob, d_cvar, d_opt, noise, noise_level, num_prime, num_obs, a.variant,
-                                             rng=a.rng)
+                                             rng=a.rng, risk=a.risk, risk_sigma=a.risk_sigma)
                         dst = stats_path(a.stats_root, noise, noise_level, num_prime, num_reduced, num_obs)
                         os.makedirs(os.path.dirname(dst), exist_ok=True)
                         np.savez(dst, **out)
