@@ -1,6 +1,7 @@
-// What the C ABI's source files (mpcmmd.hip, validate_api.hip) share: the
-// thread's last error, HIP error checking and a scratch allocator for the
-// entry points that use no handle.  Internal to the library.
+// What the C ABI's HIP sources (handle.hip, begin.hip, sequence.hip,
+// validate_api.hip) share: the thread's last error (host_api.hpp), HIP error
+// checking and a scratch allocator for the entry points that use no handle.
+// Internal to the library.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,12 +9,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/mpcmmd.h"
+#include "host_api.hpp"
 
 namespace mpcmmd {
-
-// records msg as the calling thread's mpcmmd_last_error and returns code (mpcmmd.hip)
-__attribute__((visibility("hidden"))) int fail(int code, const std::string& msg);
 
 struct HipError : std::runtime_error {
   using std::runtime_error::runtime_error;

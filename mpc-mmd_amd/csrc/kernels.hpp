@@ -26,7 +26,8 @@ struct Params {
   float sigma_acc, sigma_steer, acc_const, steer_const, K_steer;
   float y_lb, y_ub;
   float w_obs, w_lane;
-  // constants (device)
+  // constants (device).  Every pointer below is a device buffer of the handle:
+  // buffers.hpp lists them (type, element count, condition) under these names
   const float* basis;      // [3][100][11] fp32: P, Pd, Pdd
   const double* guess_g;   // [2][11][4]  (x: v-columns, y: y-columns)
   const double* proj_m;    // [2][11][11] (Kinv[:11,:11] for x, y)
@@ -169,7 +170,6 @@ struct Cfg {
   int32_t* tr_obs;
   int32_t* tr_cem;
 };
-HDI_CONST size_t gtab_stride(int S, int H) { return size_t(4) * 4 * 4 * S * H; }  // == gamma_tab_size (rng.hpp)
 __device__ inline Cfg cfg_of(const Params& p, int g) {
   Cfg c;
   const size_t T = size_t(p.T), H = size_t(p.H), S = size_t(p.S), O = size_t(p.O);
@@ -275,7 +275,7 @@ size_t validate_carla_lds(int O, int H, int P);  // dynamic LDS bytes of a workg
 bool launch_validate_carla(const ValidateCarlaParams& v, size_t lds_limit, hipStream_t s);
 void launch_gamma_tab(const Params& p, int t, hipStream_t s);
 void launch_beta_planes(const Params& p, int t, hipStream_t s);
-// mmd_opt risk, one launch each (mpcmmd.hip chains them)
+// mmd_opt risk, one launch each (sequence.hip chains them)
 void launch_mother(const Params& p, int t, hipStream_t s);
 void launch_dist_pad(const Params& p, int cap, hipStream_t s);  // once per handle (cap candidates), before the first launch_bdist
 void launch_bdist(const Params& p, hipStream_t s);

@@ -60,6 +60,8 @@ constexpr int kFeatStride = 24;
 constexpr int kMom = 12;
 constexpr int kMomStride = 16;
 constexpr int kMomR = 12;
+// doubles per configuration of Params::gtab
+HDI_CONST size_t gtab_stride(int S, int H) { return size_t(4) * 4 * 4 * S * H; }  // == gamma_tab_size (rng.hpp)
 constexpr int kMaxSplit = 8;  // workgroups per candidate of the row-sum kernels
 constexpr int kMaxPath = 2048;  // CARLA path points (the reference's num_path = 600)
 constexpr int kMaxDetObs = 32;  // obstacles of compute_cem_det (k_front's per-lane non-finite mask: 2 bits each)

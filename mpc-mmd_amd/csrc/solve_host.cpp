@@ -5,7 +5,6 @@
 #include <cstring>
 #include <stdexcept>
 
-#include "../../include/mpcmmd.h"
 #include "layout.hpp"
 
 namespace mpcmmd {
@@ -223,18 +222,3 @@ void plan_speed(const ProblemConsts& pc, const float* cx, const float* cy, float
 }
 
 }  // namespace mpcmmd
-
-// The linear quantile's position among n ascending samples with JAX's fp32
-// weights (jnp.quantile: pos = alpha (n - 1) in fp32, low = floor, w = pos -
-// low).  Host only; mpcmmd_validate_risk takes its order statistics from here.
-extern "C" int mpcmmd_quantile_position(int32_t n, float alpha, int32_t* lo, int32_t* hi, float* w_lo, float* w_hi) {
-  if (n < 1 || !(alpha >= 0.0f && alpha <= 1.0f) || !lo || !hi || !w_lo || !w_hi) return MPCMMD_E_INVALID;
-  const float pos = alpha * float(n - 1);
-  const float fl = std::floor(pos), ce = std::ceil(pos);
-  const float hw = pos - fl;
-  *w_hi = hw;
-  *w_lo = 1.0f - hw;
-  *lo = int32_t(std::min(std::max(fl, 0.0f), float(n - 1)));
-  *hi = int32_t(std::min(std::max(ce, 0.0f), float(n - 1)));
-  return MPCMMD_OK;
-}

@@ -1,5 +1,5 @@
 // Host arithmetic of libmpcmmd's create / begin / finish paths: what the
-// handle code (mpcmmd.hip, validate_api.hip) uploads as raw bytes or unpacks
+// handle code (handle.hip, begin.hip, sequence.hip, validate_api.hip) uploads as raw bytes or unpacks
 // from a result.  No HIP: compiled by g++, built a second time under
 // ASan/UBSan (tests/native/asan_host.cpp) and tested on the CPU.
 #pragma once

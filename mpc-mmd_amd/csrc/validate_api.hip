@@ -23,6 +23,37 @@ void select_device(int device) {
   HIPC(hipSetDevice(device));
 }
 
+// the noise kind and the variant family of a validation call (carla: a CARLA
+// town; else static / dynamic): MPCMMD_OK, or the entry point's own code and
+// message for a variant of the other family
+int check_noise_variant(int noise, int variant, bool carla, int code, const char* msg) {
+  if (noise != MPCMMD_NOISE_GAUSSIAN && noise != MPCMMD_NOISE_BETA) return fail(MPCMMD_E_INVALID, "noise");
+  const bool ok = carla ? variant == MPCMMD_VARIANT_CARLA_TOWN05 || variant == MPCMMD_VARIANT_CARLA_TOWN10HD
+                        : variant == MPCMMD_VARIANT_STATIC || variant == MPCMMD_VARIANT_DYNAMIC;
+  return ok ? MPCMMD_OK : fail(code, msg);
+}
+
+// the plan inputs of mpcmmd_validate / mpcmmd_validate_risk on the device
+// (count and count_lane stay null)
+template <class Args>
+void plan_params(const Args& a, Scratch& dev, ValidateParams& v) {
+  const int K = a.num_cfg, O = a.num_obs, H = a.num_prime, R = a.num_rollouts;
+  const ProblemConsts pc = build_constants(H, a.variant);
+  const std::vector<float> basis = pack_basis(pc);  // P, Pdot, Pddot
+  v.K = K, v.O = O, v.H = H, v.R = R, v.noise = a.noise;
+  v.noise_level = a.noise_level, v.acc_const = a.acc_const_noise, v.steer_const = a.steer_const_noise;
+  v.K_steer = pc.K_steer, v.y_lb = pc.y_lb, v.y_ub = pc.y_ub, v.seed = a.seed;
+  v.Pdot = (const float*)dev.up(basis.data() + kNum * kNvar, kNum * kNvar * 4);
+  v.Pddot = (const float*)dev.up(basis.data() + 2 * kNum * kNvar, kNum * kNvar * 4);
+  v.cx = (const double*)dev.up(a.cx, size_t(K) * 11 * 8);
+  v.cy = (const double*)dev.up(a.cy, size_t(K) * 11 * 8);
+  v.init_state = (const double*)dev.up(a.init_state, size_t(K) * 6 * 8);
+  v.x_obs = (const float*)dev.up(a.x_obs, size_t(K) * O * 100 * 4);
+  v.y_obs = (const float*)dev.up(a.y_obs, size_t(K) * O * 100 * 4);
+  v.draws = a.draws ? (const double*)dev.up(a.draws, size_t(K) * 3 * R * H * 8) : nullptr;
+  v.keys = (const uint32_t*)dev.up(a.keys, size_t(K) * 4);
+}
+
 }  // namespace
 
 extern "C" {
@@ -31,32 +62,18 @@ int mpcmmd_validate(const mpcmmd_validate_args* a) {
   if (!a) return fail(MPCMMD_E_INVALID, "null argument");
   const int K = a->num_cfg, O = a->num_obs, H = a->num_prime, R = a->num_rollouts;
   if (K < 0 || R < 1 || !validate_shape_ok(O, H)) return fail(MPCMMD_E_INVALID, "validate: shape out of range");
-  if (a->noise != MPCMMD_NOISE_GAUSSIAN && a->noise != MPCMMD_NOISE_BETA) return fail(MPCMMD_E_INVALID, "noise");
-  if (a->variant != MPCMMD_VARIANT_STATIC && a->variant != MPCMMD_VARIANT_DYNAMIC)
-    return fail(MPCMMD_E_UNSUPPORTED,
-                "validate: static / dynamic variants (S/validation.py, D/validation.py); CARLA plans: "
-                "mpcmmd_validate_carla");
+  if (int rc = check_noise_variant(a->noise, a->variant, false, MPCMMD_E_UNSUPPORTED,
+                                   "validate: static / dynamic variants (S/validation.py, D/validation.py); CARLA "
+                                   "plans: mpcmmd_validate_carla"))
+    return rc;
   if (K == 0) return MPCMMD_OK;
   if (!a->cx || !a->cy || !a->init_state || !a->x_obs || !a->y_obs || !a->keys || !a->count || !a->count_lane)
     return fail(MPCMMD_E_INVALID, "null argument");
   return guarded([&] {
     select_device(a->device);
-    const ProblemConsts pc = build_constants(H, a->variant);
-    const std::vector<float> basis = pack_basis(pc);  // P, Pdot, Pddot
     Scratch dev;
     ValidateParams v{};
-    v.K = K, v.O = O, v.H = H, v.R = R, v.noise = a->noise;
-    v.noise_level = a->noise_level, v.acc_const = a->acc_const_noise, v.steer_const = a->steer_const_noise;
-    v.K_steer = pc.K_steer, v.y_lb = pc.y_lb, v.y_ub = pc.y_ub, v.seed = a->seed;
-    v.Pdot = (const float*)dev.up(basis.data() + kNum * kNvar, kNum * kNvar * 4);
-    v.Pddot = (const float*)dev.up(basis.data() + 2 * kNum * kNvar, kNum * kNvar * 4);
-    v.cx = (const double*)dev.up(a->cx, size_t(K) * 11 * 8);
-    v.cy = (const double*)dev.up(a->cy, size_t(K) * 11 * 8);
-    v.init_state = (const double*)dev.up(a->init_state, size_t(K) * 6 * 8);
-    v.x_obs = (const float*)dev.up(a->x_obs, size_t(K) * O * 100 * 4);
-    v.y_obs = (const float*)dev.up(a->y_obs, size_t(K) * O * 100 * 4);
-    v.draws = a->draws ? (const double*)dev.up(a->draws, size_t(K) * 3 * R * H * 8) : nullptr;
-    v.keys = (const uint32_t*)dev.up(a->keys, size_t(K) * 4);
+    plan_params(*a, dev, v);
     v.count = (int32_t*)dev.up(nullptr, size_t(K) * 4);
     v.count_lane = (int32_t*)dev.up(nullptr, size_t(K) * 4);
     launch_validate(v, nullptr);
@@ -73,9 +90,9 @@ int mpcmmd_validate_carla(const mpcmmd_validate_carla_args* a) {
   const int K = a->num_cfg, O = a->num_obs, H = a->num_prime, R = a->num_rollouts, P = a->num_path;
   if (K < 0 || K > 65535 || R < 1 || !validate_carla_shape_ok(O, H, P) || int64_t(R) * H >= (int64_t(1) << 31))
     return fail(MPCMMD_E_INVALID, "validate_carla: shape out of range");
-  if (a->noise != MPCMMD_NOISE_GAUSSIAN && a->noise != MPCMMD_NOISE_BETA) return fail(MPCMMD_E_INVALID, "noise");
-  if (a->variant != MPCMMD_VARIANT_CARLA_TOWN05 && a->variant != MPCMMD_VARIANT_CARLA_TOWN10HD)
-    return fail(MPCMMD_E_INVALID, "validate_carla: a CARLA variant (static / dynamic optima: mpcmmd_validate)");
+  if (int rc = check_noise_variant(a->noise, a->variant, true, MPCMMD_E_INVALID,
+                                   "validate_carla: a CARLA variant (static / dynamic optima: mpcmmd_validate)"))
+    return rc;
   if (K == 0) return MPCMMD_OK;
   if (!a->init_state || !a->v || !a->steer || !a->x_obs || !a->y_obs || !a->path || !a->keys || !a->count ||
       !a->count_lane || !a->count_rows)
@@ -155,9 +172,9 @@ int mpcmmd_validate_risk(const mpcmmd_validate_risk_args* a) {
     return fail(MPCMMD_E_INVALID, "validate_risk: shape out of range");
   if (S < 0 || S > kRiskMaxSigma) return fail(MPCMMD_E_INVALID, "validate_risk: num_sigma out of [0, 8]");
   if (!(a->alpha >= 0.0f && a->alpha <= 1.0f)) return fail(MPCMMD_E_INVALID, "validate_risk: alpha out of [0, 1]");
-  if (a->noise != MPCMMD_NOISE_GAUSSIAN && a->noise != MPCMMD_NOISE_BETA) return fail(MPCMMD_E_INVALID, "noise");
-  if (a->variant != MPCMMD_VARIANT_STATIC && a->variant != MPCMMD_VARIANT_DYNAMIC)
-    return fail(MPCMMD_E_UNSUPPORTED, "validate_risk: static / dynamic variants only");
+  if (int rc = check_noise_variant(a->noise, a->variant, false, MPCMMD_E_UNSUPPORTED,
+                                   "validate_risk: static / dynamic variants only"))
+    return rc;
   if (K == 0) return MPCMMD_OK;
   if (!a->costs_in &&
       (!a->cx || !a->cy || !a->init_state || !a->x_obs || !a->y_obs || !a->keys))
@@ -183,23 +200,7 @@ int mpcmmd_validate_risk(const mpcmmd_validate_risk_args* a) {
     Scratch dev;
     const size_t n3 = size_t(3) * K, nc = n3 * R, T = (size_t(R) + kRiskTile - 1) / kRiskTile;
     v.costs = (float*)dev.up(a->costs_in, nc * 4);
-    if (!a->costs_in) {
-      const ProblemConsts pc = build_constants(H, a->variant);
-      const std::vector<float> basis = pack_basis(pc);  // P, Pdot, Pddot
-      ValidateParams& r = v.roll;
-      r.K = K, r.O = O, r.H = H, r.R = R, r.noise = a->noise;
-      r.noise_level = a->noise_level, r.acc_const = a->acc_const_noise, r.steer_const = a->steer_const_noise;
-      r.K_steer = pc.K_steer, r.y_lb = pc.y_lb, r.y_ub = pc.y_ub, r.seed = a->seed;
-      r.Pdot = (const float*)dev.up(basis.data() + kNum * kNvar, kNum * kNvar * 4);
-      r.Pddot = (const float*)dev.up(basis.data() + 2 * kNum * kNvar, kNum * kNvar * 4);
-      r.cx = (const double*)dev.up(a->cx, size_t(K) * 11 * 8);
-      r.cy = (const double*)dev.up(a->cy, size_t(K) * 11 * 8);
-      r.init_state = (const double*)dev.up(a->init_state, size_t(K) * 6 * 8);
-      r.x_obs = (const float*)dev.up(a->x_obs, size_t(K) * O * 100 * 4);
-      r.y_obs = (const float*)dev.up(a->y_obs, size_t(K) * O * 100 * 4);
-      r.draws = a->draws ? (const double*)dev.up(a->draws, size_t(K) * 3 * R * H * 8) : nullptr;
-      r.keys = (const uint32_t*)dev.up(a->keys, size_t(K) * 4);
-    }
+    if (!a->costs_in) plan_params(*a, dev, v.roll);
     // one allocation of the per-channel results: count_pos | np | var | cvar | mean | max
     int32_t* res = (int32_t*)dev.up(nullptr, n3 * 6 * 4);
     v.count_pos = res, v.np = res + n3;

@@ -1,12 +1,16 @@
 // Host-code sanitizer harness ("run the CPU-side C++ under
 // ASan/UBSan").  Built by `make -C mpc-mmd_amd asan` with
 // -fsanitize=address,undefined from the library's own host sources
-// (csrc/host_constants.cpp, carla_host.cpp, solve_host.cpp), no GPU and no HIP
-// runtime.  Exercises every host-only entry: the batch-invariant constants of
-// each variant and horizon (mpcmmd_host_constant's builders) and the
+// (csrc/*.cpp: host_constants, carla_host, solve_host, host_api), no GPU and no
+// HIP runtime.  Exercises every host-only entry: the batch-invariant constants
+// of each variant and horizon (mpcmmd_host_constant's builders) and the
 // dynamic-obstacle QP trajectories (mpcmmd_obs_dynamic_traj's builder), then
 // prints one line per quantity ("name count sum sumabs") for
-// tests/test_asan_host.py to compare with the product library's values.
+// tests/test_asan_host.py to compare with the product library's values.  The
+// C entry points that need no device (host_api.cpp) are called with valid and
+// with each kind of invalid argument, mpcmmd_create_batch's range check at its
+// boundaries, and the device buffer list (buffers.hpp) is expanded for five
+// shapes; a wrong status ends the run with exit code 3.
 //
 // Given a file name, it also writes there the inputs and results of the path
 // helpers (carla_host.cpp) and of every function of solve_host.cpp at the
@@ -16,10 +20,15 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "../../mpc-mmd_amd/csrc/buffers.hpp"
+#include "../../mpc-mmd_amd/csrc/host_api.hpp"
 #include "../../mpc-mmd_amd/csrc/host_constants.hpp"
 #include "../../mpc-mmd_amd/csrc/layout.hpp"
 #include "../../mpc-mmd_amd/csrc/solve_host.hpp"
@@ -213,7 +222,162 @@ static void beta_case(int n) {
   put(c + "beta_z", beta_z_image(z.data(), M));
 }
 
+static void expect(const char* what, int got, int want) {
+  if (got == want) return;
+  std::fprintf(stderr, "asan_host: %s: status %d, expected %d (%s)\n", what, got, want, mpcmmd_last_error());
+  std::exit(3);
+}
+static void expect_true(const char* what, bool ok) { expect(what, ok ? 1 : 0, 1); }
+
+// host_api.cpp: each entry point once with valid small inputs and once per documented invalid argument
+static void api_cases() {
+  const int OK = MPCMMD_OK, BAD = MPCMMD_E_INVALID;
+  expect("abi_version", mpcmmd_abi_version(), MPCMMD_ABI_VERSION);
+  // path smoothing / parameters / Frenet states of a 6-point path
+  const int P = 6;
+  std::vector<float> xw(P), yw(P), x(P), y(P), Fxd(P), Fyd(P), Fxdd(P), Fydd(P), arc(P), kap(P);
+  for (int i = 0; i < P; ++i) xw[i] = 2.0f * float(i), yw[i] = 0.05f * float(i * i);
+  float len = 0.0f;
+  expect("path_smoothing", mpcmmd_path_smoothing(P, xw.data(), yw.data(), 0.1f, x.data(), y.data()), OK);
+  expect("path_smoothing null", mpcmmd_path_smoothing(P, nullptr, yw.data(), 0.1f, x.data(), y.data()), BAD);
+  expect("path_smoothing null out", mpcmmd_path_smoothing(P, xw.data(), yw.data(), 0.1f, x.data(), nullptr), BAD);
+  expect("path_smoothing 3", mpcmmd_path_smoothing(3, xw.data(), yw.data(), 0.1f, x.data(), y.data()), BAD);
+  expect("path_smoothing kMaxPath + 1",
+         mpcmmd_path_smoothing(kMaxPath + 1, xw.data(), yw.data(), 0.1f, x.data(), y.data()), BAD);
+  expect_true("last_error", std::strlen(mpcmmd_last_error()) > 0);
+  expect("path_parameters", mpcmmd_path_parameters(P, x.data(), y.data(), Fxd.data(), Fyd.data(), Fxdd.data(),
+                                                   Fydd.data(), arc.data(), kap.data(), &len), OK);
+  expect("path_parameters null", mpcmmd_path_parameters(P, x.data(), nullptr, Fxd.data(), Fyd.data(), Fxdd.data(),
+                                                        Fydd.data(), arc.data(), kap.data(), &len), BAD);
+  expect("path_parameters 2", mpcmmd_path_parameters(2, x.data(), y.data(), Fxd.data(), Fyd.data(), Fxdd.data(),
+                                                     Fydd.data(), arc.data(), kap.data(), &len), BAD);
+  mpcmmd_path pth{P, x.data(), y.data(), arc.data(), Fxd.data(), Fyd.data(), kap.data()};
+  const int N = 3;
+  const std::vector<float> gx = {1.0f, 4.5f, 9.0f}, gy = {0.2f, -0.3f, 1.0f}, gv = {5.0f, 6.0f, 7.0f};
+  const std::vector<float> gvd = {0.1f, 0.0f, -0.1f}, gpsi = {0.0f, 0.1f, 0.2f}, gpd = {0.0f, 0.01f, 0.02f};
+  std::vector<float> fr(size_t(N) * 7);
+  expect("global_to_frenet", mpcmmd_global_to_frenet(&pth, N, gx.data(), gy.data(), gv.data(), gvd.data(), gpsi.data(),
+                                                     gpd.data(), fr.data()), OK);
+  expect("global_to_frenet count 0",
+         mpcmmd_global_to_frenet(&pth, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), OK);
+  expect("global_to_frenet null path", mpcmmd_global_to_frenet(nullptr, N, gx.data(), gy.data(), gv.data(), gvd.data(),
+                                                               gpsi.data(), gpd.data(), fr.data()), BAD);
+  expect("global_to_frenet count < 0", mpcmmd_global_to_frenet(&pth, -1, gx.data(), gy.data(), gv.data(), gvd.data(),
+                                                               gpsi.data(), gpd.data(), fr.data()), BAD);
+  expect("global_to_frenet null out", mpcmmd_global_to_frenet(&pth, N, gx.data(), gy.data(), gv.data(), gvd.data(),
+                                                              gpsi.data(), gpd.data(), nullptr), BAD);
+  mpcmmd_path bad = pth;
+  bad.num_path = 1;
+  expect("global_to_frenet num_path 1", mpcmmd_global_to_frenet(&bad, N, gx.data(), gy.data(), gv.data(), gvd.data(),
+                                                                gpsi.data(), gpd.data(), fr.data()), BAD);
+  bad = pth;
+  bad.kappa = nullptr;
+  expect("global_to_frenet null path array", mpcmmd_global_to_frenet(&bad, N, gx.data(), gy.data(), gv.data(),
+                                                                     gvd.data(), gpsi.data(), gpd.data(), fr.data()), BAD);
+  // host constants: every name (the det KKT of a CARLA configuration), then the refusals
+  mpcmmd_config cfg{};
+  cfg.num_reduced = 4, cfg.num_obs = 2, cfg.noise_level = 0.1f, cfg.num_prime = 8, cfg.num_batch = 32;
+  cfg.maxiter_cem = 2;
+  for (const char* name : {"P", "Pdot", "Pddot", "P_prime", "P64", "Pdot64", "Pddot64", "guess_kinv_x", "guess_kinv_y",
+                           "proj_kinv_x", "proj_kinv_y", "fit", "det_kinv_x", "det_kinv_y"}) {
+    cfg.variant = std::strncmp(name, "det_", 4) == 0 ? MPCMMD_VARIANT_CARLA_TOWN05 : MPCMMD_VARIANT_STATIC;
+    const int cnt = mpcmmd_host_constant(&cfg, name, nullptr, 0);
+    expect_true(name, cnt > 0);
+    std::vector<double> v(cnt);
+    expect(name, mpcmmd_host_constant(&cfg, name, v.data(), v.size()), cnt);
+    expect("host_constant count too small", mpcmmd_host_constant(&cfg, name, v.data(), v.size() - 1), BAD);
+  }
+  expect("host_constant unknown name", mpcmmd_host_constant(&cfg, "no_such_constant", nullptr, 0), BAD);
+  expect("host_constant null cfg", mpcmmd_host_constant(nullptr, "P", nullptr, 0), BAD);
+  expect("host_constant null name", mpcmmd_host_constant(&cfg, nullptr, nullptr, 0), BAD);
+  // dynamic obstacle tracks of two obstacles
+  const int O = 2;
+  const std::vector<float> x0 = {30.0f, 40.0f}, y0 = {1.75f, -1.75f}, vx0 = {3.0f, 4.0f}, vy0 = {0.0f, 0.1f};
+  const std::vector<float> vd = {4.0f, 5.0f};
+  std::vector<float> xt(size_t(O) * kNum), yt(size_t(O) * kNum);
+  expect("obs_dynamic_traj", mpcmmd_obs_dynamic_traj(O, x0.data(), y0.data(), vx0.data(), vy0.data(), vd.data(), -1.75f,
+                                                     xt.data(), yt.data()), OK);
+  expect("obs_dynamic_traj 0",
+         mpcmmd_obs_dynamic_traj(0, nullptr, nullptr, nullptr, nullptr, nullptr, -1.75f, nullptr, nullptr), OK);
+  expect("obs_dynamic_traj -1", mpcmmd_obs_dynamic_traj(-1, x0.data(), y0.data(), vx0.data(), vy0.data(), vd.data(),
+                                                        -1.75f, xt.data(), yt.data()), BAD);
+  expect("obs_dynamic_traj null", mpcmmd_obs_dynamic_traj(O, x0.data(), nullptr, vx0.data(), vy0.data(), vd.data(),
+                                                          -1.75f, xt.data(), yt.data()), BAD);
+  int32_t lo = -1, hi = -1;
+  float wl = 0.0f, wh = 0.0f;
+  expect("quantile_position", mpcmmd_quantile_position(10, 0.95f, &lo, &hi, &wl, &wh), OK);
+  expect_true("quantile_position values", lo == 8 && hi == 9 && wl + wh == 1.0f);
+  expect("quantile_position n 0", mpcmmd_quantile_position(0, 0.5f, &lo, &hi, &wl, &wh), BAD);
+  expect("quantile_position alpha", mpcmmd_quantile_position(10, 1.5f, &lo, &hi, &wl, &wh), BAD);
+  expect("quantile_position null", mpcmmd_quantile_position(10, 0.5f, nullptr, &hi, &wl, &wh), BAD);
+}
+
+// mpcmmd_create_batch's range check at each boundary it names
+static void create_range_cases() {
+  const int OK = MPCMMD_OK, BAD = MPCMMD_E_INVALID, UNS = MPCMMD_E_UNSUPPORTED;
+  mpcmmd_config base{};
+  base.num_reduced = 4, base.num_obs = 3, base.noise_level = 0.1f, base.num_prime = 10, base.num_batch = 32;
+  base.maxiter_cem = 2;
+  auto with = [&](int32_t mpcmmd_config::*field, int32_t value) {
+    mpcmmd_config c = base;
+    c.*field = value;
+    return c;
+  };
+  expect("base", check_create_ranges(base, 1), OK);
+  expect("max_configs 0", check_create_ranges(base, 0), BAD);
+  expect("num_batch 19", check_create_ranges(with(&mpcmmd_config::num_batch, 19), 1), BAD);
+  expect("num_batch 20", check_create_ranges(with(&mpcmmd_config::num_batch, 20), 1), OK);
+  expect("num_batch 4096", check_create_ranges(with(&mpcmmd_config::num_batch, 4096), 1), OK);
+  expect("num_batch 4097", check_create_ranges(with(&mpcmmd_config::num_batch, 4097), 1), BAD);
+  expect("num_prime 1", check_create_ranges(with(&mpcmmd_config::num_prime, 1), 1), BAD);
+  expect("num_prime 2", check_create_ranges(with(&mpcmmd_config::num_prime, 2), 1), OK);
+  expect("num_prime 100", check_create_ranges(with(&mpcmmd_config::num_prime, 100), 1), OK);
+  expect("num_prime 101", check_create_ranges(with(&mpcmmd_config::num_prime, 101), 1), BAD);
+  expect("num_reduced 1", check_create_ranges(with(&mpcmmd_config::num_reduced, 1), 1), BAD);
+  expect("num_reduced 2", check_create_ranges(with(&mpcmmd_config::num_reduced, 2), 1), OK);
+  expect("num_reduced 1024", check_create_ranges(with(&mpcmmd_config::num_reduced, 1024), 1), OK);
+  expect("num_reduced 1025", check_create_ranges(with(&mpcmmd_config::num_reduced, 1025), 1), UNS);
+  mpcmmd_config c = with(&mpcmmd_config::num_prime, 2);  // num_obs * num_prime: 4096 * 2, then 2731 * 3
+  c.num_obs = 4096;
+  expect("num_obs * num_prime 8192", check_create_ranges(c, 1), OK);
+  c.num_obs = 2731, c.num_prime = 3;
+  expect("num_obs * num_prime 8193", check_create_ranges(c, 1), UNS);
+  expect("65535 candidates", check_create_ranges(with(&mpcmmd_config::num_batch, 3855), 17), OK);
+  expect("65536 candidates", check_create_ranges(with(&mpcmmd_config::num_batch, 4096), 16), UNS);
+}
+
+// buffers.hpp's list for five shapes: unique names, every buffer the shape has
+// of at least one byte, a staging area that holds every staged buffer
+static void buffer_list_cases() {
+  const BufferShape shapes[] = {
+      //  B     S   H   O   n    M       T  Gmax R0  beta   mmd_ok carla  stampw
+      {32, 4, 10, 3, 4, 16, 2, 1, 0, false, true, false, false},            // static Gaussian
+      {32, 4, 10, 3, 4, 16, 2, 1, 0, true, true, false, false},             // Beta noise
+      {32, 4, 10, 3, 4, 16, 2, 3, 0, false, true, false, false},            // batch handle
+      {1024, 500, 30, 10, 500, 250000, 2, 1, 0, true, false, false, false},  // no mmd_opt
+      {32, 4, 10, 3, 4, 16, 2, 1, 16, false, true, true, false},            // CARLA
+  };
+  for (const BufferShape& sh : shapes) {
+    const std::vector<BufferSpec> specs = buffer_specs(sh);
+    std::set<std::string> names;
+    size_t staged = 0;
+    size_t present = 0;
+    for (const BufferSpec& b : specs) {
+      expect_true(b.name, names.insert(b.name).second);
+      present += b.bytes >= 1;  // 0: the shape has no such buffer
+      if (b.staged) staged += b.bytes;
+    }
+    // all but dbgw, the Beta attempt table, the 29 mmd_opt and the 8 CARLA buffers exist for every shape
+    expect("buffers present", int(present),
+           int(specs.size()) - 1 - (sh.beta_noise ? 0 : 1) - (sh.mmd_ok ? 0 : 29) - (sh.carla ? 0 : 8));
+    expect_true("staging capacity", staging_bytes(specs) >= staged);
+  }
+}
+
 int main(int argc, char** argv) {
+  api_cases();
+  create_range_cases();
+  buffer_list_cases();
   for (int variant = 0; variant < 4; ++variant) {
     for (int H : {2, 8, 20, 30, 50, 60, 100}) {
       if (variant >= 2 && H > 100) continue;

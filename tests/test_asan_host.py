@@ -4,7 +4,10 @@ item 8): `make -C mpc-mmd_amd asan` builds csrc/host_constants.cpp with
 builds every variant's constants and the dynamic-obstacle QP tracks.  The run
 must be clean (any ASan / UBSan report aborts it: -fno-sanitize-recover), and
 its values must equal the product library's (mpcmmd_host_constant,
-mpcmmd_obs_dynamic_traj: no GPU needed)."""
+mpcmmd_obs_dynamic_traj: no GPU needed).  The harness also calls the entry
+points of csrc/host_api.cpp with valid and invalid arguments, the range check
+of mpcmmd_create_batch at its boundaries and the expansion of the device buffer
+list (csrc/buffers.hpp); a wrong status there fails its run."""
 import math
 import os
 import shutil

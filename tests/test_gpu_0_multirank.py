@@ -9,7 +9,7 @@ this file sorts before every other GPU test.
 
 The one-process solve holds 12 configurations x num_batch 100 = 1200
 candidates, so its beta-CEM runs as two candidate groups on two streams
-(mpcmmd.hip: run_beta_cem), while each rank's 6-configuration batches run as
+(sequence.hip: run_beta_cem), while each rank's 6-configuration batches run as
 one: the rows must not depend on the grouping either."""
 import os
 import socket

@@ -6,7 +6,7 @@ k_bdirect_pairs (nb <= 256) or k_bkernel<false> + the row-sorted k_bdirect,
 the parts per candidate of both row-sum kernels (ker_split), k_bqp at 64 or
 128 threads, the waves per candidate of k_bselect (sel_waves), k_bsample or
 k_bsample_chunks (nb >= 384), the fused k_bcem_small, and candidate groups on
-separate streams with b0 offsets.  mpcmmd.hip claims "a candidate's bits do
+separate streams with b0 offsets.  handle.hip claims "a candidate's bits do
 not depend on how the batch is split into groups or whether k_bcem_small
 runs it"; these tests hold every candidate of a launch to that claim:
 

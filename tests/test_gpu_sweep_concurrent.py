@@ -54,7 +54,7 @@ def test_batch_equals_sequential(cost, n, noise, variant):
 def test_batch_two_groups_equals_sequential():
     """A batch of 12 configurations x num_batch 100 (1200 candidates) runs its
     beta-CEM as two candidate groups on two streams, the group boundary
-    inside a configuration (mpcmmd.hip: run_beta_cem) -- the production
+    inside a configuration (sequence.hip: run_beta_cem) -- the production
     path of `optimizer.sweep --batch 32`: rows bit-identical to one
     configuration at a time."""
     from optimizer import _native
