@@ -79,6 +79,27 @@ constexpr double kInvRidge = 20.0;
 // carries their top-n rows, sigma, QP solution and cost
 HDI int first_sample(int tb) { return tb > 0 ? kBetaElite : 0; }
 
+// The elite rows [11][M + 1] (fp32) and position means [pos_pad(M)] (fp64)
+// that candidate b's generators re-encode (layout.hpp: gen_u): k_belite of
+// beta-iteration t writes half (t + 1) & 1 of Params::belite, which k_bgen /
+// k_bsigma of iteration t and the sampler of iteration t + 1 read -- `half`
+// is t + 1 for all three.
+DEVI const float* gen_elites(const Params& p, int half, int b) {
+  return p.belite + (size_t(half & 1) * p.Bt + b) * kBetaElite * (p.M + 1);
+}
+DEVI const double* gen_mean_row(const Params& p, int b) {
+  return p.gen + size_t(b) * pos_pad(p.M) * kGenStride + gen_means(pos_pad(p.M));
+}
+
+// raw buffer loads: lane offset (bytes) in a VGPR, wave-uniform offset in an
+// SGPR; out of range returns 0
+DEVI float buf_ld_f(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 0));
+}
+DEVI double buf_ld_d(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
+  return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 0));
+}
+
 #define kconst __attribute__((address_space(4)))
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -200,8 +221,10 @@ HDI EliteLds elite_lds(int M1, int waves = kThreads / 64) {
   return L;
 }
 
-// the fused kernel's sampler: an LDS copy of the candidate's generators and
-// every block's T (betacem_sample.hpp: bsample_tblocks)
+// the fused kernel's sampler: an LDS copy of the candidate's generators
+// ([W plane][U rows: pos_pad(M) x kGenRow, formed in place][genm]) and every
+// block's T (betacem_sample.hpp: bsample_tblocks)
+HDI size_t lds_uplane(int Pp) { return size_t(Pp) * kGenRow; }  // doubles from the W plane to the U rows
 HDI size_t gen_lds_bytes(int M) { return size_t(pos_pad(M)) * (2 * kGenRow + 1) * 8 + 16 * 8; }  // + wA's overreach
 HDI size_t tblk_lds_bytes(int M) { return size_t(pos_pad(M) >> 4) * 4 * 64 * 8; }
 

@@ -99,13 +99,12 @@ DEVI void belite_body(const Params& p, int tb, int b, char* smem) {
   float* Enew = p.belite + (size_t((tb + 1) & 1) * p.Bt + b) * kBetaElite * M1;
   const int ys = ygen_stride(M);
   const float* Y = p.ygen + size_t(b) * kBzCols * ys;
-  const double rs10 = 1.0 / sqrt(10.0);
-  double* gen = p.gen + size_t(b) * pos_pad(M) * kGenStride;
+  double* gmean = p.gen + size_t(b) * pos_pad(M) * kGenStride + gen_means(pos_pad(M));
   const int nblk = (M1 + 15) / 16;
   const int span = ((nblk * 16 + 63) / 64) * 64;  // whole waves
   for (int j = tid; j < span; j += blockDim.x) {
     const bool valid = j < M1;
-    double u[kBetaElite], mean;
+    double u[kBetaElite];
     {
       float v[kBetaElite];
       double s = 0.0;
@@ -136,8 +135,9 @@ DEVI void belite_body(const Params& p, int tb, int b, char* smem) {
       }
       const double m = s / double(kBetaElite);
 #pragma unroll
-      for (int q = 0; q < kBetaElite; ++q) u[q] = valid ? (double(v[q]) - m) * rs10 : 0.0;
-      mean = valid ? double(float(m)) : 0.0;
+      for (int q = 0; q < kBetaElite; ++q) u[q] = valid ? gen_u(v[q], m) : 0.0;
+      // the generators' readers re-form u from Enew and this mean (layout.hpp)
+      if (valid) gmean[j] = m;
     }
     // level 1: block sums G = U^T U of u u^T over each 16-position block (66
     // packed entries) on fp64 MFMA: the wave's four blocks one at a time, the
@@ -152,7 +152,6 @@ DEVI void belite_body(const Params& p, int tb, int b, char* smem) {
       if ((lane >> 4) == k) {
 #pragma unroll
         for (int q = 0; q < kBetaElite; ++q) ub[(lane & 15) * kUPitch + q] = u[q];
-        ub[(lane & 15) * kUPitch + kGenMean] = mean;  // the U row's slot 11 (the MFMA below masks it)
       }
       wave_sync();
       d4 G = d4{0.0, 0.0, 0.0, 0.0};
@@ -160,15 +159,6 @@ DEVI void belite_body(const Params& p, int tb, int b, char* smem) {
       for (int st = 0; st < 4; ++st) {
         const double x = r < 11 ? ub[(4 * st + h) * kUPitch + r] : 0.0;
         G = mfma64(x, x, G);
-      }
-      // the block's u rows into gen from the same staging: consecutive lanes
-      // on consecutive features of a row, so a store instruction covers ~6
-      // position rows (a lane per position wrote 64 rows per instruction)
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {  // whole rows: u_0..u_10 and the mean
-        const int e = lane + 64 * i, row = e / kGenRow, q = e - row * kGenRow;
-        const int pos = blk * 16 + row;
-        if (pos < M1) gen[gen_uplane(pos_pad(M)) + size_t(pos) * kGenRow + q] = ub[row * kUPitch + q];
       }
       wave_sync();
       // register i: G[h + 4 i][r]; the packed upper triangle a <= c
@@ -249,9 +239,9 @@ DEVI double rsq_nr(double d) {
   return y;
 }
 
-// Block blk (< nblk) of candidate b on the calling wave.  xl: the wave's 32
-// doubles of LDS.
-DEVI void bgen_wave(const Params& p, int b, int blk, double* xl) {
+// Block blk (< nblk) of candidate b on the calling wave, after k_belite of
+// beta-iteration tb.  xl: the wave's 32 doubles of LDS.
+DEVI void bgen_wave(const Params& p, int tb, int b, int blk, double* xl) {
   const int M = p.M, M1 = M + 1, nblk = (M1 + 15) / 16, Pp = pos_pad(M);
   const int lane = tidx() & 63, r = lane & 15, h = lane >> 4;
   double* gen = p.gen + size_t(b) * Pp * kGenStride;
@@ -260,15 +250,19 @@ DEVI void bgen_wave(const Params& p, int b, int blk, double* xl) {
   d4 A;
   double U[3];
   const double* Gb = p.phib + (size_t(b) * nblk + blk) * 66;
+  const float* E = gen_elites(p, tb + 1, b);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int a = h + 4 * i;
     A[i] = a < 11 && r < 11 ? Gb[sym11i(min(a, 10), min(r, 10))] : 0.0;
   }
+  const int jr = min(j0 + r, M);  // clamped: the loads unconditional
+  const double mr = gen_mean_row(p, b)[jr];
 #pragma unroll
   for (int s = 0; s < 3; ++s) {
     const int f = 4 * s + h;  // feature 11 is the mean's slot: zero here
-    U[s] = f < 11 && j0 + r < M1 ? gen[gen_uplane(Pp) + size_t(j0 + r) * kGenRow + f] : 0.0;
+    const float e = E[size_t(min(f, 10)) * M1 + jr];
+    U[s] = f < 11 && j0 + r < M1 ? gen_u(e, mr) : 0.0;
   }
   // sweep: A_kk <- -1/d, A_ik = A_ki <- A_ik / d, A_ij <- A_ij - A_ik A_kj / d
 #pragma unroll
@@ -371,16 +365,17 @@ DEVI void bsigma_body(const Params& p, int tb, int b, double* red) {
       for (int a = 0; a < 11; ++a) red[(tid >> 6) * 11 + a] = part[a];
     __syncthreads();
     if (tid == 0) {
-      const double* g = gen + size_t(M) * kGenRow;
-      const double* gu = g + gen_uplane(pos_pad(M));
+      // u_M and the mean's slot of the NEW generators (this iteration's k_belite)
+      const float* EM = gen_elites(p, tb + 1, b) + M;
+      const double mM = gen_mean_row(p, b)[M];
       double d = 0.0;
       for (int a = 0; a < 11; ++a) {
         double sa = 0.0;
         for (int w2 = 0; w2 < kThreads / 64; ++w2) sa += red[w2 * 11 + a];
-        d += gu[a] * sa;
+        d += gen_u(EM[size_t(a) * (M + 1)], mM) * sa;
       }
       const double zM = z[bz_index(M, si)];
-      const float yM = float((gu[kGenMean] + p.genm[size_t(b) * pos_pad(M) + M] * zM) + d);
+      const float yM = float((gen_mean_slot(mM) + p.genm[size_t(b) * pos_pad(M) + M] * zM) + d);
       p.sigma[b] = fmaxf(yM, 0.01f);
     }
   }

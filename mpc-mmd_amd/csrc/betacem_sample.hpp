@@ -43,6 +43,10 @@ HDI int sample_chunk(int nblk) {
   while ((nblk + cl - 1) / cl > kChunkWavesMax) cl <<= 1;
   return cl;
 }
+// The blocks every sampler walks: those that hold a position 0..M.  The
+// chunking stays that of the padded count pos_pad(M) / 16 (a pair of blocks
+// more at most, pure padding: W^T Z of zeros into sums nothing reads).
+HDI int sample_blocks(int M) { return (M + 1 + 15) >> 4; }
 template <int TPW>
 constexpr int sample_waves() {
   static_assert(kSampleTiles % TPW == 0, "tiles per wave");
@@ -51,32 +55,48 @@ constexpr int sample_waves() {
 
 // Operands of one block, loaded unconditionally (generators and normals are
 // zero padded to whole blocks and tiles), so the loop has no branches and the
-// compiler can count outstanding loads exactly.  Generator rows (k_belite,
-// k_bgen): W plane = w_0..w_10 and a zero slot 11, U plane = u_0..u_10 and the
-// position's mean in slot 11, genm = L_jj.  With row 11 of S_pre held at 1
-// (and row 11 of S_loc exactly 0, W's slot 11 being 0), U S carries the mean
-// as its twelfth term: no mean operand, no accumulator initialisation.
+// compiler can count outstanding loads exactly.  Generators (k_belite,
+// k_bgen; layout.hpp): W plane = w_0..w_10 and a zero slot 11, genm = L_jj,
+// and the U row u_0..u_10 with the position's mean in slot 11, which
+// block_u forms from the elite rows' fp32 values and the fp64 mean.  With
+// row 11 of S_pre held at 1 (and row 11 of S_loc exactly 0, W's slot 11 being
+// 0), U S carries the mean as its twelfth term: no mean operand, no
+// accumulator initialisation.
 template <int TPW>
 struct SampleBlock {
   double wA[4];  // W[p0 + 4k + h][r]        (A of W^T Z; r = feature)
   double wX[3];  // W[p0 + r][4i + h]        (A of W U^T; 4i + h = feature)
-  double uX[3];  // U[p0 + r][4i + h]        (B of W U^T, A of U S; feature 11 = mean)
+  float eX[3];   // E[4i + h][p0 + r]        (the elite value of U[p0 + r][4i + h]; feature 11: unused)
+  double m;      // elite mean of position p0 + r (0 at padding positions)
   double L;      // L_jj of position p0 + r
   float z[TPW][4];   // Z[p0 + 4k + h][sample of (tile t, lane r)] (sample_of); fp32 normals, widened at use
 };
 
+// U[p0 + r][4i + h] of a loaded block (B of W U^T, A of U S; feature 11 =
+// the mean).  TAIL: the block may hold positions past the sigma coordinate
+// (valid = p0 + r <= M), whose u is 0 as their mean is: the elite rows are
+// not padded, so there eX holds some other value.
+template <bool TAIL, int TPW>
+DEVI void block_u(const SampleBlock<TPW>& q, double (&uX)[3], int h, bool valid) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) uX[i] = gen_u(TAIL && !valid ? 0.0f : q.eX[i], q.m);
+  uX[2] = h == 3 ? gen_mean_slot(q.m) : uX[2];
+}
+
+// E: the candidate's elite rows (gen_elites), mrow its means (gen_mean_row)
 template <int TPW>
-DEVI void load_block(SampleBlock<TPW>& q, const double* G, const double* GU, const double* gm, const float* z, int p0,
-                     int s0, int r, int h) {
+DEVI void load_block(SampleBlock<TPW>& q, const double* G, const float* E, const double* mrow, const double* gm,
+                     const float* z, int M, int p0, int s0, int r, int h) {
 #pragma unroll
   for (int k = 0; k < 4; ++k) q.wA[k] = G[size_t(p0 + 4 * k + h) * kGenRow + kGenW + r];  // rows > 11 of S unused
   const double* g = G + size_t(p0 + r) * kGenRow;
-  const double* gu = GU + size_t(p0 + r) * kGenRow;
+  const float* e = E + min(p0 + r, M);  // clamped into the rows, as the feature below (block_u masks both)
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
     q.wX[i] = g[kGenW + 4 * i + h];  // W's zero slot 11 times U's mean: X gets no mean term
-    q.uX[i] = gu[4 * i + h];
+    q.eX[i] = e[size_t(min(4 * i + h, kBetaElite - 1)) * (M + 1)];
   }
+  q.m = mrow[p0 + r];
   q.L = gm[p0 + r];
   // tiles in pairs: lane r of tiles 2u, 2u + 1 takes samples 32u + 2r, 32u +
   // 2r + 1 -- the lane image of bz_index, six float4 loads per block (one
@@ -105,25 +125,30 @@ DEVI void load_block(SampleBlock<TPW>& q, const double* G, const double* GU, con
 // a block's 17 loads need no per-lane address arithmetic and no 64-bit
 // address registers (the walker runs at 1 wave per SIMD, where every VALU
 // instruction and register counts).  Same addresses as load_block.
+// The elite rows' buffer ends with row 10: feature 11's load (lanes h = 3 of
+// i = 2) and a padding position's in row 10 are out of range and return 0; a
+// padding position's in the rows before reads the next row (block_u's mask).
 struct SampleRsrc {
-  __amdgpu_buffer_rsrc_t gen, genm, z;
-  int vA, vX, vL, vZ;  // lane offsets (bytes): W^T rows, W / U rows, L_jj, normals
-  int uplane;          // bytes from the W plane to the U plane
+  __amdgpu_buffer_rsrc_t gen, genm, z, el;
+  int vA, vX, vL, vZ, vE;  // lane offsets (bytes): W^T rows, W rows, L_jj / mean, normals, elite values
+  int means;               // bytes from the W plane to the means
+  int erow;                // bytes of four elite rows (features 4i + h -> 4(i + 1) + h)
 };
-DEVI SampleRsrc sample_rsrc(const double* G, const double* gm, const float* z, int Pp, int r, int h) {
+DEVI SampleRsrc sample_rsrc(const double* G, const float* E, const double* gm, const float* z, int M, int r, int h) {
   SampleRsrc s;
+  const int Pp = pos_pad(M);
   s.gen = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(G), short(0), Pp * kGenStride * 8, 0x00020000);
+  s.el = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(E), short(0), kBetaElite * (M + 1) * 4, 0x00020000);
   s.genm = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(gm), short(0), Pp * 8, 0x00020000);
   s.z = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(z), short(0), Pp * kBzCols * 4, 0x00020000);
   s.vA = (h * kGenRow + kGenW + r) * 8;
   s.vX = (r * kGenRow + h) * 8;
   s.vL = r * 8;
   s.vZ = (r + 16 * h) * 16;
-  s.uplane = Pp * kGenRow * 8;
+  s.vE = (h * (M + 1) + r) * 4;
+  s.means = int(gen_means(Pp)) * 8;
+  s.erow = 4 * (M + 1) * 4;
   return s;
-}
-DEVI double buf_ld_d(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
-  return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 0));
 }
 DEVI void load_block_buf(SampleBlock<kSampleTiles>& q, const SampleRsrc& s, int p0) {
   const int sg = p0 * kGenRow * 8;
@@ -132,8 +157,9 @@ DEVI void load_block_buf(SampleBlock<kSampleTiles>& q, const SampleRsrc& s, int 
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
     q.wX[i] = buf_ld_d(s.gen, s.vX + 32 * i, sg);
-    q.uX[i] = buf_ld_d(s.gen, s.vX + 32 * i, sg + s.uplane);
+    q.eX[i] = buf_ld_f(s.el, s.vE, p0 * 4 + i * s.erow);
   }
+  q.m = buf_ld_d(s.gen, s.vL, p0 * 8 + s.means);
   q.L = buf_ld_d(s.genm, s.vL, p0 * 8);
   const int szz = (p0 >> 4) * (16 * kBzCols * 4);
 #pragma unroll
@@ -160,8 +186,10 @@ DEVI void load_block_buf(SampleBlock<kSampleTiles>& q, const SampleRsrc& s, int 
 // Tiles are interleaved, so every accumulator chain has 6 MFMAs between
 // dependent steps.  No VALU work on the accumulators: the pipe never waits
 // for a vector add between blocks.
-template <int TPW>
-DEVI void block_mfma(const SampleBlock<TPW>& cur, d4* S, const d4* Sp, d4* Y, int r, int h) {
+template <bool TAIL = false, int TPW>
+DEVI void block_mfma(const SampleBlock<TPW>& cur, d4* S, const d4* Sp, d4* Y, int r, int h, bool valid = true) {
+  double uX[3];
+  block_u<TAIL>(cur, uX, h, valid);
   double zd[TPW][4];  // the fp32 normals widened once (exact), used by two MFMA chains
 #pragma unroll
   for (int t = 0; t < TPW; ++t)
@@ -169,7 +197,7 @@ DEVI void block_mfma(const SampleBlock<TPW>& cur, d4* S, const d4* Sp, d4* Y, in
     for (int k = 0; k < 4; ++k) zd[t][k] = double(cur.z[t][k]);
   d4 X = d4{0.0, 0.0, 0.0, 0.0};  // X = W_c U_c^T: register i holds w_{h+4i} . u_r = T[row r][col h + 4i]
 #pragma unroll
-  for (int i = 0; i < 3; ++i) X = mfma64(cur.wX[i], cur.uX[i], X);
+  for (int i = 0; i < 3; ++i) X = mfma64(cur.wX[i], uX[i], X);
   const d4 zero = d4{0.0, 0.0, 0.0, 0.0};
   // B operand of U S: S_pre + S_loc (rows 0..11 of S: registers 0..2)
   double St[TPW][3];
@@ -180,7 +208,7 @@ DEVI void block_mfma(const SampleBlock<TPW>& cur, d4* S, const d4* Sp, d4* Y, in
 #pragma unroll
   for (int k = 0; k < 3; ++k)
 #pragma unroll
-    for (int t = 0; t < TPW; ++t) Y[t] = mfma64(St[t][k], cur.uX[k], k == 0 ? zero : Y[t]);
+    for (int t = 0; t < TPW; ++t) Y[t] = mfma64(St[t][k], uX[k], k == 0 ? zero : Y[t]);
 #pragma unroll
   for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -251,8 +279,63 @@ DEVI void fold_chunk(d4& Sp, d4& S) {
   S = d4{0.0, 0.0, 0.0, 0.0};
 }
 
+// Blocks [c0, c1) (c1 > c0) in order on the calling wave, c1 - 1 the last
+// block a caller walks before its sums are dropped.  Blocks in pairs,
+// operands and outputs ping-ponged: the next block's loads are in flight and
+// its MFMAs issued while the previous block's samples are converted and
+// stored (sched barriers keep that order).  The pairs stop short of block
+// c1 - 1, which may hold positions past the sigma coordinate M: it is peeled,
+// alone or after its unpaired predecessor, with block_u's mask.  pair_end(c)
+// follows the second block of the pair that starts at c (the walker's chunk
+// folds: chunk lengths are even, so no chunk ends inside the peeled blocks
+// but with the walk).
+template <int TPW, class Load, class Store, class PairEnd>
+DEVI void walk_blocks(int c0, int c1, int M, int r, int h, d4* S, const d4* Sp, Load&& load, Store&& store,
+                      PairEnd&& pair_end) {
+  d4 Ya[TPW], Yb[TPW];
+  SampleBlock<TPW> qa, qb;
+  const int last = c1 - 1;
+  const bool valid = (last << 4) + r <= M;
+  load(qa, c0 << 4);
+  int c = c0;
+  for (; c + 2 <= last; c += 2) {
+    const int p0 = c << 4;
+    load(qb, p0 + 16);
+    __builtin_amdgcn_sched_barrier(0);
+    block_mfma(qa, S, Sp, Ya, r, h);
+    __builtin_amdgcn_sched_barrier(0);
+    if (c > c0) store(Yb, p0 - 16);
+    __builtin_amdgcn_sched_barrier(0);
+    load(qa, p0 + 32);  // <= last
+    __builtin_amdgcn_sched_barrier(0);
+    block_mfma(qb, S, Sp, Yb, r, h);
+    pair_end(c);
+    __builtin_amdgcn_sched_barrier(0);
+    store(Ya, p0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  const int p0 = c << 4;
+  if (c < last) {  // two blocks left (wave-uniform)
+    load(qb, p0 + 16);
+    __builtin_amdgcn_sched_barrier(0);
+    block_mfma(qa, S, Sp, Ya, r, h);
+    __builtin_amdgcn_sched_barrier(0);
+    if (c > c0) store(Yb, p0 - 16);
+    __builtin_amdgcn_sched_barrier(0);
+    block_mfma<true>(qb, S, Sp, Yb, r, h, valid);
+    __builtin_amdgcn_sched_barrier(0);
+    store(Ya, p0);
+    store(Yb, p0 + 16);
+  } else {
+    block_mfma<true>(qa, S, Sp, Ya, r, h, valid);
+    __builtin_amdgcn_sched_barrier(0);
+    if (c > c0) store(Yb, p0 - 16);
+    store(Ya, p0);
+  }
+}
+
 // k_bcem_small's sampler, from an LDS copy of the candidate's generators (lg:
-// W plane, U plane, genm, as in global memory; its workgroup just wrote them).
+// W plane, the U rows' image, genm; its workgroup just wrote them).
 // Two passes:
 //   bsample_tblocks  every block's T = strict_lower(W U^T) + diag(L_jj) (the
 //                    X MFMAs of block_mfma), once per block into LDS (Tl)
@@ -267,19 +350,19 @@ DEVI void fold_chunk(d4& Sp, d4& S) {
 constexpr int kZAhead = 4;
 
 DEVI void bsample_tblocks(const Params& p, const double* lg, double* Tl, int w, int W) {
-  const int M = p.M, Pp = pos_pad(M), nblk = Pp >> 4;
+  const int M = p.M, Pp = pos_pad(M), nblk = sample_blocks(M);
   const int lane = tidx() & 63, r = lane & 15, h = lane >> 4;
   for (int blk = w; blk < nblk; blk += W) {
     const int p0 = blk * 16;
     const double* g = lg + size_t(p0 + r) * kGenRow;
-    const double* gu = lg + gen_uplane(Pp) + size_t(p0 + r) * kGenRow;
+    const double* gu = lg + lds_uplane(Pp) + size_t(p0 + r) * kGenRow;
     double wX[3], uX[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       wX[i] = g[kGenW + 4 * i + h];
       uX[i] = gu[4 * i + h];
     }
-    const double L = lg[2 * gen_uplane(Pp) + p0 + r];
+    const double L = lg[2 * lds_uplane(Pp) + p0 + r];
     d4 X = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int i = 0; i < 3; ++i) X = mfma64(wX[i], uX[i], X);
@@ -292,11 +375,11 @@ DEVI void bsample_tblocks(const Params& p, const double* lg, double* Tl, int w, 
 }
 
 DEVI void bsample_unit_lds(const Params& p, int tb, int b, int tile, int chunk, const double* lg, const double* Tl) {
-  const int M = p.M, Pp = pos_pad(M), nblk = Pp >> 4, cl = sample_chunk(nblk);
-  const int c0 = chunk * cl, c1 = min(nblk, c0 + cl);
+  const int M = p.M, Pp = pos_pad(M), cl = sample_chunk(Pp >> 4);
+  const int c0 = chunk * cl, c1 = min(sample_blocks(M), c0 + cl);  // the walker's bound
   const int lane = tidx() & 63, r = lane & 15, h = lane >> 4, s0 = tile * 16;
   const double* LW = lg;
-  const double* LU = lg + gen_uplane(Pp);
+  const double* LU = lg + lds_uplane(Pp);
   const float* z = p.beta_z + size_t(tb - 1) * Pp * kBzCols;
   const int ys = ygen_stride(M);
   float* plane = p.ygen + size_t(b) * kBzCols * ys;

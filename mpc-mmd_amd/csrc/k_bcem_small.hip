@@ -98,13 +98,23 @@ __global__ __launch_bounds__(kSmallThreads) void k_bcem_small(Params p0, int per
     // the shared initial draws (Q3), taken from the handle's selection table
     if (tb > 0) {
       if (tb == 5) SMALL_STAMP(p, 0);
-      {  // the generators into LDS (W and U planes, genm), then the walkers
-        const int Pp = pos_pad(M);
+      {  // the generators into LDS (the W plane, an image of the U rows formed
+         // here from the elite rows and means, genm), then the walkers
+        const int Pp = pos_pad(M), M1 = M + 1;
         const double2* gsrc = reinterpret_cast<const double2*>(p.gen + size_t(b) * Pp * kGenStride);
         const double2* msrc = reinterpret_cast<const double2*>(p.genm + size_t(b) * Pp);
         double2* dst = reinterpret_cast<double2*>(smem);
-        const int ng = Pp * kGenRow, nm = Pp >> 1;  // double2 counts
-        for (int i = tid; i < ng + nm; i += kSmallThreads) dst[i] = i < ng ? gsrc[i] : msrc[i - ng];
+        const int nw = Pp * (kGenRow / 2), ng = 2 * nw, nm = Pp >> 1;  // double2 counts: W plane, both, genm
+        for (int i = tid; i < nw + nm; i += kSmallThreads) dst[i < nw ? i : i + nw] = i < nw ? gsrc[i] : msrc[i - nw];
+        const float* E = gen_elites(p, tb, b);
+        const double* mrow = gen_mean_row(p, b);
+        double* ul = reinterpret_cast<double*>(smem) + lds_uplane(Pp);
+        for (int i = tid; i < Pp * kGenRow; i += kSmallThreads) {
+          const int pos = i / kGenRow, q = i - pos * kGenRow;
+          const double m = mrow[pos];  // 0 at padding positions, whose u is 0
+          const float e = pos < M1 ? E[min(q, kBetaElite - 1) * M1 + pos] : 0.0f;
+          ul[i] = q < kBetaElite ? gen_u(e, m) : gen_mean_slot(m);
+        }
         if (tid < 8) dst[ng + nm + tid] = double2{0.0, 0.0};
       }
       __syncthreads();
@@ -197,7 +207,7 @@ __global__ __launch_bounds__(kSmallThreads) void k_bcem_small(Params p0, int per
     {
       const int nblk = (M + 1 + 15) / 16;
       double* xl = reinterpret_cast<double*>(smem) + 32 * w;
-      for (int blk = w; blk < nblk; blk += kSmallWaves) bgen_wave(p, b, blk, xl);
+      for (int blk = w; blk < nblk; blk += kSmallWaves) bgen_wave(p, tb, b, blk, xl);
     }
     __syncthreads();
     if (tb == 5) SMALL_STAMP(p, 7);

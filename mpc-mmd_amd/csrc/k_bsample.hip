@@ -35,13 +35,14 @@ __global__ __launch_bounds__(64 * sample_waves<TPW>()) void k_bsample(Params p, 
   const float* z = p.beta_z + size_t(tb - 1) * Pp * kBzCols;
   const int ys = ygen_stride(M);
   float* plane = p.ygen + size_t(b) * kBzCols * ys;
-  d4 S[TPW], Sp[TPW], Ya[TPW], Yb[TPW];
+  const float* E = gen_elites(p, tb, b);
+  d4 S[TPW], Sp[TPW];
 #pragma unroll
   for (int t = 0; t < TPW; ++t) {
     S[t] = Sp[t] = d4{0.0, 0.0, 0.0, 0.0};
     Sp[t][2] = h == 3 ? 1.0 : 0.0;  // row 11 of S_pre: the mean's coefficient
   }
-  const int nblk = Pp >> 4, cl = sample_chunk(nblk);
+  const int cl = sample_chunk(Pp >> 4);
   const __amdgpu_buffer_rsrc_t yr = ygen_rsrc(plane, ys);
   const int vl = (2 * h * ys + r) * 4, v43 = h == 0 ? vl : kDropOffset;
   auto store = [&](const d4* Yv, int q0) {
@@ -50,38 +51,18 @@ __global__ __launch_bounds__(64 * sample_waves<TPW>()) void k_bsample(Params p, 
     else
       block_store<TPW>(Yv, plane, q0, M, ys, s0, r, h);
   };
-  // blocks in pairs, operands and outputs ping-ponged: the next block's loads
-  // are in flight and its MFMAs issued while the previous block's samples
-  // are converted and stored (the last prefetch re-reads a block; nblk and
-  // the chunk length are even; sched barriers keep that order)
-  SampleBlock<TPW> qa, qb;
-  const SampleRsrc srs = sample_rsrc(G, gm, z, Pp, r, h);
+  const SampleRsrc srs = sample_rsrc(G, E, gm, z, M, r, h);
   auto load = [&](SampleBlock<TPW>& q, int q0) {
     if constexpr (TPW == kSampleTiles)
       load_block_buf(q, srs, q0);
     else
-      load_block(q, G, G + gen_uplane(Pp), gm, z, q0, s0, r, h);
+      load_block(q, G, E, gen_mean_row(p, b), gm, z, M, q0, s0, r, h);
   };
-  load(qa, 0);
-  for (int c = 0; c < nblk; c += 2) {
-    const int p0 = c << 4;
-    load(qb, p0 + 16);
-    __builtin_amdgcn_sched_barrier(0);
-    block_mfma(qa, S, Sp, Ya, r, h);
-    __builtin_amdgcn_sched_barrier(0);
-    if (c > 0) store(Yb, p0 - 16);
-    __builtin_amdgcn_sched_barrier(0);
-    load(qa, min(p0 + 32, Pp - 16));
-    __builtin_amdgcn_sched_barrier(0);
-    block_mfma(qb, S, Sp, Yb, r, h);
+  walk_blocks<TPW>(0, sample_blocks(M), M, r, h, S, Sp, load, store, [&](int c) {
     if ((c + 2) % cl == 0)
 #pragma unroll
       for (int t = 0; t < TPW; ++t) fold_chunk(Sp[t], S[t]);
-    __builtin_amdgcn_sched_barrier(0);
-    store(Ya, p0);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  store(Yb, Pp - 16);
+  });
   MPCMMD_STAMP(p, 1);
 }
 
@@ -129,30 +110,18 @@ __global__ __launch_bounds__(64 * kChunkWavesMax) void k_bsample_chunks(Params p
     for (int i = 0; i < 3; ++i) dS[k][i][lane] = Sl[i];
   }
   __syncthreads();
-  d4 S[1] = {d4{0.0, 0.0, 0.0, 0.0}}, Sp[1] = {d4{0.0, 0.0, 0.0, 0.0}}, Ya[1], Yb[1];
+  d4 S[1] = {d4{0.0, 0.0, 0.0, 0.0}}, Sp[1] = {d4{0.0, 0.0, 0.0, 0.0}};
   Sp[0][2] = h == 3 ? 1.0 : 0.0;  // row 11 of S_pre: the mean's coefficient (the chunks' row 11 sums are 0)
   for (int j = 0; j < k; ++j)
 #pragma unroll
     for (int i = 0; i < 3; ++i) Sp[0][i] = Sp[0][i] + dS[j][i][lane];
-  SampleBlock<1> qa, qb;
-  const int pend = c1 << 4;
-  load_block(qa, G, G + gen_uplane(Pp), gm, z, c0 << 4, s0, r, h);
-  for (int c = c0; c < c1; c += 2) {
-    const int p0 = c << 4;
-    load_block(qb, G, G + gen_uplane(Pp), gm, z, p0 + 16, s0, r, h);
-    __builtin_amdgcn_sched_barrier(0);
-    block_mfma(qa, S, Sp, Ya, r, h);
-    __builtin_amdgcn_sched_barrier(0);
-    if (c > c0) block_store<1>(Yb, plane, p0 - 16, M, ys, s0, r, h);
-    __builtin_amdgcn_sched_barrier(0);
-    load_block(qa, G, G + gen_uplane(Pp), gm, z, min(p0 + 32, pend - 16), s0, r, h);
-    __builtin_amdgcn_sched_barrier(0);
-    block_mfma(qb, S, Sp, Yb, r, h);
-    __builtin_amdgcn_sched_barrier(0);
-    block_store<1>(Ya, plane, p0, M, ys, s0, r, h);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  block_store<1>(Yb, plane, pend - 16, M, ys, s0, r, h);
+  const float* E = gen_elites(p, tb, b);
+  const double* mrow = gen_mean_row(p, b);
+  // the last chunk ends with the last block that holds a position (the walker's bound)
+  walk_blocks<1>(
+      c0, min(sample_blocks(M), c1), M, r, h, S, Sp,
+      [&](SampleBlock<1>& q, int q0) { load_block(q, G, E, mrow, gm, z, M, q0, s0, r, h); },
+      [&](const d4* Yv, int q0) { block_store<1>(Yv, plane, q0, M, ys, s0, r, h); }, [](int) {});
   MPCMMD_STAMP(p, 1);
 }
 

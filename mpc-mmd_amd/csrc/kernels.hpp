@@ -107,7 +107,7 @@ struct Params {
   float* btop;             // [B][100][n]  QP solutions
   float* bcost;            // [B][100]     QP costs
   float* belite;           // [2][B][11][M+1] elite sample vectors (ping-pong)
-  double* gen;             // [B][W, U plane][pos_pad(M)][kGenRow] (pad rows 0)
+  double* gen;             // [B][2][pos_pad(M)][kGenRow]: the W plane (pad rows 0), then pos_pad(M) elite means (layout.hpp)
   double* phib;            // [B][ceil((M+1)/16)][66] Phi at the start of each 16-position block
   int32_t* bimin;          // [B] argmin sample of the last beta-iteration
   double* genm;            // [B][pos_pad(M)]  L_jj of the generators (pad 0)

@@ -20,17 +20,28 @@ constexpr int kEliteCost = 20;         // cem.py:140
 constexpr int kCnormStride = 12;       // doubles per candidate of Params::cnorm (11 norms)
 constexpr int kElite = 5;              // cem.py:138
 constexpr int kResultStride = 11 + 11 + 2 + 1 + 20 + kMaxReduced;  // cx, cy, lane, obs, sigma, res_beta, beta
-// generators per candidate: two planes of pos_pad(M) rows x kGenRow doubles,
-// W (features 0..10, slot 11 zero) then U (features 0..10, the position's
-// fp32-rounded elite mean in slot 11), and L_jj in Params::genm.  The sampler
-// feeds slot 11 through the 16x16x4 MFMA operands unmasked: W's zero slot
-// keeps the mean out of W U^T, and row 11 of its S_pre is 1, so U S adds the
-// mean.  192 B per position; planes, not interleaved rows, so k_bgen's U
-// reads and W writes never share a line.
+// generators per candidate: a W plane of pos_pad(M) rows x kGenRow doubles
+// (features 0..10, slot 11 zero), L_jj in Params::genm, and the U rows
+// (features u_0..u_10, the position's fp32-rounded elite mean in slot 11).
+// The U rows are not stored: u_e of a position is the elite row E_e
+// (Params::belite, fp32, row stride M + 1) re-encoded against the position's
+// fp64 elite mean m, and every user forms it with gen_u / gen_mean_slot below
+// (one expression, so one set of bits).  k_belite writes the means to the
+// first pos_pad(M) doubles after the W plane (gen_means; padding positions
+// keep the allocation's 0).  The rest of that second plane of the candidate's
+// kGenStride doubles per position -- it held the U rows -- is neither written
+// nor read: the allocation keeps its size only because the buffer sizes are
+// pinned.  The sampler feeds slot 11 through the 16x16x4 MFMA
+// operands unmasked: W's zero slot keeps the mean out of W U^T, and row 11 of
+// its S_pre is 1, so U S adds the mean.
 constexpr int kGenRow = 12;
 constexpr int kGenStride = 2 * kGenRow;  // doubles per position and candidate
 constexpr int kGenW = 0, kGenMean = 11;
-HDI_CONST size_t gen_uplane(int Pp) { return size_t(Pp) * kGenRow; }  // U plane offset
+HDI_CONST size_t gen_means(int Pp) { return size_t(Pp) * kGenRow; }  // offset of the means: [pos_pad(M)] fp64
+constexpr double kRsqrt10 = 0x1.43d136248490fp-2;  // 1.0 / sqrt(10.0) in fp64 arithmetic (jnp.cov's 1 / (11 - 1))
+// u_e of a position from its elite value and mean; slot 11 of the U row
+HDI_CONST double gen_u(float e, double m) { return (double(e) - m) * kRsqrt10; }
+HDI_CONST double gen_mean_slot(double m) { return double(float(m)); }
 HDI_CONST int ygen_stride(int M) { return ((M + 1) + 31) & ~31; }
 // beta-CEM sample generation works on pairs of blocks of 16 positions and
 // tiles of 16 samples: generators (gen, genm) and the device normals (beta_z)
