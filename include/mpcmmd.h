@@ -503,6 +503,87 @@ typedef struct mpcmmd_validate_risk_args {
 } mpcmmd_validate_risk_args;
 int mpcmmd_validate_risk(const mpcmmd_validate_risk_args* args);
 
+/* Monte-Carlo risk statistics of CARLA plans on the GPU: the statistics of
+ * mpcmmd_validate_risk on the rollouts of mpcmmd_validate_carla.  ABI version
+ * unchanged; detect the entry point by its symbol.
+ *
+ * The rollouts are mpcmmd_validate_carla's, unchanged: the plan controls, the
+ * noisy initial rows, the noise model, the Philox streams 32..39 with the same
+ * element indices, the recorded point at h (the state before step h) and the
+ * closest-point Frenet transform.  The same (inputs, keys, seed, draws,
+ * init_eps) roll the same points in both calls, and one pass over them forms
+ * the counts and the costs.
+ *
+ * Per tick k and rollout r three fp32 channels over the H recorded points
+ * (carla/optimizer/costs.py:48-68, 117-211), (s, d) the point's Frenet
+ * coordinates:
+ *   obs[r]     = max over (o, h) of max(0, f), f = f_bar(s, d, x_obs[o][h],
+ *                y_obs[o][h]) with a^2, b^2: the value whose sign the counts of
+ *                mpcmmd_validate_carla test
+ *   lane_lb[r] = max over h of max(0, -d + y_lb)
+ *   lane_ub[r] = max over h of max(0,  d - y_ub)
+ * One term t contributes t if t > 0, +0 if t <= 0 and NaN if t is NaN; a row's
+ * cost is NaN if any of its terms is (jnp.maximum and jnp.max propagate NaN),
+ * stored as the one quiet NaN 0x7fc00000.  Hence !(cost <= 0) <=> some term
+ * !(t <= 0), and count_pos[k][0] == count_rows[k] exactly.
+ *
+ * The statistics are mpcmmd_validate_risk's, definition for definition
+ * (count_pos, var, cvar, mean, max [num_cfg][3], mmd [num_cfg][3][num_sigma];
+ * the same kernels on the device cost buffer, mpcmmd_quantile_position's
+ * ranks).  costs [num_cfg][3][R] and the counts of mpcmmd_validate_carla
+ * (count, count_lane, count_rows [num_cfg], count_oh [num_cfg][O][H]) are
+ * optional outputs: NULL is not copied.  elapsed_ms [3], or NULL: HIP-event
+ * times of the rollouts with costs and counts, the statistics and the MMD.
+ * Nothing accumulates through floating-point atomics (the row maxima are
+ * integer maxima of ordered keys): a value depends on (k, r) only, a call
+ * repeated returns the same bits, and a tick returns in a batch the bits it
+ * returns alone.
+ *
+ * Out of scope: the desired-lane term (compute_lane_des_*), a single Frobenius
+ * norm over the whole sample set and not a per-rollout cost.
+ *
+ * Limits: those of mpcmmd_validate_carla, and num_rollouts <= 2^20, 0 <= alpha
+ * <= 1, 0 <= num_sigma <= 8, every sigma finite and > 0.  Anything else, a
+ * NULL required argument or a static / dynamic variant (mpcmmd_validate_risk's)
+ * is MPCMMD_E_INVALID before any HIP call; num_cfg == 0 returns MPCMMD_OK
+ * without touching a device.  A shape whose workgroup does not fit the
+ * device's LDS is MPCMMD_E_UNSUPPORTED (never on an MI355X: the largest shape
+ * needs 768 B more than mpcmmd_validate_carla's, under 131 KiB).  Synchronous,
+ * needs no handle, allocates its own device buffers. */
+typedef struct mpcmmd_validate_carla_risk_args {
+  int32_t num_cfg, num_obs, num_prime, num_rollouts, num_path;
+  int32_t noise;            /* MPCMMD_NOISE_* */
+  int32_t variant;          /* MPCMMD_VARIANT_CARLA_* (y_lb, y_ub) */
+  float noise_level, acc_const_noise, steer_const_noise;
+  uint32_t seed;
+  int32_t device;
+  const float* init_state;  /* [num_cfg][6] init_state_global */
+  const float* v;           /* [num_cfg][100] v_best */
+  const float* steer;       /* [num_cfg][100] steering_best */
+  const float* x_obs;       /* [num_cfg][num_obs][100] Frenet tracks */
+  const float* y_obs;
+  const float* path;        /* [num_cfg][6][num_path] */
+  const float* draws;       /* [num_cfg][3][R][H] or NULL */
+  const float* init_eps;    /* [num_cfg][R][4] or NULL */
+  const uint32_t* keys;     /* [num_cfg] */
+  float alpha;              /* quantile level (the optimizer's alpha_quant = 0.98) */
+  int32_t num_sigma;
+  const float* sigma;       /* [num_cfg][num_sigma] */
+  int32_t* count_pos;       /* [num_cfg][3] out */
+  float* var;               /* [num_cfg][3] out */
+  float* cvar;              /* [num_cfg][3] out */
+  float* mean;              /* [num_cfg][3] out */
+  float* max;               /* [num_cfg][3] out */
+  float* mmd;               /* [num_cfg][3][num_sigma] out */
+  float* costs;             /* [num_cfg][3][R] out, or NULL */
+  int32_t* count;           /* [num_cfg] out, or NULL */
+  int32_t* count_lane;      /* [num_cfg] out, or NULL */
+  int32_t* count_rows;      /* [num_cfg] out, or NULL */
+  int32_t* count_oh;        /* [num_cfg][num_obs][num_prime] out, or NULL */
+  float* elapsed_ms;        /* [3] out, or NULL */
+} mpcmmd_validate_carla_risk_args;
+int mpcmmd_validate_carla_risk(const mpcmmd_validate_carla_risk_args* args);
+
 /* The linear quantile's position among n >= 1 ascending samples, 0 <= alpha <=
  * 1 (else MPCMMD_E_INVALID): indices lo, hi and fp32 weights w_lo, w_hi of
  * quantile = v[lo] w_lo + v[hi] w_hi.  Host only, no GPU needed. */

@@ -14,12 +14,21 @@ bounds).  Per cost one ``validate_<cost>.npz`` is written with ``count``
 ``count_lane``, ``tick`` and ``num_rollouts``; and one line is printed with the
 share of ticks with ``count_rows > 0`` and the mean ``count_rows / R``.
 
+With ``--risk`` the one call per cost is ``mpcmmd_validate_carla_risk``
+(``optimizer/validation.py: risk_plans``): the count arrays come from it, and
+the file also holds ``risk_count_pos``, ``risk_var``, ``risk_cvar``,
+``risk_mean``, ``risk_max`` [ticks, 3] (channels obs, lane_lb, lane_ub: the
+plan's own cost terms over the R rollouts, at quantile ``--risk-alpha``),
+``risk_mmd`` [ticks, 3, S] at the bandwidths ``--risk-sigma``, ``risk_sigma``
+and ``risk_alpha``; one more line per cost gives the mean obstacle CVaR and
+SAA.  Without ``--risk`` the file and the line are what they were.
+
     cd mpc-mmd_amd/carla
     python -m validate_replay --synthetic 200 --costs cvar det --ticks 40 120 --out stats
 
 The solver, the validator and the per-tick inputs are parameters of
-``validate_replay`` (``solve=``, ``validate=``, ``inputs=``), so the accounting
-is testable without a GPU.
+``validate_replay`` (``solve=``, ``validate=``, ``risk_fn=``, ``inputs=``), so the
+accounting is testable without a GPU.
 """
 from __future__ import annotations
 
@@ -68,6 +77,15 @@ def _validate(prob, plans, num_rollouts, seed):
     return validate_plans(prob, plans, num_rollouts=num_rollouts, seed=seed)
 
 
+def _risk(prob, plans, num_rollouts, seed, alpha, sigma):
+    pkg = type(prob).__module__.rpartition(".")[0]
+    risk_plans = importlib.import_module(pkg + ".validation").risk_plans
+    return risk_plans(prob, plans, num_rollouts=num_rollouts, alpha=alpha, sigma=sigma, seed=seed)
+
+
+RISK_KEYS = ("count_pos", "var", "cvar", "mean", "max", "mmd")
+
+
 def solve_ticks(prob, rec, cost, ticks, v_des=V_DES, solve=None, inputs=None):
     """The plans of ``ticks`` (in order) under ``cost``: per tick a dict with
     init, xo, yo, path, v_best, steering, mean_param, tick, key (= tick)."""
@@ -84,22 +102,39 @@ def solve_ticks(prob, rec, cost, ticks, v_des=V_DES, solve=None, inputs=None):
 
 
 def validate_replay(rec, prob, costs=("mmd", "cvar", "det"), ticks=None, num_rollouts=1000, out_dir=None, seed=0,
-                    v_des=V_DES, solve=None, validate=None, inputs=None, log=print):
+                    v_des=V_DES, solve=None, validate=None, inputs=None, log=print, risk=False, risk_sigma=(),
+                    risk_alpha=0.98, risk_fn=None):
     """See the module docstring.  ticks: iterable of tick indices (default:
-    every tick of the recording).  Returns {cost: the npz fields}."""
+    every tick of the recording).  risk: one ``risk_fn(prob, plans,
+    num_rollouts, seed, alpha, sigma)`` call per cost (default: ``risk_plans``)
+    in place of ``validate``; it returns the counts too.  Returns {cost: the
+    npz fields}."""
     ticks = list(range(rec["ego"].shape[0])) if ticks is None else [int(k) for k in ticks]
     validate = validate or _validate
+    risk_fn = risk_fn or _risk
+    sigma = np.asarray(risk_sigma, np.float32).reshape(-1)
     R = int(num_rollouts)
     results = {}
     for cost in costs:
         if cost not in COSTS:
             raise ValueError(f"cost must be one of {sorted(COSTS)}")
         plans = solve_ticks(prob, rec, cost, ticks, v_des, solve, inputs)
-        res = validate(prob, plans, R, seed) if plans else {}
+        if risk:
+            res = risk_fn(prob, plans, R, seed, float(risk_alpha), sigma) if plans else {}
+        else:
+            res = validate(prob, plans, R, seed) if plans else {}
         out = {k: np.asarray(res.get(k, np.zeros(0, np.int32)), np.int32).reshape(len(ticks))
                for k in ("count", "count_rows", "count_lane")}
         out["tick"] = np.asarray(ticks, np.int32)
         out["num_rollouts"] = np.int32(R)
+        if risk:
+            n = len(ticks)
+            for k in RISK_KEYS:
+                shape = (n, 3, sigma.size) if k == "mmd" else (n, 3)
+                dt = np.int32 if k == "count_pos" else np.float32
+                out["risk_" + k] = np.asarray(res.get(k, np.zeros(shape, dt)), dt).reshape(shape)
+            out["risk_sigma"] = sigma
+            out["risk_alpha"] = np.float32(risk_alpha)
         if out_dir is not None:
             os.makedirs(out_dir, exist_ok=True)
             np.savez(os.path.join(out_dir, f"validate_{cost}.npz"), **out)
@@ -107,6 +142,11 @@ def validate_replay(rec, prob, costs=("mmd", "cvar", "det"), ticks=None, num_rol
         share = float((out["count_rows"] > 0).mean()) if n else 0.0
         prob_mean = float((out["count_rows"] / R).mean()) if n else 0.0
         log(f"{cost}: {n} ticks, share with count_rows > 0 = {share:.4f}, mean count_rows / R = {prob_mean:.6f}")
+        if risk:
+            cvar_obs = float(out["risk_cvar"][:, 0].mean()) if n else 0.0
+            saa_obs = float((out["risk_count_pos"][:, 0] / R).mean()) if n else 0.0
+            log(f"{cost}: risk over {R} rollouts, mean obstacle CVaR({float(risk_alpha):g}) = {cvar_obs:.6f}, "
+                f"mean obstacle SAA = {saa_obs:.6f}")
         results[cost] = out
     return results
 
@@ -130,6 +170,10 @@ def main(argv=None):
     ap.add_argument("--num-batch", type=int, default=100)
     ap.add_argument("--maxiter-cem", type=int, default=20)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--risk", action="store_true",
+                    help="also the risk statistics of the plans' cost terms (mpcmmd_validate_carla_risk)")
+    ap.add_argument("--risk-sigma", type=float, nargs="+", default=[], metavar="S", help="MMD bandwidths")
+    ap.add_argument("--risk-alpha", type=float, default=0.98, help="quantile level of VaR / CVaR")
     a = ap.parse_args(argv)
     if (a.replay is None) == (a.synthetic is None):
         ap.error("give a replay file or --synthetic TICKS")
@@ -142,7 +186,8 @@ def main(argv=None):
                    a.acc_const_noise, a.steer_const_noise, num_batch=a.num_batch, maxiter_cem=a.maxiter_cem,
                    seed=a.seed)
     ticks = None if a.ticks is None else range(a.ticks[0], a.ticks[1])
-    validate_replay(rec, prob, a.costs, ticks, a.num_rollouts, a.out, a.seed)
+    validate_replay(rec, prob, a.costs, ticks, a.num_rollouts, a.out, a.seed, risk=a.risk,
+                    risk_sigma=a.risk_sigma, risk_alpha=a.risk_alpha)
     prob.handle.close()
 
 

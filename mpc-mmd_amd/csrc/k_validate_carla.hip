@@ -21,6 +21,12 @@
 //   epilogue the workgroup's counts are added to the tick's global integer
 //            counters (order-independent); k_validate_carla_max takes the maxima
 //
+// The cost variant (k_validate_carla_costs, mpcmmd_validate_carla_risk) is the
+// same body with kCosts set: phase B also keeps, per row, the maximum of each
+// of the three cost terms (obs, lane_lb, lane_ub) as an ordered 32-bit key in
+// an LDS table [3][64] (integer atomicMax: order-independent), and the epilogue
+// stores costs[k][c][r0 + row].  The count kernels compile none of it.
+//
 // The table's row stride is 65 words: phase A writes it with h fastest across
 // lanes (coalesced reads of the [R][H] draws), the chain reads it with the row
 // fastest, phase B with h fastest again -- all conflict-free at an odd stride.
@@ -43,9 +49,17 @@ constexpr int kVcStride = kVcRows + 1;
 constexpr int kVcMaxObs = 32;
 
 // LDS words: path | obstacle tracks | acc, steer | table (controls, then points) | counters | row flags
-HDI size_t vc_lds_words(int O, int H, int P) {
+// | the cost variant's row maxima [3][kVcRows]
+HDI size_t vc_lds_words(int O, int H, int P, bool costs = false) {
   return size_t(8) * frenet_quarter(P) + size_t(3) * P + size_t(2) * O * H + size_t(2) * H +
-         size_t(2) * H * kVcStride + size_t(O) * H + size_t(2) * H + kVcRows;
+         size_t(2) * H * kVcStride + size_t(O) * H + size_t(2) * H + kVcRows + (costs ? 3 * kVcRows : 0);
+}
+
+// The value rule of a cost term max(0, t) as a key that orders as an unsigned integer: t > 0 -> its bits
+// (positive floats and +inf ascend), NaN -> the canonical quiet NaN (above +inf), else +0.  The maximum of
+// the keys is the bits of jnp.max(jnp.maximum(0, t)): NaN if any term is NaN.
+DEVI uint32_t vc_cost_key(float t) {
+  return t > 0.0f ? __float_as_uint(t) : (t != t ? 0x7fc00000u : 0u);
 }
 
 // standard normal e of stream (k0, k1, stream), rounded as oracle/rng.py philox_normals
@@ -67,8 +81,11 @@ DEVI float vc_beta(float u, uint32_t k0, uint32_t k1, uint32_t sa, uint32_t sb, 
 // kDraws: 0 = the draws are given, 1 = internal normals (gaussian), 2 = internal Beta variates.  Three
 // instantiations, because the fp64 samplers of the internal streams would set the register count (and with
 // it the waves per SIMD of the Frenet search, the dominant phase) of the kernel that reads given draws too.
-template <int kDraws, int kVcThreads>
-__global__ __launch_bounds__(kVcThreads) void k_validate_carla(ValidateCarlaParams v) {
+// kCosts: the body of the cost variant (the head comment); false compiles the count kernel as it was.  The
+// block is taken by value, as a kernel takes it: by reference the count kernels allocate their registers
+// differently (one SGPR spill fewer in the compiler's remarks), and they are to stay what they were.
+template <int kDraws, int kVcThreads, bool kCosts>
+DEVI void vc_body(const ValidateCarlaParams v) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int P = v.P, H = v.H, O = v.O, R = v.R, k = blockIdx.y, tid = threadIdx.x, Pq = frenet_quarter(P);
   const int r0 = blockIdx.x * kVcRows, rows = min(kVcRows, R - r0);
@@ -86,6 +103,7 @@ __global__ __launch_bounds__(kVcThreads) void k_validate_carla(ValidateCarlaPara
   int* clb = cnt + O * H;  // [H]
   int* cub = clb + H;
   int* flag = cub + H;  // [kVcRows]
+  uint32_t* cmax = reinterpret_cast<uint32_t*>(flag + kVcRows);  // [3][kVcRows] cost keys (kCosts only)
 
   const float* pa = v.path + size_t(k) * 6 * P;
   const float inf = __int_as_float(0x7f800000);
@@ -109,6 +127,8 @@ __global__ __launch_bounds__(kVcThreads) void k_validate_carla(ValidateCarlaPara
     clb[h] = cub[h] = 0;
   }
   if (tid < kVcRows) flag[tid] = 0;
+  if constexpr (kCosts)
+    if (tid < 3 * kVcRows) cmax[tid] = 0u;
   __syncthreads();
 
   // phase A: noisy controls (helper.inject_noise; rollout.hpp: noisy_from) and tan(steer_n)
@@ -179,17 +199,28 @@ __global__ __launch_bounds__(kVcThreads) void k_validate_carla(ValidateCarlaPara
       float s, d;
       frenet_point_quad(ta[h * kVcStride + rr], tt[h * kVcStride + rr], pxy, arc, Fxd, Fyd, P, Pq, s, d);
       bool any = false;
+      uint32_t ko = 0u;
       for (int o = q; o < O; o += 4) {
         const float f = f_bar_ab(s, d, xo[o * H + h], yo[o * H + h], v.obs_a2, v.obs_b2);
         if (!(f <= 0.0f)) {  // k_validate's convention: count_nonzero(max(0, f)), a NaN counts
           atomicAdd(&cnt[o * H + h], 1);
           any = true;
         }
+        if constexpr (kCosts) ko = max(ko, vc_cost_key(f));
       }
       if (any) flag[rr] = 1;
       if (q == 0) {
         if (-d + v.y_lb > 0.0f) atomicAdd(&clb[h], 1);
         if (d - v.y_ub > 0.0f) atomicAdd(&cub[h], 1);
+      }
+      if constexpr (kCosts) {  // the point's three keys into the row's maxima; a zero key changes nothing
+        ko = lane_reduce<Scope::Quad, LaneMaxU>(ko);
+        if (q == 0) {
+          const uint32_t kl = vc_cost_key(-d + v.y_lb), ku = vc_cost_key(d - v.y_ub);
+          if (ko) atomicMax(&cmax[rr], ko);
+          if (kl) atomicMax(&cmax[kVcRows + rr], kl);
+          if (ku) atomicMax(&cmax[2 * kVcRows + rr], ku);
+        }
       }
     }
   }
@@ -210,6 +241,19 @@ __global__ __launch_bounds__(kVcThreads) void k_validate_carla(ValidateCarlaPara
     const int n = __popcll(__ballot(f));
     if (tid == 0 && n) atomicAdd(&v.count_rows[k], n);
   }
+  if constexpr (kCosts)
+    if (tid < rows)  // coalesced per channel
+      for (int c = 0; c < 3; ++c)
+        v.costs[(size_t(k) * 3 + c) * R + r0 + tid] = __uint_as_float(cmax[c * kVcRows + tid]);
+}
+
+template <int kDraws, int kVcThreads>
+__global__ __launch_bounds__(kVcThreads) void k_validate_carla(ValidateCarlaParams v) {
+  vc_body<kDraws, kVcThreads, false>(v);
+}
+template <int kDraws, int kVcThreads>
+__global__ __launch_bounds__(kVcThreads) void k_validate_carla_costs(ValidateCarlaParams v) {
+  vc_body<kDraws, kVcThreads, true>(v);
 }
 
 // count = max_{o,h} count_oh, count_lane = max_h #lb + max_h #ub (S/validation.py:153-169)
@@ -240,14 +284,19 @@ bool validate_carla_shape_ok(int O, int H, int P) {
   return O >= 1 && O <= kVcMaxObs && H >= 2 && H <= kMaxH && P >= 4 && P <= kMaxPath;
 }
 
-size_t validate_carla_lds(int O, int H, int P) { return vc_lds_words(O, H, P) * 4; }
+size_t validate_carla_lds(int O, int H, int P, bool costs) { return vc_lds_words(O, H, P, costs) * 4; }
 
 bool launch_validate_carla(const ValidateCarlaParams& v, size_t lds_limit, hipStream_t s) {
-  const size_t lds = validate_carla_lds(v.O, v.H, v.P);
+  const bool costs = v.costs != nullptr;
+  const size_t lds = validate_carla_lds(v.O, v.H, v.P, costs);
   if (lds > lds_limit) return false;
   const int threads = v.draws ? kVcThreadsGiven : kVcThreadsDrawn;
   auto kern = v.draws ? k_validate_carla<0, kVcThreadsGiven>
                       : (v.noise == 0 ? k_validate_carla<1, kVcThreadsDrawn> : k_validate_carla<2, kVcThreadsDrawn>);
+  if (costs)
+    kern = v.draws ? k_validate_carla_costs<0, kVcThreadsGiven>
+                   : (v.noise == 0 ? k_validate_carla_costs<1, kVcThreadsDrawn>
+                                   : k_validate_carla_costs<2, kVcThreadsDrawn>);
   if (lds > 64 * 1024)  // above the default dynamic-LDS cap of a launch
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                               int(lds));

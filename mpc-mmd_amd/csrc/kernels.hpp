@@ -268,9 +268,12 @@ struct ValidateCarlaParams {
   int32_t* count_rows;    // [K]        (accumulator and result)
   int32_t* count;         // [K]
   int32_t* count_lane;    // [K]
+  float* costs;           // [K][3][R] per-rollout costs (obs, lane_lb, lane_ub), or null: the counts only.
+                          //           Non-null selects the cost kernels (mpcmmd_validate_carla_risk)
 };
 bool validate_carla_shape_ok(int O, int H, int P);
-size_t validate_carla_lds(int O, int H, int P);  // dynamic LDS bytes of a workgroup
+// dynamic LDS bytes of a workgroup (costs: the cost variant's, 768 B more)
+size_t validate_carla_lds(int O, int H, int P, bool costs = false);
 // false: the shape's LDS need exceeds lds_limit (nothing is launched)
 bool launch_validate_carla(const ValidateCarlaParams& v, size_t lds_limit, hipStream_t s);
 void launch_gamma_tab(const Params& p, int t, hipStream_t s);

@@ -131,6 +131,7 @@ DEVI void wave_sync() {
 //   LaneMax    fmaxf (NaN ignored unless every lane is NaN); old = v: rows a
 //              broadcast does not write keep their own value
 //   LaneMinU   unsigned minimum; old = ~0, the identity
+//   LaneMaxU   unsigned maximum; old = 0, the identity
 enum class Scope { Quad, Row16, Wave };
 struct LaneSum {
   template <int CTRL, int ROWS, class T>
@@ -143,6 +144,10 @@ struct LaneMax {
 struct LaneMinU {
   template <int CTRL, int ROWS>
   static DEVI uint32_t step(uint32_t v) { return min(v, dpp_old<CTRL, ROWS>(v, ~0u)); }
+};
+struct LaneMaxU {
+  template <int CTRL, int ROWS>
+  static DEVI uint32_t step(uint32_t v) { return max(v, dpp_old<CTRL, ROWS>(v, 0u)); }
 };
 template <Scope S, class Op, class T>
 DEVI T lane_reduce(T v) {

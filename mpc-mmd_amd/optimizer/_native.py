@@ -29,7 +29,7 @@ SYMBOLS = (
     "mpcmmd_max_configs", "mpcmmd_solve_batch", "mpcmmd_begin_batch", "mpcmmd_finish_batch",
     "mpcmmd_carla_begin", "mpcmmd_carla_solve", "mpcmmd_path_smoothing", "mpcmmd_path_parameters",
     "mpcmmd_global_to_frenet", "mpcmmd_set_graphs", "mpcmmd_handle_info", "mpcmmd_validate_carla",
-    "mpcmmd_validate_risk", "mpcmmd_quantile_position",
+    "mpcmmd_validate_risk", "mpcmmd_quantile_position", "mpcmmd_validate_carla_risk",
 )
 
 
@@ -103,6 +103,18 @@ class ValidateRiskArgs(C.Structure):
                 ("costs", C.POINTER(C.c_float)), ("elapsed_ms", C.POINTER(C.c_float))]
 
 
+class ValidateCarlaRiskArgs(C.Structure):
+    _fields_ = ValidateCarlaArgs._fields_[:21] + [
+        ("alpha", C.c_float), ("num_sigma", C.c_int32), ("sigma", C.POINTER(C.c_float)),
+        ("count_pos", C.POINTER(C.c_int32)), ("var", C.POINTER(C.c_float)), ("cvar", C.POINTER(C.c_float)),
+        ("mean", C.POINTER(C.c_float)), ("max", C.POINTER(C.c_float)), ("mmd", C.POINTER(C.c_float)),
+        ("costs", C.POINTER(C.c_float)), ("count", C.POINTER(C.c_int32)), ("count_lane", C.POINTER(C.c_int32)),
+        ("count_rows", C.POINTER(C.c_int32)), ("count_oh", C.POINTER(C.c_int32)),
+        ("elapsed_ms", C.POINTER(C.c_float))]
+
+
+assert ValidateCarlaRiskArgs._fields_[20][0] == "keys"   # the inputs of ValidateCarlaArgs, up to the keys
+
 RISK_CHANNELS = ("obs", "lane_lb", "lane_ub")
 
 
@@ -160,6 +172,8 @@ def lib():
     L.mpcmmd_validate.argtypes = [C.POINTER(ValidateArgs)]
     L.mpcmmd_validate_carla.argtypes = [C.POINTER(ValidateCarlaArgs)]
     L.mpcmmd_validate_risk.argtypes = [C.POINTER(ValidateRiskArgs)]
+    if hasattr(L, "mpcmmd_validate_carla_risk"):   # an older library lacks it: validate_carla_risk raises
+        L.mpcmmd_validate_carla_risk.argtypes = [C.POINTER(ValidateCarlaRiskArgs)]
     L.mpcmmd_quantile_position.argtypes = [C.c_int32, C.c_float, ip, ip, fp, fp]
     L.mpcmmd_obs_dynamic_traj.argtypes = [C.c_int32, fp, fp, fp, fp, fp, C.c_float, fp, fp]
     cargs = [vp, C.c_int32, C.c_int32, fp, fp, fp, fp, fp, C.c_float, C.POINTER(Path), C.POINTER(Draws)]
@@ -249,29 +263,9 @@ def validate_carla(init_state, v, steer, x_obs, y_obs, paths, keys, num_prime, n
     (internal Philox streams).  Returns a dict: count, count_lane, count_rows
     [K] int32, with ``count_oh`` also count_oh [K,O,H], with ``timing`` also
     elapsed_ms (HIP events around the device work)."""
-    f = lambda a, *shape: np.ascontiguousarray(np.asarray(a, np.float32).reshape(*shape))
-    K = int(np.asarray(keys).reshape(-1).shape[0])
     H, R = int(num_prime), int(num_rollouts)
-    if K == 0:
-        pa = np.zeros((0, 6, 4), np.float32)
-    elif isinstance(paths, np.ndarray):
-        pa = f(paths, K, 6, -1)
-    else:
-        if len(paths) != K:
-            raise ValueError("one path per tick")
-        if len({np.asarray(p[k]).size for p in paths for k in PATH_KEYS}) > 1:
-            raise ValueError("path arrays differ in length (one num_path per call)")
-        pa = f([[np.asarray(p[k], np.float32).reshape(-1) for k in PATH_KEYS] for p in paths], K, 6, -1)
-    P = pa.shape[2]
-    st, vv, ss = f(init_state, K, 6), f(v, K, 100), f(steer, K, 100)
-    if K:
-        xo, yo = f(x_obs, K, -1, 100), f(y_obs, K, -1, 100)
-    else:  # nothing to run: the library returns before it looks at the arrays
-        xo = yo = np.zeros((0, 1, 100), np.float32)
-    O = xo.shape[1]
-    ks = np.ascontiguousarray(np.asarray(keys, np.int64).reshape(K).astype(np.uint32))
-    dr = None if draws is None else f(draws, K, 3, R, H)
-    ie = None if init_eps is None else f(init_eps, K, R, 4)
+    K, O, P, (st, vv, ss, xo, yo, pa, dr, ie, ks) = _carla_plan_arrays(init_state, v, steer, x_obs, y_obs, paths,
+                                                                     keys, H, R, draws, init_eps)
     out = {k: np.zeros(K, np.int32) for k in ("count", "count_lane", "count_rows")}
     oh = np.zeros((K, O, H), np.int32) if count_oh else None
     ms = C.c_float(0.0)
@@ -286,6 +280,85 @@ def validate_carla(init_state, v, steer, x_obs, y_obs, paths, keys, num_prime, n
         out["count_oh"] = oh
     if timing:
         out["elapsed_ms"] = float(ms.value)
+    return out
+
+
+def _carla_plan_arrays(init_state, v, steer, x_obs, y_obs, paths, keys, H, R, draws, init_eps):
+    """The input arrays of validate_carla / validate_carla_risk: (K, O, P, arrays in the struct's order)."""
+    f = lambda a, *shape: np.ascontiguousarray(np.asarray(a, np.float32).reshape(*shape))
+    K = int(np.asarray(keys).reshape(-1).shape[0])
+    if K == 0:
+        pa = np.zeros((0, 6, 4), np.float32)
+    elif isinstance(paths, np.ndarray):
+        pa = f(paths, K, 6, -1)
+    else:
+        if len(paths) != K:
+            raise ValueError("one path per tick")
+        if len({np.asarray(p[k]).size for p in paths for k in PATH_KEYS}) > 1:
+            raise ValueError("path arrays differ in length (one num_path per call)")
+        pa = f([[np.asarray(p[k], np.float32).reshape(-1) for k in PATH_KEYS] for p in paths], K, 6, -1)
+    st, vv, ss = f(init_state, K, 6), f(v, K, 100), f(steer, K, 100)
+    if K:
+        xo, yo = f(x_obs, K, -1, 100), f(y_obs, K, -1, 100)
+    else:  # nothing to run: the library returns before it looks at the arrays
+        xo = yo = np.zeros((0, 1, 100), np.float32)
+    ks = np.ascontiguousarray(np.asarray(keys, np.int64).reshape(K).astype(np.uint32))
+    dr = None if draws is None else f(draws, K, 3, R, H)
+    ie = None if init_eps is None else f(init_eps, K, R, 4)
+    return K, xo.shape[1], pa.shape[2], (st, vv, ss, xo, yo, pa, dr, ie, ks)
+
+
+def validate_carla_risk(init_state, v, steer, x_obs, y_obs, paths, keys, num_prime, noise, noise_level,
+                        acc_const_noise=0.0, steer_const_noise=0.0, num_rollouts=1000, variant="carla_town05",
+                        draws=None, init_eps=None, seed=0, device=0, alpha=0.98, sigma=None, return_costs=False,
+                        counts=False, timing=False):
+    """mpcmmd_validate_carla_risk over K simulator ticks (include/mpcmmd.h): the
+    inputs of ``validate_carla``, whose rollouts it repeats point for point;
+    ``sigma`` [K,S] (or [S], shared) the MMD bandwidths.  Returns the dict of
+    ``validate_risk``: count_pos (int32), var, cvar, mean, max, saa [K,3]
+    (channels RISK_CHANNELS), mmd [K,3,S], cvar_lane [K], mmd_lane [K,S]; with
+    ``return_costs`` costs [K,3,R]; with ``counts`` also count, count_lane,
+    count_rows [K] and count_oh [K,O,H] of ``validate_carla``; with ``timing``
+    elapsed_ms [3] (rollouts with costs, statistics, MMD)."""
+    L = lib()
+    if not hasattr(L, "mpcmmd_validate_carla_risk"):
+        raise NativeError(f"{LIB_PATH} has no mpcmmd_validate_carla_risk (built before the entry point existed): "
+                          "rebuild it")
+    H, R = int(num_prime), int(num_rollouts)
+    K, O, P, arr = _carla_plan_arrays(init_state, v, steer, x_obs, y_obs, paths, keys, H, R, draws, init_eps)
+    if sigma is None:
+        sg = np.zeros((K, 0), np.float32)
+    else:
+        sg = np.asarray(sigma, np.float32)
+        sg = np.ascontiguousarray(np.broadcast_to(sg, (K, sg.shape[-1])) if sg.ndim == 1 else sg.reshape(K, -1))
+    S = sg.shape[1]
+    out = dict(count_pos=np.zeros((K, 3), np.int32))
+    out.update({k: np.zeros((K, 3), np.float32) for k in ("var", "cvar", "mean", "max")})
+    out["mmd"] = np.zeros((K, 3, S), np.float32)
+    costs = np.zeros((K, 3, R), np.float32) if return_costs else None
+    cnt = {k: np.zeros(K, np.int32) for k in ("count", "count_lane", "count_rows")} if counts else {}
+    if counts:
+        cnt["count_oh"] = np.zeros((K, O, H), np.int32)
+    ms = (C.c_float * 3)()
+    ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    args = ValidateCarlaRiskArgs(K, O, H, R, P, NOISE[noise], VARIANT[variant], float(noise_level),
+                                 float(acc_const_noise), float(steer_const_noise), int(seed) & 0xFFFFFFFF,
+                                 int(device), *[_fptr(a) for a in arr[:8]],
+                                 arr[8].ctypes.data_as(C.POINTER(C.c_uint32)), float(alpha), S,
+                                 _fptr(sg) if S else None, ip(out["count_pos"]), _fptr(out["var"]),
+                                 _fptr(out["cvar"]), _fptr(out["mean"]), _fptr(out["max"]),
+                                 _fptr(out["mmd"]) if S else None, _fptr(costs), ip(cnt.get("count")),
+                                 ip(cnt.get("count_lane")), ip(cnt.get("count_rows")), ip(cnt.get("count_oh")),
+                                 C.cast(ms, C.POINTER(C.c_float)) if timing else None)
+    check(L.mpcmmd_validate_carla_risk(C.byref(args)))
+    out["saa"] = (out["count_pos"].astype(np.float32) / np.float32(R)).astype(np.float32)
+    out["cvar_lane"] = (out["cvar"][:, 1] + out["cvar"][:, 2]).astype(np.float32)
+    out["mmd_lane"] = (out["mmd"][:, 1] + out["mmd"][:, 2]).astype(np.float32)
+    out.update(cnt)
+    if return_costs:
+        out["costs"] = costs
+    if timing:
+        out["elapsed_ms"] = np.array(list(ms), np.float32)
     return out
 
 
