@@ -1,4 +1,5 @@
-// The beta-CEM sampler's device code (k_bsample.hip, k_bcem_small.hip).
+// The beta-CEM sampler's device code (k_bsample_walk.hip, k_bsample.hip,
+// k_bcem_small.hip).
 //
 // k_bsample: the new samples of beta-CEM iteration tb >= 1 (rows 11..99,
 // mean + L z, compute_beta.py:51-68) with the structured factor of
@@ -11,13 +12,16 @@
 // sum_{j < 16c} w_j z_j, U_c / W_c [16 x 11] the generators u_j / w_j and
 // T_c [16 x 16] = strict_lower(U_c W_c^T) + diag(L_jj) (itself one MFMA
 // product, masked).  A wave owns kTilesPerWave tiles of 16 samples and walks
-// the blocks in order; S lives in accumulator registers and is, by the
-// 16x16x4 f64 layouts, directly the B operand of U_c S_c.  All in fp64 (the
-// oracle's dense fp64 Cholesky agrees to ~1e-15 before the fp32 rounding).
+// the blocks in order; S stays in the registers its MFMAs accumulate in and
+// is, by the 16x16x4 f64 layouts, directly the B operand of U_c S_c.  All in
+// fp64 (the oracle's dense fp64 Cholesky agrees to ~1e-15 before the fp32
+// rounding).
 //
 // f64 16x16x4 layouts (lane l, r = l & 15, h = l >> 4):
 //   A: A[r][h]   B: B[h][r]   C/D register i: C[h + 4 i][r]
 #pragma once
+#include <type_traits>
+
 #include "betacem_common.hpp"
 
 namespace mpcmmd {
@@ -280,22 +284,44 @@ DEVI void fold_chunk(d4& Sp, d4& S) {
 }
 
 // Blocks [c0, c1) (c1 > c0) in order on the calling wave, c1 - 1 the last
-// block a caller walks before its sums are dropped.  Blocks in pairs,
-// operands and outputs ping-ponged: the next block's loads are in flight and
-// its MFMAs issued while the previous block's samples are converted and
-// stored (sched barriers keep that order).  The pairs stop short of block
-// c1 - 1, which may hold positions past the sigma coordinate M: it is peeled,
-// alone or after its unpaired predecessor, with block_u's mask.  pair_end(c)
-// follows the second block of the pair that starts at c (the walker's chunk
-// folds: chunk lengths are even, so no chunk ends inside the peeled blocks
-// but with the walk).
-template <int TPW, class Load, class Store, class PairEnd>
+// block a caller walks before its sums are dropped.  Blocks in pairs with the
+// operands ping-ponged, so the next block's loads are in flight during a
+// block's MFMAs (sched barriers keep that order).
+// HOLD: a finished block's samples are converted and stored after the next
+// block's MFMAs are issued (outputs ping-ponged too), so the wave does not
+// wait for its last MFMAs -- k_bsample_chunks, whose one tile per wave makes
+// that wait long and the second Y cheap.  The one-wave walker stores a block
+// right after its MFMAs, from one Y: with six tiles the wait is short, a
+// wave's VALU work does not run in the shadow of its own fp64 MFMAs on gfx950
+// anyway (tools/mfma_overlap.hip), and the second Y's 48 registers are the
+// difference between a loop with AccVGPR spill moves and one without.
+// The pairs stop short of block c1 - 1, which may hold positions past the
+// sigma coordinate M: it is peeled, alone or after its unpaired predecessor,
+// with block_u's mask.  pair_end(c) follows the second block of the pair that
+// starts at c (the walker's chunk folds: chunk lengths are even, so no chunk
+// ends inside the peeled blocks but with the walk).
+// store(Y, p0, tag) gets a compile-time tag.  InteriorBlock for the blocks
+// c < c1 - 1 <= sample_blocks(M) - 1, which lie wholly before the sigma
+// coordinate: 16 (sample_blocks(M) - 1) <= M gives p0 + 15 = 16 c + 15 <=
+// 16 (sample_blocks(M) - 1) - 1 < M.  EdgeBlock for block c1 - 1, which may
+// hold M or positions past it.
+using InteriorBlock = std::true_type;
+using EdgeBlock = std::false_type;
+template <int TPW, bool HOLD, class Load, class Store, class PairEnd>
 DEVI void walk_blocks(int c0, int c1, int M, int r, int h, d4* S, const d4* Sp, Load&& load, Store&& store,
                       PairEnd&& pair_end) {
-  d4 Ya[TPW], Yb[TPW];
+  d4 Y[HOLD ? 2 : 1][TPW];
+  d4 *const Ya = Y[0], *const Yb = Y[HOLD ? 1 : 0];
   SampleBlock<TPW> qa, qb;
   const int last = c1 - 1;
   const bool valid = (last << 4) + r <= M;
+  // block q0 / 16 < last is finished in Yc: its store, or with HOLD that of the block before it (in Yp)
+  auto finished = [&](const d4* Yc, int q0, const d4* Yp, bool prev) {
+    if constexpr (!HOLD)
+      store(Yc, q0, InteriorBlock{});
+    else if (prev)
+      store(Yp, q0 - 16, InteriorBlock{});
+  };
   load(qa, c0 << 4);
   int c = c0;
   for (; c + 2 <= last; c += 2) {
@@ -304,14 +330,14 @@ DEVI void walk_blocks(int c0, int c1, int M, int r, int h, d4* S, const d4* Sp, 
     __builtin_amdgcn_sched_barrier(0);
     block_mfma(qa, S, Sp, Ya, r, h);
     __builtin_amdgcn_sched_barrier(0);
-    if (c > c0) store(Yb, p0 - 16);
+    finished(Ya, p0, Yb, c > c0);
     __builtin_amdgcn_sched_barrier(0);
     load(qa, p0 + 32);  // <= last
     __builtin_amdgcn_sched_barrier(0);
     block_mfma(qb, S, Sp, Yb, r, h);
     pair_end(c);
     __builtin_amdgcn_sched_barrier(0);
-    store(Ya, p0);
+    finished(Yb, p0 + 16, Ya, true);
     __builtin_amdgcn_sched_barrier(0);
   }
   const int p0 = c << 4;
@@ -320,17 +346,18 @@ DEVI void walk_blocks(int c0, int c1, int M, int r, int h, d4* S, const d4* Sp, 
     __builtin_amdgcn_sched_barrier(0);
     block_mfma(qa, S, Sp, Ya, r, h);
     __builtin_amdgcn_sched_barrier(0);
-    if (c > c0) store(Yb, p0 - 16);
+    finished(Ya, p0, Yb, c > c0);
     __builtin_amdgcn_sched_barrier(0);
     block_mfma<true>(qb, S, Sp, Yb, r, h, valid);
     __builtin_amdgcn_sched_barrier(0);
-    store(Ya, p0);
-    store(Yb, p0 + 16);
-  } else {
+    if constexpr (HOLD) store(Ya, p0, InteriorBlock{});
+    store(Yb, p0 + 16, EdgeBlock{});
+  } else {  // block c1 - 1 alone (a copy of qa into a shared tail costs the walker's loop six spilled registers)
     block_mfma<true>(qa, S, Sp, Ya, r, h, valid);
     __builtin_amdgcn_sched_barrier(0);
-    if (c > c0) store(Yb, p0 - 16);
-    store(Ya, p0);
+    if constexpr (HOLD)
+      if (c > c0) store(Yb, p0 - 16, InteriorBlock{});
+    store(Ya, p0, EdgeBlock{});
   }
 }
 

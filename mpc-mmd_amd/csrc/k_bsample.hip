@@ -1,5 +1,6 @@
-// k_bsample, k_bsample_chunks, k_bsel0, k_bselect: a beta-iteration's new
-// samples and their top-n selection (betacem_common.hpp has the pipeline).
+// k_bsample_chunks, k_bsel0, k_bselect: a beta-iteration's new samples in
+// small launches and the top-n selection (betacem_common.hpp has the
+// pipeline; k_bsample_walk.hip has the one-wave sampler of large launches).
 #include <algorithm>
 
 #include "betacem_sample.hpp"
@@ -21,49 +22,6 @@ __global__ __launch_bounds__(256) void k_bsel0(Params p) {
     else
       p.bsig[size_t(b) * kBetaSamples + e - kBetaSamples * n] = p.sig0[e - kBetaSamples * n];
   }
-}
-
-template <int TPW>
-__global__ __launch_bounds__(64 * sample_waves<TPW>()) void k_bsample(Params p, int tb) {
-  const int b = p.b0 + blockIdx.x, M = p.M, Pp = pos_pad(M);
-  const int lane = tidx() & 63, w = tidx() >> 6;
-  const int r = lane & 15, h = lane >> 4;
-  const int s0 = w * TPW * 16;
-  MPCMMD_STAMP(p, 0);
-  const double* G = p.gen + size_t(b) * Pp * kGenStride;
-  const double* gm = p.genm + size_t(b) * Pp;
-  const float* z = p.beta_z + size_t(tb - 1) * Pp * kBzCols;
-  const int ys = ygen_stride(M);
-  float* plane = p.ygen + size_t(b) * kBzCols * ys;
-  const float* E = gen_elites(p, tb, b);
-  d4 S[TPW], Sp[TPW];
-#pragma unroll
-  for (int t = 0; t < TPW; ++t) {
-    S[t] = Sp[t] = d4{0.0, 0.0, 0.0, 0.0};
-    Sp[t][2] = h == 3 ? 1.0 : 0.0;  // row 11 of S_pre: the mean's coefficient
-  }
-  const int cl = sample_chunk(Pp >> 4);
-  const __amdgpu_buffer_rsrc_t yr = ygen_rsrc(plane, ys);
-  const int vl = (2 * h * ys + r) * 4, v43 = h == 0 ? vl : kDropOffset;
-  auto store = [&](const d4* Yv, int q0) {
-    if (TPW == kSampleTiles && q0 + 15 < M)  // block-uniform
-      block_store_rows(Yv, yr, q0, ys, vl, v43);
-    else
-      block_store<TPW>(Yv, plane, q0, M, ys, s0, r, h);
-  };
-  const SampleRsrc srs = sample_rsrc(G, E, gm, z, M, r, h);
-  auto load = [&](SampleBlock<TPW>& q, int q0) {
-    if constexpr (TPW == kSampleTiles)
-      load_block_buf(q, srs, q0);
-    else
-      load_block(q, G, E, gen_mean_row(p, b), gm, z, M, q0, s0, r, h);
-  };
-  walk_blocks<TPW>(0, sample_blocks(M), M, r, h, S, Sp, load, store, [&](int c) {
-    if ((c + 2) % cl == 0)
-#pragma unroll
-      for (int t = 0; t < TPW; ++t) fold_chunk(Sp[t], S[t]);
-  });
-  MPCMMD_STAMP(p, 1);
 }
 
 // k_bsample_chunks: the samples of k_bsample for small batches, workgroup =
@@ -118,10 +76,10 @@ __global__ __launch_bounds__(64 * kChunkWavesMax) void k_bsample_chunks(Params p
   const float* E = gen_elites(p, tb, b);
   const double* mrow = gen_mean_row(p, b);
   // the last chunk ends with the last block that holds a position (the walker's bound)
-  walk_blocks<1>(
+  walk_blocks<1, true>(
       c0, min(sample_blocks(M), c1), M, r, h, S, Sp,
       [&](SampleBlock<1>& q, int q0) { load_block(q, G, E, mrow, gm, z, M, q0, s0, r, h); },
-      [&](const d4* Yv, int q0) { block_store<1>(Yv, plane, q0, M, ys, s0, r, h); }, [](int) {});
+      [&](const d4* Yv, int q0, auto) { block_store<1>(Yv, plane, q0, M, ys, s0, r, h); }, [](int) {});
   MPCMMD_STAMP(p, 1);
 }
 
@@ -137,15 +95,10 @@ __global__ __launch_bounds__(64) void k_bselect(Params p, int tb) {
 
 }  // namespace
 
-void launch_bsample(const Params& p, int tb, hipStream_t s) {
-  // one wave per candidate when the launch alone holds >= ~half a wave per
-  // SIMD; smaller batches one wave per (candidate, tile, chunk)
-  if (p.nb >= 384) {
-    hipLaunchKernelGGL((k_bsample<6>), dim3(p.nb), dim3(64 * sample_waves<6>()), 0, s, p, tb);
-  } else {
-    const int nblk = pos_pad(p.M) >> 4, cl = sample_chunk(nblk);
-    hipLaunchKernelGGL(k_bsample_chunks, dim3(p.nb, kSampleTiles), dim3(64 * ((nblk + cl - 1) / cl)), 0, s, p, tb);
-  }
+// one wave per (candidate, tile, chunk): launch_bsample's small batches
+void launch_bsample_chunks(const Params& p, int tb, hipStream_t s) {
+  const int nblk = pos_pad(p.M) >> 4, cl = sample_chunk(nblk);
+  hipLaunchKernelGGL(k_bsample_chunks, dim3(p.nb, kSampleTiles), dim3(64 * ((nblk + cl - 1) / cl)), 0, s, p, tb);
 }
 
 void launch_bsel0(const Params& p, hipStream_t s) {

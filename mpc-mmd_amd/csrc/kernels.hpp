@@ -283,7 +283,8 @@ void launch_mother(const Params& p, int t, hipStream_t s);
 void launch_dist_pad(const Params& p, int cap, hipStream_t s);  // once per handle (cap candidates), before the first launch_bdist
 void launch_bdist(const Params& p, hipStream_t s);
 void launch_bmoment(const Params& p, hipStream_t s);  // after launch_bdist: series records of the distance rows
-void launch_bsample(const Params& p, int tb, hipStream_t s);
+void launch_bsample(const Params& p, int tb, hipStream_t s);         // k_bsample_walk.hip; small launches:
+void launch_bsample_chunks(const Params& p, int tb, hipStream_t s);  // k_bsample.hip
 void launch_bselect(const Params& p, int tb, hipStream_t s);
 void launch_bsel0(const Params& p, hipStream_t s);  // first beta-iteration: the handle's table into bsel / bsig
 void launch_bkernel(const Params& p, int tb, hipStream_t s);  // K_mixed row sums by the series, K_red
