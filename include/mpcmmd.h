@@ -57,7 +57,11 @@ extern "C" {
 /* The CARLA optimizer (carla/optimizer/cem.py, CEM(num_reduced_sqrt,
  * num_mother, num_obs, noise_level, num_prime, noise, town, ...)): town
  * "Town05" / "Town10HD" select y_lb, y_ub, y_des (cem.py:161-166).  A CARLA
- * handle solves through mpcmmd_carla_begin / mpcmmd_carla_solve only. */
+ * handle solves through the mpcmmd_carla_* entry points only (a path is
+ * needed): mpcmmd_carla_begin / mpcmmd_carla_solve for one tick, and on a
+ * handle of mpcmmd_create_batch with max_configs > 1 also
+ * mpcmmd_carla_begin_batch / mpcmmd_carla_solve_batch for up to max_configs
+ * independent ticks per launch. */
 #define MPCMMD_VARIANT_CARLA_TOWN05 2
 #define MPCMMD_VARIANT_CARLA_TOWN10HD 3
 
@@ -159,6 +163,9 @@ int32_t mpcmmd_max_configs(mpcmmd_handle* h);
  *                  handle of 512 and one of 1024 candidates, or with another
  *                  max_configs.  Pin it with the environment variable
  *                  MPCMMD_GENWAVE=0/1 (read at create) to compare batch sizes.
+ *                  CARLA batches alike: a tick's mmd_opt bits on a batch handle
+ *                  of more than 512 candidates (say 6 x 100) differ from its
+ *                  bits on the default 100-candidate handle unless pinned.
  *   "select_prep"  1: for cvar / saa / mmd_random the risk launch (stage 2) also
  *                  sorts the residuals and forms compute_cost's norms, so stage 3
  *                  needs stage 2 of the same iteration (MPCMMD_SELECT_PREP=0: in
@@ -239,6 +246,28 @@ int mpcmmd_carla_begin(mpcmmd_handle* h, int32_t cost_kind, int32_t idx_mpc, con
 int mpcmmd_carla_solve(mpcmmd_handle* h, int32_t cost_kind, int32_t idx_mpc, const float init_state[6],
                        const float mean[8], const float cov[64], const float* x_obs, const float* y_obs, float v_des,
                        const mpcmmd_path* path, const mpcmmd_draws* draws, mpcmmd_result* out);
+/* Both work on a handle of any max_configs, as n_cfg = 1 of the batch below.
+ *
+ * n_cfg <= max_configs independent CARLA solves (ticks) in one batch.  Arrays carry a
+ * leading configuration axis as in mpcmmd_begin_batch; paths [n_cfg], every path with
+ * the same num_path.  One cost_kind (mmd_opt, cvar or det) per batch.  Configuration g
+ * uses the internal streams keyed by idx_mpc[g] (init_eps included), so its result is
+ * bit-identical to mpcmmd_carla_solve of that tick alone on a handle with the same
+ * "gen_wave" (mpcmmd_handle_info).  External draws: n_cfg == 1 only (use
+ * mpcmmd_carla_begin).  Then mpcmmd_iterate / mpcmmd_finish_batch, which fills steering,
+ * v_best and mean_param of every out[g].  Before any HIP call or upload:
+ * MPCMMD_E_INVALID for a handle that is no CARLA variant's, n_cfg outside
+ * 1..max_configs, a NULL array (inside a path too), num_path outside 4..2048 or not the
+ * same for every configuration; MPCMMD_E_UNSUPPORTED for det with num_obs > 32.  The ABI
+ * version is unchanged: callers detect the two entry points by their symbols. */
+int mpcmmd_carla_begin_batch(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc,
+                             const float* init_state, const float* mean, const float* cov,
+                             const float* x_obs, const float* y_obs, const float* v_des,
+                             const mpcmmd_path* paths);
+int mpcmmd_carla_solve_batch(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc,
+                             const float* init_state, const float* mean, const float* cov,
+                             const float* x_obs, const float* y_obs, const float* v_des,
+                             const mpcmmd_path* paths, mpcmmd_result* out);
 
 /* Helper.custom_path_smoothing(x_waypoints, y_waypoints, threshold)
  * (carla/optimizer/cem_helper.py:279-318, 391-410): 10 ADMM iterations of the

@@ -15,8 +15,11 @@ deterministic baseline with the obstacle-constrained projection of
 projection_det.py) are built, so every ``--costs`` of main_carla.py:188-194
 runs.  Extra keyword-only options:
 ``num_batch`` (reference: 100, cem.py:138), ``maxiter_cem``, ``device``,
-``seed``; per call ``draws`` (explicit standard normals incl. ``init_eps``,
-include/mpcmmd.h) and ``trace``.
+``seed``, ``max_configs`` (ticks the one handle solves per launch, default 1);
+per call ``draws`` (explicit standard normals incl. ``init_eps``,
+include/mpcmmd.h) and ``trace``.  ``compute_cem_batch`` solves up to
+``max_configs`` independent ticks in one launch (mpcmmd_carla_solve_batch),
+each bit-identical to its ``compute_cem_*`` call.
 """
 from __future__ import annotations
 
@@ -34,7 +37,8 @@ _TOWN = {"Town10HD": "carla_town10hd"}
 
 class CEM:
     def __init__(self, num_reduced_sqrt, num_mother, num_obs, noise_level, num_prime, noise, town,
-                 acc_const_noise, steer_const_noise, *, num_batch=100, maxiter_cem=20, device=None, seed=0):
+                 acc_const_noise, steer_const_noise, *, num_batch=100, maxiter_cem=20, device=None, seed=0,
+                 max_configs=1):
         N = native()
         if noise not in N.NOISE:
             raise ValueError("noise must be 'gaussian' or 'beta'")
@@ -83,7 +87,8 @@ class CEM:
         self.P_jax, self.Pdot_jax, self.Pddot_jax = (a.astype(np.float32) for a in (self.P, self.Pdot, self.Pddot))
         self.nvar = 11
         self.cem_helper = Helper(self)
-        self._h = N.Handle(self._cfg)
+        self.max_configs = int(max_configs)
+        self._h = N.Handle(self._cfg, self.max_configs)
 
     def _solve(self, cost, idx_mpc, init_state_global, mean_param_init, cov_param_init, x_obs_traj, y_obs_traj,
                v_des, x_path, y_path, arc_vec, Fx_dot, Fy_dot, kappa, draws=None, trace=False):
@@ -113,6 +118,20 @@ class CEM:
         (cx_best, cy_best, v_best, steering_best, mean_param)."""
         return self._solve("det", idx_mpc, init_state_global, mean_param_init, cov_param_init, x_obs_traj,
                            y_obs_traj, v_des, x_path, y_path, arc_vec, Fx_dot, Fy_dot, kappa, **kw)
+
+    def compute_cem_batch(self, cost, idx_mpc, init_states, means, cov, x_obs, y_obs, v_des, paths):
+        """len(idx_mpc) <= max_configs independent ticks under one cost ("mmd",
+        "cvar" or "det") in one batch: init_states [G, 6], means [G, 8] (or one
+        [8]), cov one [8, 8] or [G, 8, 8], x_obs / y_obs [G, O, 100], v_des a
+        scalar or [G], paths G dicts of the six path arrays.  Returns a list of
+        the reference's 5-tuples (cx_best, cy_best, v_best, steering_best,
+        mean_param), tick g's equal to its compute_cem_<cost> call."""
+        kinds = {"mmd": "mmd_opt", "cvar": "cvar", "det": "det"}
+        if cost not in kinds:
+            raise ValueError("cost must be 'mmd', 'cvar' or 'det'")
+        rs = self._h.carla_solve_batch(kinds[cost], idx_mpc, init_states, means, cov, x_obs, y_obs, v_des, paths)
+        self.last_results = rs
+        return [(r["cx"], r["cy"], r["v_best"].copy(), r["steering"].copy(), r["mean_param"]) for r in rs]
 
     @property
     def handle(self):

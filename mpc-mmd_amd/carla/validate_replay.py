@@ -23,11 +23,24 @@ plan's own cost terms over the R rollouts, at quantile ``--risk-alpha``),
 and ``risk_alpha``; one more line per cost gives the mean obstacle CVaR and
 SAA.  Without ``--risk`` the file and the line are what they were.
 
+The solver is a sampling optimizer, so a difference between two costs needs
+replicas over solver seeds.  With ``--replicas E`` (E > 1) every cost runs E
+independent chains in lockstep: at tick k all E chains are ONE batched solve
+(``CEM.compute_cem_batch``, mpcmmd_carla_solve_batch) on the tick's inputs,
+computed once; chain e solves with ``idx_mpc = k + 100000 e`` (so every tick
+must be < 100000) and carries its own ``mean_param``; chain 0 is the chain of
+``--replicas 1``.  All E x ticks plans of a cost go to the one validation call
+with the TICK as every chain's validation key -- common random numbers: the
+chains differ by their plans only.  Every per-tick array of the file then has a
+leading [E] axis, ``replica_key_stride`` (100000) is stored, and the lines
+give mean +- sample standard deviation over the chains.  With ``--replicas 1``
+files and lines are byte for byte what they are without the option.
+
     cd mpc-mmd_amd/carla
     python -m validate_replay --synthetic 200 --costs cvar det --ticks 40 120 --out stats
 
 The solver, the validator and the per-tick inputs are parameters of
-``validate_replay`` (``solve=``, ``validate=``, ``risk_fn=``, ``inputs=``), so the
+``validate_replay`` (``solve=``, ``solve_batch=``, ``validate=``, ``risk_fn=``, ``inputs=``), so the
 accounting is testable without a GPU.
 """
 from __future__ import annotations
@@ -46,6 +59,7 @@ COSTS = {"mmd": "compute_cem_mmd", "cvar": "compute_cem_cvar", "det": "compute_c
 V_DES = 10.0
 MEAN = np.array([V_DES] * 4 + [0.0] * 4, np.float32)
 COV = np.diag([20.0] * 4 + [100.0] * 4).astype(np.float32)
+REPLICA_KEY_STRIDE = 100000   # chain e of --replicas solves tick k with idx_mpc = k + REPLICA_KEY_STRIDE e
 
 
 def _replay():
@@ -64,6 +78,11 @@ def _solve(prob, cost, tick, init, mean, cov, xo, yo, v_des, path):
     p = path
     return getattr(prob, COSTS[cost])(tick, init, mean, cov, xo, yo, v_des, p["x_path"], p["y_path"], p["arc_vec"],
                                       p["Fx_dot"], p["Fy_dot"], p["kappa"])
+
+
+def _solve_batch(prob, cost, idx_mpc, inits, means, cov, xo, yo, v_des, paths):
+    """len(idx_mpc) independent solves of one cost in one batch: a list of func_cem's 5-tuples."""
+    return prob.compute_cem_batch(cost, idx_mpc, inits, means, cov, xo, yo, v_des, paths)
 
 
 def _inputs(rec, prob, tick):
@@ -101,15 +120,56 @@ def solve_ticks(prob, rec, cost, ticks, v_des=V_DES, solve=None, inputs=None):
     return plans
 
 
+def solve_ticks_replicas(prob, rec, cost, ticks, replicas, v_des=V_DES, solve_batch=None, inputs=None):
+    """``replicas`` chains over ``ticks`` in lockstep, a tick's chains as one
+    batched solve: plans[e][i] as ``solve_ticks`` gives them (key = the tick
+    for every chain), plus ``replica`` and ``idx_mpc``."""
+    solve_batch = solve_batch or _solve_batch
+    inputs = inputs or _inputs
+    E = int(replicas)
+    means = [MEAN.copy() for _ in range(E)]
+    plans = [[] for _ in range(E)]
+    for k in ticks:
+        init, xo, yo, path = inputs(rec, prob, int(k))   # once per tick: the chains share them
+        idx = [int(k) + REPLICA_KEY_STRIDE * e for e in range(E)]
+        res = solve_batch(prob, cost, idx, [init] * E, [m.copy() for m in means], COV, [xo] * E, [yo] * E, v_des,
+                          [path] * E)
+        if len(res) != E:
+            raise ValueError(f"solve_batch returned {len(res)} results for {E} chains")
+        for e, (_, _, v_best, steering, mean) in enumerate(res):
+            means[e] = np.array(mean, np.float32)
+            plans[e].append(dict(tick=int(k), key=int(k), replica=e, idx_mpc=idx[e], init=init, xo=xo, yo=yo,
+                                 path=path, v_best=np.array(v_best), steering=np.array(steering),
+                                 mean_param=means[e].copy()))
+    return plans
+
+
+def _mean_std(v):
+    """mean and sample standard deviation (n - 1) over the chains"""
+    v = np.asarray(v, np.float64)
+    return float(v.mean()), float(v.std(ddof=1)) if v.size > 1 else 0.0
+
+
 def validate_replay(rec, prob, costs=("mmd", "cvar", "det"), ticks=None, num_rollouts=1000, out_dir=None, seed=0,
                     v_des=V_DES, solve=None, validate=None, inputs=None, log=print, risk=False, risk_sigma=(),
-                    risk_alpha=0.98, risk_fn=None):
+                    risk_alpha=0.98, risk_fn=None, replicas=1, solve_batch=None):
     """See the module docstring.  ticks: iterable of tick indices (default:
     every tick of the recording).  risk: one ``risk_fn(prob, plans,
     num_rollouts, seed, alpha, sigma)`` call per cost (default: ``risk_plans``)
-    in place of ``validate``; it returns the counts too.  Returns {cost: the
-    npz fields}."""
+    in place of ``validate``; it returns the counts too.  replicas: E chains per
+    cost through ``solve_batch(prob, cost, idx_mpc, inits, means, cov, xo, yo,
+    v_des, paths)`` (default: ``prob.compute_cem_batch``; ``solve`` is the
+    single chain's and unused then).  Returns {cost: the npz fields}."""
     ticks = list(range(rec["ego"].shape[0])) if ticks is None else [int(k) for k in ticks]
+    E = int(replicas)
+    if E < 1:
+        raise ValueError("replicas must be >= 1")
+    if E > 1:
+        if any(k < 0 or k >= REPLICA_KEY_STRIDE for k in ticks):
+            raise ValueError(f"replicas need every tick in [0, {REPLICA_KEY_STRIDE}): chain e solves tick k with "
+                             f"idx_mpc = k + {REPLICA_KEY_STRIDE} e")
+        return _validate_replicas(rec, prob, costs, ticks, num_rollouts, out_dir, seed, v_des, solve_batch, validate,
+                                  inputs, log, risk, risk_sigma, risk_alpha, risk_fn, E)
     validate = validate or _validate
     risk_fn = risk_fn or _risk
     sigma = np.asarray(risk_sigma, np.float32).reshape(-1)
@@ -151,6 +211,51 @@ def validate_replay(rec, prob, costs=("mmd", "cvar", "det"), ticks=None, num_rol
     return results
 
 
+def _validate_replicas(rec, prob, costs, ticks, num_rollouts, out_dir, seed, v_des, solve_batch, validate, inputs, log,
+                       risk, risk_sigma, risk_alpha, risk_fn, E):
+    """validate_replay with E > 1 chains per cost."""
+    validate = validate or _validate
+    risk_fn = risk_fn or _risk
+    sigma = np.asarray(risk_sigma, np.float32).reshape(-1)
+    R, n = int(num_rollouts), len(ticks)
+    results = {}
+    for cost in costs:
+        if cost not in COSTS:
+            raise ValueError(f"cost must be one of {sorted(COSTS)}")
+        chains = solve_ticks_replicas(prob, rec, cost, ticks, E, v_des, solve_batch, inputs)
+        plans = [p for chain in chains for p in chain]   # chain-major: [E][ticks]
+        if risk:
+            res = risk_fn(prob, plans, R, seed, float(risk_alpha), sigma) if plans else {}
+        else:
+            res = validate(prob, plans, R, seed) if plans else {}
+        out = {k: np.asarray(res.get(k, np.zeros(0, np.int32)), np.int32).reshape(E, n)
+               for k in ("count", "count_rows", "count_lane")}
+        out["tick"] = np.tile(np.asarray(ticks, np.int32), (E, 1))
+        out["num_rollouts"] = np.int32(R)
+        out["replica_key_stride"] = np.int32(REPLICA_KEY_STRIDE)
+        if risk:
+            for k in RISK_KEYS:
+                shape = (E, n, 3, sigma.size) if k == "mmd" else (E, n, 3)
+                dt = np.int32 if k == "count_pos" else np.float32
+                out["risk_" + k] = np.asarray(res.get(k, np.zeros(shape, dt)), dt).reshape(shape)
+            out["risk_sigma"] = sigma
+            out["risk_alpha"] = np.float32(risk_alpha)
+        if out_dir is not None:
+            os.makedirs(out_dir, exist_ok=True)
+            np.savez(os.path.join(out_dir, f"validate_{cost}.npz"), **out)
+        share = _mean_std((out["count_rows"] > 0).mean(axis=1) if n else np.zeros(E))
+        prob_mean = _mean_std((out["count_rows"] / R).mean(axis=1) if n else np.zeros(E))
+        log(f"{cost}: {n} ticks x {E} replicas, share with count_rows > 0 = {share[0]:.4f} +- {share[1]:.4f}, "
+            f"mean count_rows / R = {prob_mean[0]:.6f} +- {prob_mean[1]:.6f}")
+        if risk:
+            cvar_obs = _mean_std(out["risk_cvar"][:, :, 0].mean(axis=1) if n else np.zeros(E))
+            saa_obs = _mean_std((out["risk_count_pos"][:, :, 0] / R).mean(axis=1) if n else np.zeros(E))
+            log(f"{cost}: risk over {R} rollouts, mean obstacle CVaR({float(risk_alpha):g}) = {cvar_obs[0]:.6f} +- "
+                f"{cvar_obs[1]:.6f}, mean obstacle SAA = {saa_obs[0]:.6f} +- {saa_obs[1]:.6f}")
+        results[cost] = out
+    return results
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Monte-Carlo validation of the plans of a CARLA replay")
     ap.add_argument("replay", nargs="?", help="replay .npz (replay.py)")
@@ -174,6 +279,8 @@ def main(argv=None):
                     help="also the risk statistics of the plans' cost terms (mpcmmd_validate_carla_risk)")
     ap.add_argument("--risk-sigma", type=float, nargs="+", default=[], metavar="S", help="MMD bandwidths")
     ap.add_argument("--risk-alpha", type=float, default=0.98, help="quantile level of VaR / CVaR")
+    ap.add_argument("--replicas", type=int, default=1, metavar="E",
+                    help="independent solver chains per cost, a tick's E solves in one batch")
     a = ap.parse_args(argv)
     if (a.replay is None) == (a.synthetic is None):
         ap.error("give a replay file or --synthetic TICKS")
@@ -184,10 +291,10 @@ def main(argv=None):
     from optimizer import cem
     prob = cem.CEM(a.num_reduced, 1, a.num_obs, a.noise_level, a.num_prime, a.noise, str(rec["town"]),
                    a.acc_const_noise, a.steer_const_noise, num_batch=a.num_batch, maxiter_cem=a.maxiter_cem,
-                   seed=a.seed)
+                   seed=a.seed, max_configs=a.replicas)
     ticks = None if a.ticks is None else range(a.ticks[0], a.ticks[1])
     validate_replay(rec, prob, a.costs, ticks, a.num_rollouts, a.out, a.seed, risk=a.risk,
-                    risk_sigma=a.risk_sigma, risk_alpha=a.risk_alpha)
+                    risk_sigma=a.risk_sigma, risk_alpha=a.risk_alpha, replicas=a.replicas)
     prob.handle.close()
 
 

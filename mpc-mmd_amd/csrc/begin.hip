@@ -63,7 +63,7 @@ void gen_beta_tables(mpcmmd_handle* h) {
 // axis); external draws only for n == 1 (the parity contract)
 int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc, const float* init_state,
                const float* mean, const float* cov, const float* x_obs, const float* y_obs, const float* v_des,
-               const mpcmmd_draws* draws, const mpcmmd_path* path = nullptr) {
+               const mpcmmd_draws* draws, const mpcmmd_path* path = nullptr) {  // path: n_cfg paths (CARLA)
   if (!h || !idx_mpc || !init_state || !mean || !cov || !x_obs || !y_obs || !v_des)
     return fail(MPCMMD_E_INVALID, "null argument");
   if (h->carla != (path != nullptr))
@@ -76,11 +76,17 @@ int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t
     return fail(MPCMMD_E_INVALID, "compute_cem_det exists for the CARLA optimizer only");
   if (cost_kind == MPCMMD_COST_DET && h->O > kMaxDetObs)
     return fail(MPCMMD_E_UNSUPPORTED, "compute_cem_det: num_obs <= 32");
-  if (path && (path->num_path < 4 || path->num_path > kMaxPath || !path->x_path || !path->y_path || !path->arc_vec ||
-               !path->Fx_dot || !path->Fy_dot || !path->kappa))
-    return fail(MPCMMD_E_INVALID, "path: 4 <= num_path <= 2048 and six arrays");
   if (cost_kind < 0 || cost_kind > 4) return fail(MPCMMD_E_INVALID, "cost_kind must be 0..4");
   if (n_cfg < 1 || n_cfg > h->Gmax) return fail(MPCMMD_E_INVALID, "n_cfg must be 1..max_configs of the handle");
+  for (int g = 0; path && g < n_cfg; ++g) {
+    const mpcmmd_path& q = path[g];
+    if (q.num_path < 4 || q.num_path > kMaxPath || !q.x_path || !q.y_path || !q.arc_vec || !q.Fx_dot || !q.Fy_dot ||
+        !q.kappa)
+      return fail(MPCMMD_E_INVALID, "path: 4 <= num_path <= 2048 and six arrays");
+    // Params::P is one scalar and the k_frenet / k_front LDS sizes depend on it
+    if (q.num_path != path[0].num_path)
+      return fail(MPCMMD_E_INVALID, "paths of one batch must have the same num_path");
+  }
   if (draws && n_cfg > 1) return fail(MPCMMD_E_INVALID, "external draws need n_cfg == 1");
   if (cost_kind == MPCMMD_COST_MMD_OPT && !h->mmd_ok) return fail(MPCMMD_E_UNSUPPORTED, h->mmd_why);
   return guarded([&] {
@@ -129,22 +135,35 @@ int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t
     const std::vector<float>& z0 = draws && draws->pop0 ? z0x : h->pop0_normals;
     std::vector<double> sc(size_t(G) * 4 * kNvar);
     std::vector<float> st0(size_t(G) * 8), ob(size_t(G) * 2 * O * H), pop(size_t(G) * B * 8);
-    std::vector<float> rows0;  // CARLA noisy initial rows [R0][8]
     const bool det = cost_kind == MPCMMD_COST_DET;  // the det projection's own KKT
     const double* pkx = det ? h->det_kx.data() : h->pc.proj_kinv_x.data();
     const double* pky = det ? h->det_ky.data() : h->pc.proj_kinv_y.data();
+    CarlaBatch cb;  // CARLA: the noisy initial rows, path and det track images of every configuration
+    if (h->carla) {
+      // compute_noisy_init_state / _baseline / _det (cem_helper.py:661-715): n^2, n or 1 rows,
+      // configuration g's normals from the stream keyed by idx_mpc[g]
+      const int R = cost_kind == MPCMMD_COST_MMD_OPT ? h->M : det ? 1 : h->S;
+      std::vector<std::vector<float>> own(G);
+      std::vector<const float*> eps(G);
+      std::vector<PathView> views(G);
+      for (int g = 0; g < G; ++g) {
+        views[g] = view_of(path[g]);
+        eps[g] = draws ? draws->init_eps : nullptr;  // external draws: G == 1
+        if (!eps[g]) {
+          own[g] = host_normals(uint32_t(idx_mpc[g]), h->cfg.seed, kStreamInitEps, 0, size_t(R) * 4);
+          eps[g] = own[g].data();
+        }
+      }
+      cb = carla_batch(h->pc, G, R, h->R0, O, det, init_state, views.data(), eps.data(), x_obs, y_obs);
+    }
     for (int g = 0; g < G; ++g) {
       const float* is = init_state + size_t(g) * 6;
       // boundary vectors (cem_helper.py:152-167) and the per-solve KKT columns
       double bx[3] = {is[0], is[2], is[4]};
       double by[4] = {is[1], is[3], is[5], 0.0};
-      if (h->carla) {
-        // compute_noisy_init_state / _baseline / _det (cem_helper.py:661-715): n^2, n or 1 rows
-        const int R = cost_kind == MPCMMD_COST_MMD_OPT ? h->M : det ? 1 : h->S;
-        const float* eps = draws ? draws->init_eps : nullptr;
-        std::vector<float> own;
-        if (!eps) own = host_normals(uint32_t(idx_mpc[g]), h->cfg.seed, kStreamInitEps, 0, size_t(R) * 4);
-        carla_rows(h->pc, R, h->R0, is, view_of(*path), eps ? eps : own.data(), rows0, bx, by);
+      if (h->carla) {  // from the mean of the noisy rows' Frenet states (carla_rows)
+        std::memcpy(bx, &cb.bx[size_t(g) * 3], sizeof bx);
+        std::memcpy(by, &cb.by[size_t(g) * 4], sizeof by);
       }
       solve_columns(h->pc, pkx, pky, bx, by, sc.data() + size_t(g) * 4 * kNvar);
       initial_state(is, st0.data() + size_t(g) * 8);
@@ -154,17 +173,19 @@ int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t
     }
     upload_staged(h, p.solve_c, sc.data(), sc.size() * 8);
     if (h->carla) {
-      upload_staged(h, p.st0r, rows0.data(), rows0.size() * 4);
-      const float* arrs[6] = {path->x_path, path->y_path, path->arc_vec, path->Fx_dot, path->Fy_dot, path->kappa};
-      for (int k = 0; k < 6; ++k)
-        upload_staged(h, p.path, arrs[k], size_t(path->num_path) * 4, size_t(k) * kMaxPath * 4);
-      p.P = path->num_path;
-      if (cost_kind == MPCMMD_COST_DET) {  // all 100 plan points of the tracks; risks stay 0 (no risk stage)
-        upload_staged(h, p.obs_full, x_obs, size_t(O) * kNum * 4);
-        upload_staged(h, p.obs_full, y_obs, size_t(O) * kNum * 4, size_t(O) * kNum * 4);
-        HIPC(hipMemsetAsync(p.obs_cost, 0, size_t(B) * 4, h->stream));
-        HIPC(hipMemsetAsync(p.lane_cost, 0, size_t(B) * 4, h->stream));
-        HIPC(hipMemsetAsync(p.lane_des, 0, size_t(B) * 4, h->stream));
+      // one staged copy per buffer whatever G is (the staging area holds each staged buffer once)
+      for (const CarlaBatch::Piece& piece : cb.staged()) {
+        const std::string name(piece.buffer);
+        const void* dst = name == "st0r" ? static_cast<const void*>(p.st0r)
+                          : name == "path" ? static_cast<const void*>(p.path)
+                                           : static_cast<const void*>(p.obs_full);
+        upload_staged(h, dst, piece.image->data(), piece.image->size() * 4);
+      }
+      p.P = path[0].num_path;
+      if (cost_kind == MPCMMD_COST_DET) {  // the risks stay 0 (no risk stage)
+        HIPC(hipMemsetAsync(p.obs_cost, 0, size_t(G) * B * 4, h->stream));
+        HIPC(hipMemsetAsync(p.lane_cost, 0, size_t(G) * B * 4, h->stream));
+        HIPC(hipMemsetAsync(p.lane_des, 0, size_t(G) * B * 4, h->stream));
       }
     }
     upload_staged(h, p.st0, st0.data(), st0.size() * 4);
@@ -296,6 +317,24 @@ int mpcmmd_carla_begin(mpcmmd_handle* h, int32_t cost_kind, int32_t idx_mpc, con
                        const mpcmmd_path* path, const mpcmmd_draws* draws) {
   if (!path) return fail(MPCMMD_E_INVALID, "null path");
   return begin_impl(h, 1, cost_kind, &idx_mpc, init_state, mean, cov, x_obs, y_obs, &v_des, draws, path);
+}
+
+int mpcmmd_carla_begin_batch(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc,
+                             const float* init_state, const float* mean, const float* cov, const float* x_obs,
+                             const float* y_obs, const float* v_des, const mpcmmd_path* paths) {
+  if (!paths) return fail(MPCMMD_E_INVALID, "null argument");
+  return begin_impl(h, n_cfg, cost_kind, idx_mpc, init_state, mean, cov, x_obs, y_obs, v_des, nullptr, paths);
+}
+
+int mpcmmd_carla_solve_batch(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc,
+                             const float* init_state, const float* mean, const float* cov, const float* x_obs,
+                             const float* y_obs, const float* v_des, const mpcmmd_path* paths, mpcmmd_result* out) {
+  if (!out) return fail(MPCMMD_E_INVALID, "null argument");
+  int rc = mpcmmd_carla_begin_batch(h, n_cfg, cost_kind, idx_mpc, init_state, mean, cov, x_obs, y_obs, v_des, paths);
+  if (rc) return rc;
+  rc = mpcmmd_iterate(h, 0, h->T);
+  if (rc) return rc;
+  return mpcmmd_finish_batch(h, n_cfg, out);
 }
 
 int mpcmmd_carla_solve(mpcmmd_handle* h, int32_t cost_kind, int32_t idx_mpc, const float init_state[6],

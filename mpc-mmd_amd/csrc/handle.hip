@@ -129,8 +129,6 @@ int mpcmmd_create_batch(const mpcmmd_config* cfg, int32_t max_configs, mpcmmd_ha
     p.y_des1 = float(h->pc.y_des_1);
     p.y_des2 = float(h->pc.y_des_2);
     p.gamma_des = float(h->pc.gamma_lane_des);
-    if (h->carla && max_configs != 1)
-      throw std::invalid_argument("CARLA handles solve one configuration (max_configs = 1)");
     if (h->carla) {
       h->R0 = mmd_ok ? std::max(h->M, S) : S;
       p.R0 = h->R0;

@@ -201,10 +201,14 @@ __global__ __launch_bounds__(256) void k_front(Params p, int t) {
     for (int j = 0; j < kPer; ++j)
       if (int(threadIdx.x) + 256 * j < kQ) s4[threadIdx.x + 256 * j] = v[j];
   }
+  // CARLA launches are configuration-aligned (launch_front): ceil(B / 4) blocks
+  // per configuration, so a block's four candidates share one path and one set
+  // of det tracks for any B.  With G = 1 this is the plain grid of (Bt + 3) / 4
+  int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (p.carla) {
-    // every candidate of a block belongs to one configuration when B % 4 == 0
-    // (the host checks); the block's first candidate names it
-    const int g = min(blockIdx.x * 4, p.Bt - 1) / p.B;
+    const int per = (p.B + 3) / 4, g = blockIdx.x / per;
+    const int c = (blockIdx.x - g * per) * 4 + int(threadIdx.x >> 6);  // candidate within the configuration
+    b = c < p.B ? g * p.B + c : p.Bt;                                  // past the configuration's end: no work
     const float* pa = p.path + size_t(g) * 6 * kMaxPath;
     for (int i = threadIdx.x; i < p.P; i += blockDim.x) {
       sPath[i] = pa[2 * kMaxPath + i];
@@ -219,7 +223,6 @@ __global__ __launch_bounds__(256) void k_front(Params p, int t) {
   MPCMMD_STAMP(p, 40);
   MPCMMD_STAMPW(p, 1);
   const int lane = threadIdx.x & 63;
-  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= p.Bt) return;
   const double* solve_c = p.solve_c + size_t(b / p.B) * 4 * kNv;  // this candidate's configuration
   const int t0 = lane, t1 = lane + 64;
@@ -617,12 +620,15 @@ __global__ __launch_bounds__(256) void k_front(Params p, int t) {
 }  // namespace
 
 void launch_front(const Params& p, int t, hipStream_t s) {
+  // CARLA: blocks of four candidates of ONE configuration (the block stages that
+  // configuration's path in LDS); G = 1: (Bt + 3) / 4 either way
+  const int blocks = p.carla ? p.G * ((p.B + 3) / 4) : (p.Bt + 3) / 4;
   if (p.cost == 4) {  // MPCMMD_COST_DET (CARLA handles only)
     const size_t lds = (size_t(2) * p.P + size_t(2) * p.O * kN) * 4;
-    hipLaunchKernelGGL(k_front<true>, dim3((p.Bt + 3) / 4), dim3(256), lds, s, p, t);
+    hipLaunchKernelGGL(k_front<true>, dim3(blocks), dim3(256), lds, s, p, t);
     return;
   }
-  hipLaunchKernelGGL(k_front<false>, dim3((p.Bt + 3) / 4), dim3(256), p.carla ? size_t(2) * p.P * 4 : 0, s, p, t);
+  hipLaunchKernelGGL(k_front<false>, dim3(blocks), dim3(256), p.carla ? size_t(2) * p.P * 4 : 0, s, p, t);
 }
 
 }  // namespace mpcmmd

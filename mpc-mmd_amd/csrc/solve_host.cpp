@@ -153,6 +153,54 @@ void carla_rows(const ProblemConsts& pc, int R, int R0, const float* is, const P
   by[0] = m[1], by[1] = m[3], by[2] = m[5], by[3] = 0.0;
 }
 
+void carla_rows_batch(const ProblemConsts& pc, int G, int R, int R0, const float* init_state, const PathView* paths,
+                      const float* const* eps, std::vector<float>& rows, double* bx, double* by) {
+  rows.assign(size_t(G) * R0 * 8, 0.0f);
+  std::vector<float> one;
+  for (int g = 0; g < G; ++g) {
+    carla_rows(pc, R, R0, init_state + size_t(g) * 6, paths[g], eps[g], one, bx + size_t(g) * 3, by + size_t(g) * 4);
+    std::memcpy(rows.data() + size_t(g) * R0 * 8, one.data(), one.size() * 4);
+  }
+}
+
+std::vector<float> path_image(int G, const PathView* paths) {
+  std::vector<float> img(size_t(G) * 6 * kMaxPath, 0.0f);
+  for (int g = 0; g < G; ++g) {
+    const PathView& pv = paths[g];
+    if (pv.P < 1 || pv.P > kMaxPath) throw std::invalid_argument("path image: num_path out of range");
+    const float* arrs[6] = {pv.x, pv.y, pv.arc, pv.Fxd, pv.Fyd, pv.kappa};
+    for (int k = 0; k < 6; ++k) std::memcpy(img.data() + (size_t(g) * 6 + k) * kMaxPath, arrs[k], size_t(pv.P) * 4);
+  }
+  return img;
+}
+
+std::vector<float> det_track_image(int G, int O, const float* x_obs, const float* y_obs) {
+  const size_t one = size_t(O) * kNum;
+  std::vector<float> img(size_t(G) * 2 * one);
+  for (int g = 0; g < G; ++g) {
+    std::memcpy(img.data() + (size_t(g) * 2) * one, x_obs + size_t(g) * one, one * 4);
+    std::memcpy(img.data() + (size_t(g) * 2 + 1) * one, y_obs + size_t(g) * one, one * 4);
+  }
+  return img;
+}
+
+CarlaBatch carla_batch(const ProblemConsts& pc, int G, int R, int R0, int O, bool det, const float* init_state,
+                       const PathView* paths, const float* const* eps, const float* x_obs, const float* y_obs) {
+  CarlaBatch cb;
+  cb.bx.assign(size_t(G) * 3, 0.0);
+  cb.by.assign(size_t(G) * 4, 0.0);
+  carla_rows_batch(pc, G, R, R0, init_state, paths, eps, cb.rows, cb.bx.data(), cb.by.data());
+  cb.path = path_image(G, paths);
+  if (det) cb.tracks = det_track_image(G, O, x_obs, y_obs);
+  return cb;
+}
+
+std::vector<CarlaBatch::Piece> CarlaBatch::staged() const {
+  std::vector<Piece> out = {{"st0r", &rows}, {"path", &path}};
+  if (!tracks.empty()) out.push_back({"obs_full", &tracks});
+  return out;
+}
+
 void plan_controls(const float* v_all, const float* steer, int K, int H, std::vector<float>& acc,
                    std::vector<float>& steer_out) {
   acc.assign(size_t(K) * H, 0.0f);

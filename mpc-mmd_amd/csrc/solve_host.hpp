@@ -59,6 +59,39 @@ void carla_velocity_heading(float v0, float psi0, float* vx, float* vy, float* p
 void carla_rows(const ProblemConsts& pc, int R, int R0, const float* init_state, const PathView& path,
                 const float* eps, std::vector<float>& rows, double* bx, double* by);
 
+// The CARLA setup of a batch of G configurations (mpcmmd_carla_begin_batch):
+// whole host images of the three per-configuration CARLA buffers, each
+// uploaded as ONE staged piece whatever G is (buffers.hpp declares 1, 6 and 2
+// pieces for them), and the boundary vectors of every configuration.
+struct CarlaBatch {
+  std::vector<float> rows;     // st0r [G][R0][8]
+  std::vector<float> path;     // path [G][6][kMaxPath]: array k of path g at (g 6 + k) kMaxPath, zero padded
+  std::vector<float> tracks;   // obs_full [G][2][O][100]; empty unless det
+  std::vector<double> bx, by;  // [G][3], [G][4]
+  struct Piece {
+    const char* buffer;  // the device buffer's name (buffers.hpp)
+    const std::vector<float>* image;
+  };
+  std::vector<Piece> staged() const;  // the staged copies of a begin, in upload order
+};
+
+// carla_rows of every configuration into its slice: init_state [G][6], paths
+// [G], eps[g] -> [R][4]; rows [G][R0][8], bx [G][3], by [G][4].  Slice g is
+// bit for bit what carla_rows gives for configuration g alone.
+void carla_rows_batch(const ProblemConsts& pc, int G, int R, int R0, const float* init_state, const PathView* paths,
+                      const float* const* eps, std::vector<float>& rows, double* bx, double* by);
+
+// the path image [G][6][kMaxPath] of G paths of one length (x, y, arc_vec, Fx_dot, Fy_dot, kappa)
+std::vector<float> path_image(int G, const PathView* paths);
+
+// compute_cem_det's tracks, all 100 plan points: x_obs / y_obs [G][O][100] -> [G][2][O][100]
+std::vector<float> det_track_image(int G, int O, const float* x_obs, const float* y_obs);
+
+// The whole CARLA setup: rows and boundary vectors (R noisy rows of R0), the
+// path image, and with det the track image.
+CarlaBatch carla_batch(const ProblemConsts& pc, int G, int R, int R0, int O, bool det, const float* init_state,
+                       const PathView* paths, const float* const* eps, const float* x_obs, const float* y_obs);
+
 // The controls of K plans for the CARLA validator (compute_controls,
 // cem_helper.py: acc = diff([v, v_end]) / t): v, steer [K][100] -> acc, steer_out [K][H]
 void plan_controls(const float* v, const float* steer, int K, int H, std::vector<float>& acc,

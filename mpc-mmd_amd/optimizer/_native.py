@@ -30,6 +30,7 @@ SYMBOLS = (
     "mpcmmd_carla_begin", "mpcmmd_carla_solve", "mpcmmd_path_smoothing", "mpcmmd_path_parameters",
     "mpcmmd_global_to_frenet", "mpcmmd_set_graphs", "mpcmmd_handle_info", "mpcmmd_validate_carla",
     "mpcmmd_validate_risk", "mpcmmd_quantile_position", "mpcmmd_validate_carla_risk",
+    "mpcmmd_carla_begin_batch", "mpcmmd_carla_solve_batch",
 )
 
 
@@ -180,6 +181,9 @@ def lib():
     L.mpcmmd_set_graphs.argtypes = [vp, C.c_int32]
     L.mpcmmd_carla_begin.argtypes = cargs
     L.mpcmmd_carla_solve.argtypes = cargs + [C.POINTER(Result)]
+    if hasattr(L, "mpcmmd_carla_begin_batch"):   # an older library lacks them: carla_begin_batch raises
+        L.mpcmmd_carla_begin_batch.argtypes = bargs + [C.POINTER(Path)]
+        L.mpcmmd_carla_solve_batch.argtypes = bargs + [C.POINTER(Path), C.POINTER(Result)]
     L.mpcmmd_path_smoothing.argtypes = [C.c_int32, fp, fp, C.c_float, fp, fp]
     L.mpcmmd_path_parameters.argtypes = [C.c_int32, fp, fp, fp, fp, fp, fp, fp, fp, fp]
     L.mpcmmd_global_to_frenet.argtypes = [C.POINTER(Path), C.c_int32, fp, fp, fp, fp, fp, fp, fp]
@@ -608,16 +612,52 @@ class Handle:
         check(self._L.mpcmmd_begin_batch(self._h, G, COST[cost], *args))
         self._G = G
 
+    def carla_begin_batch(self, cost, idx_mpc, init_state, mean, cov, x_obs, y_obs, v_des, paths):
+        """mpcmmd_carla_begin_batch (then iterate / finish_batch): len(idx_mpc)
+        CARLA ticks in one batch, cost "mmd_opt", "cvar" or "det"; the arrays
+        as ``solve_batch`` takes them; paths: one dict of PATH_KEYS per tick,
+        all of one length."""
+        if not hasattr(self._L, "mpcmmd_carla_begin_batch"):
+            raise NativeError(f"{LIB_PATH} has no mpcmmd_carla_begin_batch (built before the entry point existed): "
+                              "rebuild it")
+        G, ins, args = self._batch_inputs(idx_mpc, init_state, mean, cov, x_obs, y_obs, v_des)
+        if len(paths) != G:
+            raise ValueError("one path per configuration")
+        made = [make_path(p) for p in paths]
+        pths = (Path * G)(*(m[0] for m in made))
+        ins["_paths"] = (pths, made)
+        self._keep = [ins]
+        check(self._L.mpcmmd_carla_begin_batch(self._h, G, COST[cost], *args, pths))
+        self._G = G
+
+    def carla_solve_batch(self, cost, idx_mpc, init_state, mean, cov, x_obs, y_obs, v_des, paths):
+        """mpcmmd_carla_solve_batch: one result dict per tick (the keys of
+        ``carla_solve``), each bit-identical to ``carla_solve`` of that tick
+        alone on a handle with the same "gen_wave"."""
+        self.carla_begin_batch(cost, idx_mpc, init_state, mean, cov, x_obs, y_obs, v_des, paths)
+        self.iterate(0, self.cfg.maxiter_cem)
+        return self.finish_batch()
+
     def finish_batch(self):
         G = self._G
         rs = (Result * G)()
         betas = [np.zeros(max(self.cfg.num_reduced, 1), np.float32) for _ in range(G)]
+        carla = self.cfg.variant >= 2
+        steer = [np.zeros(100, np.float32) for _ in range(G)] if carla else None
+        vbest = [np.zeros(100, np.float32) for _ in range(G)] if carla else None
         for g in range(G):
             rs[g].beta = _fptr(betas[g])
+            if carla:
+                rs[g].steering = _fptr(steer[g])
+                rs[g].v_best = _fptr(vbest[g])
         check(self._L.mpcmmd_finish_batch(self._h, G, rs))
-        return [dict(cx=np.array(r.cx, np.float32), cy=np.array(r.cy, np.float32),
-                     cost_lane=np.float32(r.cost_lane), cost_obs=np.float32(r.cost_obs), sigma=np.float32(r.sigma),
-                     res_beta=np.array(r.res_beta, np.float32), beta=betas[g]) for g, r in enumerate(rs)]
+        out = [dict(cx=np.array(r.cx, np.float32), cy=np.array(r.cy, np.float32),
+                    cost_lane=np.float32(r.cost_lane), cost_obs=np.float32(r.cost_obs), sigma=np.float32(r.sigma),
+                    res_beta=np.array(r.res_beta, np.float32), beta=betas[g]) for g, r in enumerate(rs)]
+        if carla:
+            for g, r in enumerate(rs):
+                out[g].update(steering=steer[g], v_best=vbest[g], mean_param=np.array(r.mean_param, np.float32))
+        return out
 
     def solve_batch(self, cost, idx_mpc, init_state, mean, cov, x_obs, y_obs, v_des):
         """mpcmmd_solve_batch: len(idx_mpc) configurations in one batch.
