@@ -269,6 +269,73 @@ int mpcmmd_carla_solve_batch(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind,
                              const float* x_obs, const float* y_obs, const float* v_des,
                              const mpcmmd_path* paths, mpcmmd_result* out);
 
+/* ---- CARLA tick route -------------------------------------------------------
+ * The per-tick preprocessing of main_carla.py:345-376 (custom_path_smoothing,
+ * compute_path_parameters, global_to_frenet_obs_vmap, compute_obs_trajectories)
+ * and the per-tick host arithmetic of mpcmmd_carla_begin_batch (the noisy
+ * initial rows, their Frenet states and mean, the boundary vectors, the KKT
+ * columns) on the handle's stream, from the raw data of n_cfg ticks: two
+ * kernels (k_tick.hip) between one upload and the first CEM iteration, with no
+ * device-to-host copy and no stream synchronisation beyond the wait for the
+ * previous begin's staging copies.  Afterwards the handle is in exactly the
+ * state mpcmmd_carla_begin_batch leaves it in when given the host helpers'
+ * outputs for the same ticks: every buffer and every result is bit-equal
+ * (tests/test_gpu_carla_tick.py), because every sum the host forms
+ * sequentially is formed in the same order on the device.
+ *
+ * A tick context belongs to one handle and one num_path (4..2048).  It owns
+ * its device memory (the (num_path+1)^2 fp64 smoothing inverse, uploaded once;
+ * the KKT coefficient columns; the tick inputs; the rows' Frenet scratch) and
+ * its pinned staging with its own event; none of it is in the handle's buffer
+ * list.  Dynamic LDS of either kernel: 24 num_path + 16 bytes (49168 at 2048);
+ * mpcmmd_tick_create returns MPCMMD_E_UNSUPPORTED if the device's workgroup
+ * limit is below that.  Destroy the context before its handle.  Threading and
+ * device binding are the handle's.  ABI version unchanged: detect the entry
+ * points by their symbols. */
+typedef struct mpcmmd_tick mpcmmd_tick;
+int mpcmmd_tick_create(mpcmmd_handle* h, int32_t num_path, mpcmmd_tick** out);
+void mpcmmd_tick_destroy(mpcmmd_tick* t);
+
+typedef struct mpcmmd_tick_inputs { /* leading axis n_cfg */
+  const float* init_state; /* [n][6] init_state_global (main_carla.py:352) */
+  const float* x_wp;       /* [n][num_path] waypoints shifted to the ego: custom_path_smoothing's input */
+  const float* y_wp;
+  /* [n][num_obs][5]: x, y (shifted to the ego), vx, vy, psi of the num_obs nearest obstacles, in order.
+   * psi is needed: global_to_frenet_obs scales the speed by cos / sin of (psi - path heading), so it
+   * reaches vx and vy of every moving obstacle. */
+  const float* obstacles;
+  float threshold; /* custom_path_smoothing's (driver: 0.1) */
+} mpcmmd_tick_inputs;
+
+/* begin of n_cfg ticks through the tick route, then mpcmmd_iterate /
+ * mpcmmd_finish_batch / mpcmmd_set_graphs / mpcmmd_read of the context's
+ * handle; the device-made path of tick g is slice g of mpcmmd_read(h, "path")
+ * ([6][2048]: x, y, arc_vec, Fx_dot, Fy_dot, kappa, zero beyond num_path).
+ * Internal RNG streams only (init_eps keyed by idx_mpc[g], as in the batch
+ * begin).  Before any HIP call: MPCMMD_E_INVALID for a NULL argument or array,
+ * a handle of no CARLA variant, n_cfg outside 1..max_configs, a threshold that
+ * is not finite, a cost other than mmd_opt, cvar or det; MPCMMD_E_UNSUPPORTED
+ * for det with num_obs > 32 and for mmd_opt on a handle without it.  A failure
+ * after the first enqueue drains the stream before the staging is reused. */
+int mpcmmd_carla_tick_begin_batch(mpcmmd_tick* t, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc,
+                                  const mpcmmd_tick_inputs* in, const float* mean, const float* cov,
+                                  const float* v_des);
+/* begin, mpcmmd_iterate(0, T), mpcmmd_finish_batch */
+int mpcmmd_carla_tick_solve_batch(mpcmmd_tick* t, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc,
+                                  const mpcmmd_tick_inputs* in, const float* mean, const float* cov,
+                                  const float* v_des, mpcmmd_result* out);
+
+/* The host route of the same tick in one call (no GPU needed): path_smoothing,
+ * path_parameters, global_to_frenet of the obstacles (v = sqrtf(vx^2 + vy^2),
+ * vdot = psidot = 0) and their tracks x[o][k] = x_o + vx_o tt[k] in fp32 on
+ * tt = np.linspace(0, 15, 100).astype(float32).  obstacles [num_obs][5] as in
+ * mpcmmd_tick_inputs; path6 [6][num_path]: x, y, arc_vec, Fx_dot, Fy_dot,
+ * kappa; x_obs, y_obs [num_obs][100].  init_state is not used by the
+ * preprocessing (it is the solve's) and must not be NULL. */
+int mpcmmd_carla_tick_host(int32_t num_path, int32_t num_obs, const float init_state[6], const float* x_wp,
+                           const float* y_wp, const float* obstacles, float threshold, float* path6, float* x_obs,
+                           float* y_obs);
+
 /* Helper.custom_path_smoothing(x_waypoints, y_waypoints, threshold)
  * (carla/optimizer/cem_helper.py:279-318, 391-410): 10 ADMM iterations of the
  * jerk-smoothing QP; the (num_path+1)^2 KKT inverse is built once per

@@ -19,7 +19,9 @@ runs.  Extra keyword-only options:
 per call ``draws`` (explicit standard normals incl. ``init_eps``,
 include/mpcmmd.h) and ``trace``.  ``compute_cem_batch`` solves up to
 ``max_configs`` independent ticks in one launch (mpcmmd_carla_solve_batch),
-each bit-identical to its ``compute_cem_*`` call.
+each bit-identical to its ``compute_cem_*`` call; ``compute_cem_tick_batch``
+does the same from the raw tick data, with the path and Frenet preprocessing
+on the GPU (mpcmmd_carla_tick_solve_batch).
 """
 from __future__ import annotations
 
@@ -89,6 +91,7 @@ class CEM:
         self.cem_helper = Helper(self)
         self.max_configs = int(max_configs)
         self._h = N.Handle(self._cfg, self.max_configs)
+        self._ticks = {}
 
     def _solve(self, cost, idx_mpc, init_state_global, mean_param_init, cov_param_init, x_obs_traj, y_obs_traj,
                v_des, x_path, y_path, arc_vec, Fx_dot, Fy_dot, kappa, draws=None, trace=False):
@@ -132,6 +135,34 @@ class CEM:
         rs = self._h.carla_solve_batch(kinds[cost], idx_mpc, init_states, means, cov, x_obs, y_obs, v_des, paths)
         self.last_results = rs
         return [(r["cx"], r["cy"], r["v_best"].copy(), r["steering"].copy(), r["mean_param"]) for r in rs]
+
+    def compute_cem_tick_batch(self, cost, idx_mpc, init_states, x_wp, y_wp, obstacles, threshold, means, cov, v_des):
+        """``compute_cem_batch`` from the raw tick data (the tick route,
+        mpcmmd_carla_tick_solve_batch): the preprocessing of main_carla.py:
+        364-376 runs on the GPU in front of the solve.  x_wp, y_wp [G, num_path]
+        the waypoints shifted to the ego, obstacles [G, num_obs, 5] = x, y
+        (shifted), vx, vy, psi of the nearest obstacles, threshold that of
+        custom_path_smoothing.  Returns (the list of 5-tuples ``compute_cem_batch``
+        returns, the list of each tick's path dict); both equal the host
+        helpers' route bit for bit."""
+        kinds = {"mmd": "mmd_opt", "cvar": "cvar", "det": "det"}
+        if cost not in kinds:
+            raise ValueError("cost must be 'mmd', 'cvar' or 'det'")
+        P = int(np.asarray(x_wp).shape[-1])
+        if P not in self._ticks:   # one tick context per path length, made at its first use
+            self._ticks[P] = native().Tick(self._h, P)
+        tk = self._ticks[P]
+        rs = tk.solve_batch(kinds[cost], idx_mpc, init_states, x_wp, y_wp, obstacles, threshold, means, cov, v_des)
+        self.last_results = rs
+        return ([(r["cx"], r["cy"], r["v_best"].copy(), r["steering"].copy(), r["mean_param"]) for r in rs],
+                [tk.path(g) for g in range(len(rs))])
+
+    def close(self):
+        """Free the tick contexts, then the handle."""
+        for tk in self._ticks.values():
+            tk.close()
+        self._ticks = {}
+        self._h.close()
 
     @property
     def handle(self):

@@ -21,6 +21,10 @@ to the ego, ``custom_path_smoothing``, ``compute_path_parameters``, the
 nearest ``num_obs`` obstacles (``compute_obs_data``, main_carla.py:74-150)
 mapped to the Frenet frame and extended to constant-velocity tracks.
 
+``tick_raw_inputs`` stops before the helpers: the shifted waypoints and nearest
+obstacles, which the tick route (mpcmmd_carla_tick_solve_batch) takes as they
+are.
+
 ``record_synthetic`` makes a recording without CARLA: a Town05-like route
 (straight, 90-degree left bend, straight, sampled every 0.25 m like the
 route planner, carla_simulation.py:72), extended past its end as
@@ -167,23 +171,32 @@ def nearest_obstacles(obs, ego, num_obs):
     return keep[np.argsort(dist, kind="stable")[:num_obs]].astype(F32)
 
 
+def tick_raw_inputs(rec, k, num_obs):
+    """The raw data of tick k as the tick route takes it (main_carla.py:345-361):
+    (init_state_global, x_wp, y_wp, obstacles) -- the waypoints shifted to the
+    ego, and the ``num_obs`` nearest obstacles [num_obs, 5] = x, y (shifted to
+    the ego), vx, vy, psi."""
+    ego = rec["ego"][k]
+    x0, y0 = float(ego[0]), float(ego[1])
+    xw = (rec["waypoints"][k, 0].astype(np.float64) - x0).astype(F32)
+    yw = (rec["waypoints"][k, 1].astype(np.float64) - y0).astype(F32)
+    ob = nearest_obstacles(rec["obstacles"][k], ego, num_obs).copy()
+    ob[:, 0] = (ob[:, 0].astype(np.float64) - x0).astype(F32)
+    ob[:, 1] = (ob[:, 1].astype(np.float64) - y0).astype(F32)
+    init = np.array([0.0, 0.0, ego[2], ego[3], ego[4], ego[5]], F32)   # x_global_shifted = y_global_shifted = 0
+    return init, xw, yw, ob
+
+
 def tick_inputs(rec, k, helper, num_obs, threshold=0.1):
     """Arguments of compute_cem_* for tick k (main_carla.py:345-382) through
     ``helper`` (``prob.cem_helper`` of the drop-in, the library's helpers):
     (init_state_global, x_obs_traj, y_obs_traj, path dict)."""
-    ego = rec["ego"][k]
-    x0, y0 = float(ego[0]), float(ego[1])
     h = helper
-    xw = (rec["waypoints"][k, 0].astype(np.float64) - x0).astype(F32)
-    yw = (rec["waypoints"][k, 1].astype(np.float64) - y0).astype(F32)
+    init, xw, yw, ob = tick_raw_inputs(rec, k, num_obs)
     x_path, y_path = h.custom_path_smoothing(xw, yw, threshold)
     Fxd, Fyd, _, _, arc, kap, _ = h.compute_path_parameters(x_path, y_path)
-    ob = nearest_obstacles(rec["obstacles"][k], ego, num_obs)
-    xs = (ob[:, 0].astype(np.float64) - x0).astype(F32)
-    ys = (ob[:, 1].astype(np.float64) - y0).astype(F32)
-    xi, yi, vxi, vyi, pi = h.global_to_frenet_obs_vmap(xs, ys, ob[:, 2], ob[:, 3], ob[:, 4], x_path, y_path, arc,
-                                                       Fxd, Fyd, kap)
+    xi, yi, vxi, vyi, pi = h.global_to_frenet_obs_vmap(ob[:, 0], ob[:, 1], ob[:, 2], ob[:, 3], ob[:, 4], x_path, y_path,
+                                                       arc, Fxd, Fyd, kap)
     xo, yo, _ = h.compute_obs_trajectories(xi, yi, vxi, vyi, pi)
-    init = np.array([0.0, 0.0, ego[2], ego[3], ego[4], ego[5]], F32)   # x_global_shifted = y_global_shifted = 0
     path = dict(x_path=x_path, y_path=y_path, arc_vec=arc, Fx_dot=Fxd, Fy_dot=Fyd, kappa=kap)
     return init, xo, yo, path

@@ -36,6 +36,12 @@ leading [E] axis, ``replica_key_stride`` (100000) is stored, and the lines
 give mean +- sample standard deviation over the chains.  With ``--replicas 1``
 files and lines are byte for byte what they are without the option.
 
+With ``--device-setup`` the solves go through the tick route
+(``CEM.compute_cem_tick_batch``, mpcmmd_carla_tick_solve_batch): the path
+smoothing, path parameters and Frenet setup of every tick run on the GPU in
+front of the solve, from ``replay.tick_raw_inputs``.  The route is bit-equal to
+the host helpers', so files and lines are unchanged.
+
     cd mpc-mmd_amd/carla
     python -m validate_replay --synthetic 200 --costs cvar det --ticks 40 120 --out stats
 
@@ -89,6 +95,25 @@ def _inputs(rec, prob, tick):
     return _replay().tick_inputs(rec, tick, prob.cem_helper, prob.num_obs)
 
 
+THRESHOLD = 0.1   # custom_path_smoothing's (main_carla.py:363)
+
+
+def _device_tick(prob, rec, cost, tick, idx_mpc, means, v_des):
+    """len(idx_mpc) solves of one tick through the tick route (``--device-setup``):
+    (the 5-tuples, init, xo, yo, path) with the path read back from the device
+    and the validator's obstacle tracks made from it by the host helpers."""
+    E = len(idx_mpc)
+    init, xw, yw, ob = _replay().tick_raw_inputs(rec, tick, prob.num_obs)
+    res, paths = prob.compute_cem_tick_batch(cost, idx_mpc, [init] * E, [xw] * E, [yw] * E, [ob] * E, THRESHOLD,
+                                             means, COV, v_des)
+    path, h = paths[0], prob.cem_helper
+    xi, yi, vxi, vyi, pi = h.global_to_frenet_obs_vmap(ob[:, 0], ob[:, 1], ob[:, 2], ob[:, 3], ob[:, 4],
+                                                       *(path[k] for k in ("x_path", "y_path", "arc_vec", "Fx_dot",
+                                                                           "Fy_dot", "kappa")))
+    xo, yo, _ = h.compute_obs_trajectories(xi, yi, vxi, vyi, pi)
+    return res, init, xo, yo, path
+
+
 def _validate(prob, plans, num_rollouts, seed):
     # optimizer/validation.py of the package prob's class lives in (whatever name it was imported under)
     pkg = type(prob).__module__.rpartition(".")[0]
@@ -105,35 +130,45 @@ def _risk(prob, plans, num_rollouts, seed, alpha, sigma):
 RISK_KEYS = ("count_pos", "var", "cvar", "mean", "max", "mmd")
 
 
-def solve_ticks(prob, rec, cost, ticks, v_des=V_DES, solve=None, inputs=None):
+def solve_ticks(prob, rec, cost, ticks, v_des=V_DES, solve=None, inputs=None, device_setup=False):
     """The plans of ``ticks`` (in order) under ``cost``: per tick a dict with
-    init, xo, yo, path, v_best, steering, mean_param, tick, key (= tick)."""
+    init, xo, yo, path, v_best, steering, mean_param, tick, key (= tick).
+    device_setup: the tick route (``solve`` and ``inputs`` are unused then)."""
     solve = solve or _solve
     inputs = inputs or _inputs
     mean = MEAN.copy()
     plans = []
     for k in ticks:
-        init, xo, yo, path = inputs(rec, prob, int(k))
-        _, _, v_best, steering, mean = solve(prob, cost, int(k), init, mean, COV, xo, yo, v_des, path)
+        if device_setup:
+            res, init, xo, yo, path = _device_tick(prob, rec, cost, int(k), [int(k)], mean, v_des)
+            _, _, v_best, steering, mean = res[0]
+        else:
+            init, xo, yo, path = inputs(rec, prob, int(k))
+            _, _, v_best, steering, mean = solve(prob, cost, int(k), init, mean, COV, xo, yo, v_des, path)
         plans.append(dict(tick=int(k), key=int(k), init=init, xo=xo, yo=yo, path=path, v_best=np.array(v_best),
                           steering=np.array(steering), mean_param=np.array(mean)))
     return plans
 
 
-def solve_ticks_replicas(prob, rec, cost, ticks, replicas, v_des=V_DES, solve_batch=None, inputs=None):
+def solve_ticks_replicas(prob, rec, cost, ticks, replicas, v_des=V_DES, solve_batch=None, inputs=None,
+                         device_setup=False):
     """``replicas`` chains over ``ticks`` in lockstep, a tick's chains as one
     batched solve: plans[e][i] as ``solve_ticks`` gives them (key = the tick
-    for every chain), plus ``replica`` and ``idx_mpc``."""
+    for every chain), plus ``replica`` and ``idx_mpc``.  device_setup: the
+    tick route (``solve_batch`` and ``inputs`` are unused then)."""
     solve_batch = solve_batch or _solve_batch
     inputs = inputs or _inputs
     E = int(replicas)
     means = [MEAN.copy() for _ in range(E)]
     plans = [[] for _ in range(E)]
     for k in ticks:
-        init, xo, yo, path = inputs(rec, prob, int(k))   # once per tick: the chains share them
         idx = [int(k) + REPLICA_KEY_STRIDE * e for e in range(E)]
-        res = solve_batch(prob, cost, idx, [init] * E, [m.copy() for m in means], COV, [xo] * E, [yo] * E, v_des,
-                          [path] * E)
+        if device_setup:
+            res, init, xo, yo, path = _device_tick(prob, rec, cost, int(k), idx, [m.copy() for m in means], v_des)
+        else:
+            init, xo, yo, path = inputs(rec, prob, int(k))   # once per tick: the chains share them
+            res = solve_batch(prob, cost, idx, [init] * E, [m.copy() for m in means], COV, [xo] * E, [yo] * E, v_des,
+                              [path] * E)
         if len(res) != E:
             raise ValueError(f"solve_batch returned {len(res)} results for {E} chains")
         for e, (_, _, v_best, steering, mean) in enumerate(res):
@@ -152,14 +187,16 @@ def _mean_std(v):
 
 def validate_replay(rec, prob, costs=("mmd", "cvar", "det"), ticks=None, num_rollouts=1000, out_dir=None, seed=0,
                     v_des=V_DES, solve=None, validate=None, inputs=None, log=print, risk=False, risk_sigma=(),
-                    risk_alpha=0.98, risk_fn=None, replicas=1, solve_batch=None):
+                    risk_alpha=0.98, risk_fn=None, replicas=1, solve_batch=None, device_setup=False):
     """See the module docstring.  ticks: iterable of tick indices (default:
     every tick of the recording).  risk: one ``risk_fn(prob, plans,
     num_rollouts, seed, alpha, sigma)`` call per cost (default: ``risk_plans``)
     in place of ``validate``; it returns the counts too.  replicas: E chains per
     cost through ``solve_batch(prob, cost, idx_mpc, inits, means, cov, xo, yo,
     v_des, paths)`` (default: ``prob.compute_cem_batch``; ``solve`` is the
-    single chain's and unused then).  Returns {cost: the npz fields}."""
+    single chain's and unused then).  device_setup: solve through the tick route
+    (``prob.compute_cem_tick_batch`` on ``replay.tick_raw_inputs``); the files
+    equal the host route's.  Returns {cost: the npz fields}."""
     ticks = list(range(rec["ego"].shape[0])) if ticks is None else [int(k) for k in ticks]
     E = int(replicas)
     if E < 1:
@@ -169,7 +206,7 @@ def validate_replay(rec, prob, costs=("mmd", "cvar", "det"), ticks=None, num_rol
             raise ValueError(f"replicas need every tick in [0, {REPLICA_KEY_STRIDE}): chain e solves tick k with "
                              f"idx_mpc = k + {REPLICA_KEY_STRIDE} e")
         return _validate_replicas(rec, prob, costs, ticks, num_rollouts, out_dir, seed, v_des, solve_batch, validate,
-                                  inputs, log, risk, risk_sigma, risk_alpha, risk_fn, E)
+                                  inputs, log, risk, risk_sigma, risk_alpha, risk_fn, E, device_setup)
     validate = validate or _validate
     risk_fn = risk_fn or _risk
     sigma = np.asarray(risk_sigma, np.float32).reshape(-1)
@@ -178,7 +215,7 @@ def validate_replay(rec, prob, costs=("mmd", "cvar", "det"), ticks=None, num_rol
     for cost in costs:
         if cost not in COSTS:
             raise ValueError(f"cost must be one of {sorted(COSTS)}")
-        plans = solve_ticks(prob, rec, cost, ticks, v_des, solve, inputs)
+        plans = solve_ticks(prob, rec, cost, ticks, v_des, solve, inputs, device_setup)
         if risk:
             res = risk_fn(prob, plans, R, seed, float(risk_alpha), sigma) if plans else {}
         else:
@@ -212,7 +249,7 @@ def validate_replay(rec, prob, costs=("mmd", "cvar", "det"), ticks=None, num_rol
 
 
 def _validate_replicas(rec, prob, costs, ticks, num_rollouts, out_dir, seed, v_des, solve_batch, validate, inputs, log,
-                       risk, risk_sigma, risk_alpha, risk_fn, E):
+                       risk, risk_sigma, risk_alpha, risk_fn, E, device_setup=False):
     """validate_replay with E > 1 chains per cost."""
     validate = validate or _validate
     risk_fn = risk_fn or _risk
@@ -222,7 +259,7 @@ def _validate_replicas(rec, prob, costs, ticks, num_rollouts, out_dir, seed, v_d
     for cost in costs:
         if cost not in COSTS:
             raise ValueError(f"cost must be one of {sorted(COSTS)}")
-        chains = solve_ticks_replicas(prob, rec, cost, ticks, E, v_des, solve_batch, inputs)
+        chains = solve_ticks_replicas(prob, rec, cost, ticks, E, v_des, solve_batch, inputs, device_setup)
         plans = [p for chain in chains for p in chain]   # chain-major: [E][ticks]
         if risk:
             res = risk_fn(prob, plans, R, seed, float(risk_alpha), sigma) if plans else {}
@@ -281,6 +318,8 @@ def main(argv=None):
     ap.add_argument("--risk-alpha", type=float, default=0.98, help="quantile level of VaR / CVaR")
     ap.add_argument("--replicas", type=int, default=1, metavar="E",
                     help="independent solver chains per cost, a tick's E solves in one batch")
+    ap.add_argument("--device-setup", action="store_true",
+                    help="the per-tick path and Frenet preprocessing on the GPU (mpcmmd_carla_tick_solve_batch)")
     a = ap.parse_args(argv)
     if (a.replay is None) == (a.synthetic is None):
         ap.error("give a replay file or --synthetic TICKS")
@@ -294,7 +333,8 @@ def main(argv=None):
                    seed=a.seed, max_configs=a.replicas)
     ticks = None if a.ticks is None else range(a.ticks[0], a.ticks[1])
     validate_replay(rec, prob, a.costs, ticks, a.num_rollouts, a.out, a.seed, risk=a.risk,
-                    risk_sigma=a.risk_sigma, risk_alpha=a.risk_alpha, replicas=a.replicas)
+                    risk_sigma=a.risk_sigma, risk_alpha=a.risk_alpha, replicas=a.replicas,
+                    device_setup=a.device_setup)
     prob.handle.close()
 
 

@@ -11,10 +11,7 @@
 
 using namespace mpcmmd;
 
-namespace {
-
-// host Philox normals of stream (stream, word1) with key (k0, k1): `count` values
-std::vector<float> host_normals(uint32_t k0, uint32_t k1, uint32_t stream, uint32_t word1, size_t count) {
+std::vector<float> mpcmmd::host_normals(uint32_t k0, uint32_t k1, uint32_t stream, uint32_t word1, size_t count) {
   std::vector<float> out(count);
   double z[4];
   for (size_t j = 0; j * 4 < count; ++j) {
@@ -23,6 +20,8 @@ std::vector<float> host_normals(uint32_t k0, uint32_t k1, uint32_t stream, uint3
   }
   return out;
 }
+
+namespace {
 
 // upload through the handle's pinned staging area (mpcmmd_begin): src may be
 // a host temporary, the copy still runs after the call returns
@@ -59,14 +58,17 @@ void gen_beta_tables(mpcmmd_handle* h) {
   h->sel0_valid = false;
 }
 
+}  // namespace
+
 // mpcmmd_begin for n configurations (arrays with a leading configuration
 // axis); external draws only for n == 1 (the parity contract)
-int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc, const float* init_state,
-               const float* mean, const float* cov, const float* x_obs, const float* y_obs, const float* v_des,
-               const mpcmmd_draws* draws, const mpcmmd_path* path = nullptr) {  // path: n_cfg paths (CARLA)
-  if (!h || !idx_mpc || !init_state || !mean || !cov || !x_obs || !y_obs || !v_des)
+int mpcmmd::begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc,
+                       const float* init_state, const float* mean, const float* cov, const float* x_obs,
+                       const float* y_obs, const float* v_des, const mpcmmd_draws* draws, const mpcmmd_path* path,
+                       const TickRoute* tick) {
+  if (!h || !idx_mpc || !init_state || !mean || !cov || (!tick && (!x_obs || !y_obs)) || !v_des)
     return fail(MPCMMD_E_INVALID, "null argument");
-  if (h->carla != (path != nullptr))
+  if (h->carla != (path != nullptr || tick != nullptr))
     return fail(MPCMMD_E_INVALID, h->carla ? "CARLA handle: use mpcmmd_carla_begin / mpcmmd_carla_solve (a path is needed)"
                                            : "mpcmmd_carla_begin needs a handle of a CARLA variant");
   if (h->carla && cost_kind != MPCMMD_COST_MMD_OPT && cost_kind != MPCMMD_COST_CVAR && cost_kind != MPCMMD_COST_DET)
@@ -139,7 +141,16 @@ int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t
     const double* pkx = det ? h->det_kx.data() : h->pc.proj_kinv_x.data();
     const double* pky = det ? h->det_ky.data() : h->pc.proj_kinv_y.data();
     CarlaBatch cb;  // CARLA: the noisy initial rows, path and det track images of every configuration
-    if (h->carla) {
+    if (tick) {  // the same init_eps streams; the rows, boundary vectors and images are made on the device
+      const int R = cost_kind == MPCMMD_COST_MMD_OPT ? h->M : det ? 1 : h->S;
+      std::vector<std::vector<float>> own(G);
+      std::vector<const float*> eps(G);
+      for (int g = 0; g < G; ++g) {
+        own[g] = host_normals(uint32_t(idx_mpc[g]), h->cfg.seed, kStreamInitEps, 0, size_t(R) * 4);
+        eps[g] = own[g].data();
+      }
+      tick->enqueue(tick->ctx, G, cost_kind, R, eps.data());
+    } else if (h->carla) {
       // compute_noisy_init_state / _baseline / _det (cem_helper.py:661-715): n^2, n or 1 rows,
       // configuration g's normals from the stream keyed by idx_mpc[g]
       const int R = cost_kind == MPCMMD_COST_MMD_OPT ? h->M : det ? 1 : h->S;
@@ -161,27 +172,31 @@ int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t
       // boundary vectors (cem_helper.py:152-167) and the per-solve KKT columns
       double bx[3] = {is[0], is[2], is[4]};
       double by[4] = {is[1], is[3], is[5], 0.0};
-      if (h->carla) {  // from the mean of the noisy rows' Frenet states (carla_rows)
+      if (h->carla && !tick) {  // from the mean of the noisy rows' Frenet states (carla_rows)
         std::memcpy(bx, &cb.bx[size_t(g) * 3], sizeof bx);
         std::memcpy(by, &cb.by[size_t(g) * 4], sizeof by);
       }
-      solve_columns(h->pc, pkx, pky, bx, by, sc.data() + size_t(g) * 4 * kNvar);
       initial_state(is, st0.data() + size_t(g) * 8);
-      obstacle_transpose(x_obs + size_t(g) * O * kNum, y_obs + size_t(g) * O * kNum, O, H,
-                         ob.data() + size_t(g) * 2 * O * H);
+      if (!tick) {  // the tick route: solve_c and obs are k_tick_setup's
+        solve_columns(h->pc, pkx, pky, bx, by, sc.data() + size_t(g) * 4 * kNvar);
+        obstacle_transpose(x_obs + size_t(g) * O * kNum, y_obs + size_t(g) * O * kNum, O, H,
+                           ob.data() + size_t(g) * 2 * O * H);
+      }
       initial_population(mean + size_t(g) * 8, cov + size_t(g) * 64, z0.data(), B, pop.data() + size_t(g) * B * 8);
     }
-    upload_staged(h, p.solve_c, sc.data(), sc.size() * 8);
+    if (!tick) upload_staged(h, p.solve_c, sc.data(), sc.size() * 8);
     if (h->carla) {
       // one staged copy per buffer whatever G is (the staging area holds each staged buffer once)
+      // (the tick route: k_tick_path and k_tick_setup write the three buffers)
       for (const CarlaBatch::Piece& piece : cb.staged()) {
+        if (tick) break;
         const std::string name(piece.buffer);
         const void* dst = name == "st0r" ? static_cast<const void*>(p.st0r)
                           : name == "path" ? static_cast<const void*>(p.path)
                                            : static_cast<const void*>(p.obs_full);
         upload_staged(h, dst, piece.image->data(), piece.image->size() * 4);
       }
-      p.P = path[0].num_path;
+      p.P = tick ? tick->num_path : path[0].num_path;
       if (cost_kind == MPCMMD_COST_DET) {  // the risks stay 0 (no risk stage)
         HIPC(hipMemsetAsync(p.obs_cost, 0, size_t(G) * B * 4, h->stream));
         HIPC(hipMemsetAsync(p.lane_cost, 0, size_t(G) * B * 4, h->stream));
@@ -189,7 +204,7 @@ int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t
       }
     }
     upload_staged(h, p.st0, st0.data(), st0.size() * 4);
-    upload_staged(h, p.obs, ob.data(), ob.size() * 4);
+    if (!tick) upload_staged(h, p.obs, ob.data(), ob.size() * 4);
     upload_staged(h, p.pop, pop.data(), pop.size() * 4);  // iteration 0's half: [0][G B][8]
     upload_staged(h, p.mean, mean, cfg_bytes(h, p.mean, G));
     upload_staged(h, p.cov, cov, cfg_bytes(h, p.cov, G));
@@ -228,6 +243,8 @@ int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t
     return MPCMMD_OK;
   });
 }
+
+namespace {
 
 // the result of configuration g (cem.py:324-333): the last enqueued iteration
 void read_result(mpcmmd_handle* h, int g, mpcmmd_result* out) {

@@ -192,4 +192,43 @@ void path_parameters(int P, const float* x, const float* y, float* Fxd, float* F
   if (arc_length) *arc_length = arc[P - 1];
 }
 
+const float* track_times() {
+  static const std::vector<float> tt = [] {
+    std::vector<float> v(100);
+    for (int k = 0; k < 100; ++k) v[k] = float(double(k) * (15.0 / 99.0));
+    v[99] = 15.0f;
+    return v;
+  }();
+  return tt.data();
+}
+
+void obstacle_tracks(const PathView& p, int O, const float* obstacles, float* x_obs, float* y_obs) {
+  const float* tt = track_times();
+  for (int o = 0; o < O; ++o) {
+    const float* q = obstacles + size_t(o) * 5;
+    const float v = std::sqrt(q[2] * q[2] + q[3] * q[3]);
+    const FrenetState f = global_to_frenet(p, q[0], q[1], v, 0.0f, q[4], 0.0f);
+    for (int k = 0; k < 100; ++k) {
+      x_obs[size_t(o) * 100 + k] = f.x + f.vx * tt[k];
+      y_obs[size_t(o) * 100 + k] = f.y + f.vy * tt[k];
+    }
+  }
+}
+
+void carla_tick_host(int P, int O, const float* x_wp, const float* y_wp, const float* obstacles, float thr,
+                     float* path6, float* x_obs, float* y_obs) {
+  float* x = path6;
+  float* y = path6 + size_t(P);
+  float* arc = path6 + size_t(2) * P;
+  float* Fxd = path6 + size_t(3) * P;
+  float* Fyd = path6 + size_t(4) * P;
+  float* kappa = path6 + size_t(5) * P;
+  std::vector<float> dd(size_t(2) * P);
+  path_smoothing(P, x_wp, y_wp, thr, x, y);
+  path_parameters(P, x, y, Fxd, Fyd, dd.data(), dd.data() + P, arc, kappa, nullptr);
+  PathView pv;
+  pv.P = P, pv.x = x, pv.y = y, pv.arc = arc, pv.Fxd = Fxd, pv.Fyd = Fyd, pv.kappa = kappa;
+  obstacle_tracks(pv, O, obstacles, x_obs, y_obs);
+}
+
 }  // namespace mpcmmd

@@ -44,4 +44,19 @@ void path_smoothing(int P, const float* x_wp, const float* y_wp, float threshold
 void path_parameters(int P, const float* x, const float* y, float* Fxd, float* Fyd, float* Fxdd, float* Fydd,
                      float* arc, float* kappa, float* arc_length);
 
+// np.linspace(0, 15, 100).astype(float32): the 100 plan times of an obstacle track
+const float* track_times();
+
+// Helper.global_to_frenet_obs_vmap + compute_obs_trajectories (C/opt/
+// cem_helper.py:171-200, 717-729) of O obstacles [O][5] = (x, y, vx, vy, psi):
+// v = sqrt(vx^2 + vy^2), vdot = psidot = 0, then the constant-velocity tracks
+// x_obs, y_obs [O][100] (one fp32 multiply and one fp32 add per point).
+void obstacle_tracks(const PathView& path, int O, const float* obstacles, float* x_obs, float* y_obs);
+
+// The preprocessing of one simulator tick (C/main_carla.py:364-376):
+// path_smoothing, path_parameters and obstacle_tracks.  path6 [6][P]: x, y,
+// arc_vec, Fx_dot, Fy_dot, kappa.
+void carla_tick_host(int P, int O, const float* x_wp, const float* y_wp, const float* obstacles, float threshold,
+                     float* path6, float* x_obs, float* y_obs);
+
 }  // namespace mpcmmd

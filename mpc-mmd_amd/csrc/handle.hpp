@@ -21,7 +21,7 @@ namespace mpcmmd {
   X(BSample, "bsample") X(BSelect, "bselect") X(BKernel, "bkernel") X(BQp, "bqp") X(BElite, "belite")            \
   X(MmdFinal, "mmdfinal") X(Select, "select") X(GammaTab, "gamma_tab") X(BetaPlanes, "beta_planes")              \
   X(BGen, "bgen") X(BMoment, "bmoment") X(BDirect, "bdirect") X(RollCarla, "roll_carla") X(Frenet, "frenet")     \
-  X(RiskCarla, "risk_carla") X(BcemSmall, "bcem_small")
+  X(RiskCarla, "risk_carla") X(BcemSmall, "bcem_small") X(TickPath, "tick_path") X(TickSetup, "tick_setup")
 enum KernelId {
 #define X(id, name) kK##id,
   MPCMMD_KERNELS(X)
@@ -181,5 +181,25 @@ inline void check_device(mpcmmd_handle* h) { HIPC(hipSetDevice(h->device)); }
 // Copy `bytes` at src into the buffer behind the Params member dst, from byte
 // `offset` on, on the handle's stream (handle.hip).  Throws past the buffer's end.
 void upload(mpcmmd_handle* h, const void* dst, const void* src, size_t bytes, size_t offset = 0);
+
+// host Philox normals of stream (stream, word1) with key (k0, k1): `count` values (begin.hip)
+std::vector<float> host_normals(uint32_t k0, uint32_t k1, uint32_t stream, uint32_t word1, size_t count);
+
+// The tick route of a begin (tick_api.hip): the device makes the path, the
+// obstacle tracks, the noisy rows and the KKT columns from the raw tick data.
+// begin_impl calls enqueue once, inside its guarded section, with the
+// init_eps normals of every configuration (eps[g] -> [R][4]).
+struct TickRoute {
+  int num_path;
+  void* ctx;
+  void (*enqueue)(void* ctx, int G, int cost_kind, int R, const float* const* eps);
+};
+
+// mpcmmd_begin for n_cfg configurations (begin.hip).  path: n_cfg paths (the
+// CARLA host route); tick: the CARLA tick route, which takes no path and no
+// obstacle tracks (x_obs, y_obs null) and no external draws.
+int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc, const float* init_state,
+               const float* mean, const float* cov, const float* x_obs, const float* y_obs, const float* v_des,
+               const mpcmmd_draws* draws, const mpcmmd_path* path = nullptr, const TickRoute* tick = nullptr);
 
 }  // namespace mpcmmd

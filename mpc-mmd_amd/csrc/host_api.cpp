@@ -86,6 +86,21 @@ int mpcmmd_global_to_frenet(const mpcmmd_path* path, int32_t count, const float*
   return MPCMMD_OK;
 }
 
+int mpcmmd_carla_tick_host(int32_t num_path, int32_t num_obs, const float init_state[6], const float* x_wp,
+                           const float* y_wp, const float* obstacles, float threshold, float* path6, float* x_obs,
+                           float* y_obs) {
+  if (num_path < 4 || num_path > kMaxPath) return fail(MPCMMD_E_INVALID, "tick: 4 <= num_path <= 2048");
+  if (num_obs < 0 || !init_state || !x_wp || !y_wp || !path6 || (num_obs > 0 && (!obstacles || !x_obs || !y_obs)))
+    return fail(MPCMMD_E_INVALID, "null argument");
+  if (!std::isfinite(threshold)) return fail(MPCMMD_E_INVALID, "tick: threshold must be finite");
+  try {
+    carla_tick_host(num_path, num_obs, x_wp, y_wp, obstacles, threshold, path6, x_obs, y_obs);
+    return MPCMMD_OK;
+  } catch (const std::exception& e) {
+    return fail(MPCMMD_E_INVALID, e.what());
+  }
+}
+
 int mpcmmd_host_constant(const mpcmmd_config* cfg, const char* name, double* dst, size_t count) {
   if (!cfg || !name) return fail(MPCMMD_E_INVALID, "null argument");
   try {

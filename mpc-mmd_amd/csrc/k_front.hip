@@ -23,6 +23,7 @@
 // work is fp32 in the reference's operation order (-ffp-contract=off).
 #include "common.hpp"
 #include "cost.hpp"
+#include "cr_math.hpp"
 #include "frenet.hpp"
 #include "kernels.hpp"
 
@@ -106,21 +107,6 @@ DEVI void unwrap2(float& a0, float& a1, int lane, bool v1) {
   }
   if (lane > 0) a0 = a0 + cs0;
   if (v1) a1 = a1 + cs1;
-}
-
-// Correctly rounded fp32 transcendentals (fp64 evaluation, one rounding).
-// The oracle does the same (oracle/helper.py: cr): feasible candidates'
-// res_norm is rounding noise, so reproducible transcendentals are what makes
-// the projection-elite order reproducible (DESIGN.md Numerics).
-DEVI float cr_atan2(float y, float x) { return float(atan2(double(y), double(x))); }
-DEVI float cr_sin(float a) { return float(sin(double(a))); }
-// cos and sin from one fp64 sincos (OCML: one argument reduction, the values
-// of cos and sin), each rounded once
-DEVI void cr_sincos(float a, float& s, float& c) {
-  double sd, cd;
-  sincos(double(a), &sd, &cd);
-  s = float(sd);
-  c = float(cd);
 }
 
 struct Polar {

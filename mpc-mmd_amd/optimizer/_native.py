@@ -30,7 +30,8 @@ SYMBOLS = (
     "mpcmmd_carla_begin", "mpcmmd_carla_solve", "mpcmmd_path_smoothing", "mpcmmd_path_parameters",
     "mpcmmd_global_to_frenet", "mpcmmd_set_graphs", "mpcmmd_handle_info", "mpcmmd_validate_carla",
     "mpcmmd_validate_risk", "mpcmmd_quantile_position", "mpcmmd_validate_carla_risk",
-    "mpcmmd_carla_begin_batch", "mpcmmd_carla_solve_batch",
+    "mpcmmd_carla_begin_batch", "mpcmmd_carla_solve_batch", "mpcmmd_tick_create", "mpcmmd_tick_destroy",
+    "mpcmmd_carla_tick_begin_batch", "mpcmmd_carla_tick_solve_batch", "mpcmmd_carla_tick_host",
 )
 
 
@@ -62,6 +63,12 @@ class Path(C.Structure):
                 ("Fy_dot", C.POINTER(C.c_float)), ("kappa", C.POINTER(C.c_float))]
 
 PATH_KEYS = ("x_path", "y_path", "arc_vec", "Fx_dot", "Fy_dot", "kappa")
+MAX_PATH = 2048   # kMaxPath: the stride of a path array in the handle's "path" buffer
+
+
+class TickInputs(C.Structure):
+    _fields_ = [("init_state", C.POINTER(C.c_float)), ("x_wp", C.POINTER(C.c_float)), ("y_wp", C.POINTER(C.c_float)),
+                ("obstacles", C.POINTER(C.c_float)), ("threshold", C.c_float)]
 
 
 class ValidateArgs(C.Structure):
@@ -184,6 +191,14 @@ def lib():
     if hasattr(L, "mpcmmd_carla_begin_batch"):   # an older library lacks them: carla_begin_batch raises
         L.mpcmmd_carla_begin_batch.argtypes = bargs + [C.POINTER(Path)]
         L.mpcmmd_carla_solve_batch.argtypes = bargs + [C.POINTER(Path), C.POINTER(Result)]
+    if hasattr(L, "mpcmmd_tick_create"):   # an older library lacks the tick route: Tick raises
+        targs = [vp, C.c_int32, C.c_int32, ip, C.POINTER(TickInputs), fp, fp, fp]
+        L.mpcmmd_tick_create.argtypes = [vp, C.c_int32, C.POINTER(vp)]
+        L.mpcmmd_tick_destroy.argtypes = [vp]
+        L.mpcmmd_tick_destroy.restype = None
+        L.mpcmmd_carla_tick_begin_batch.argtypes = targs
+        L.mpcmmd_carla_tick_solve_batch.argtypes = targs + [C.POINTER(Result)]
+        L.mpcmmd_carla_tick_host.argtypes = [C.c_int32, C.c_int32, fp, fp, fp, fp, C.c_float, fp, fp, fp]
     L.mpcmmd_path_smoothing.argtypes = [C.c_int32, fp, fp, C.c_float, fp, fp]
     L.mpcmmd_path_parameters.argtypes = [C.c_int32, fp, fp, fp, fp, fp, fp, fp, fp, fp]
     L.mpcmmd_global_to_frenet.argtypes = [C.POINTER(Path), C.c_int32, fp, fp, fp, fp, fp, fp, fp]
@@ -485,6 +500,102 @@ def global_to_frenet(path, x, y, v, vdot, psi, psidot):
     return tuple(out[:, k] for k in range(7))
 
 
+def carla_tick_host(init_state, x_wp, y_wp, obstacles, threshold=0.1):
+    """mpcmmd_carla_tick_host: the preprocessing of one simulator tick on the
+    host in one call (custom_path_smoothing, compute_path_parameters,
+    global_to_frenet_obs_vmap, compute_obs_trajectories).  x_wp, y_wp [P] the
+    waypoints shifted to the ego; obstacles [O, 5] = x, y (shifted), vx, vy,
+    psi.  Returns (path dict of PATH_KEYS, x_obs [O, 100], y_obs [O, 100])."""
+    L = lib()
+    if not hasattr(L, "mpcmmd_carla_tick_host"):
+        raise NativeError(f"{LIB_PATH} has no mpcmmd_carla_tick_host (built before the entry point existed): rebuild it")
+    f = lambda a: np.ascontiguousarray(np.asarray(a, np.float32))
+    st, xw, yw = f(init_state).reshape(6), f(x_wp).reshape(-1), f(y_wp).reshape(-1)
+    ob = f(obstacles).reshape(-1, 5)
+    P, O = xw.size, ob.shape[0]
+    if yw.size != P:
+        raise ValueError("x_wp and y_wp differ in length")
+    p6 = np.empty((6, P), np.float32)
+    xo = np.empty((O, 100), np.float32)
+    yo = np.empty((O, 100), np.float32)
+    check(L.mpcmmd_carla_tick_host(P, O, _fptr(st), _fptr(xw), _fptr(yw), _fptr(ob), float(threshold), _fptr(p6),
+                                   _fptr(xo), _fptr(yo)))
+    return dict(zip(PATH_KEYS, p6)), xo, yo
+
+
+class Tick:
+    """Owns one mpcmmd_tick: the tick route of ``handle`` for paths of
+    ``num_path`` points.  ``begin_batch`` / ``solve_batch`` take the raw data
+    of len(idx_mpc) ticks (init_state [G, 6], x_wp / y_wp [G, num_path],
+    obstacles [G, O, 5]) and do the whole per-tick setup on the handle's
+    stream; afterwards the handle's own iterate / finish_batch / read apply.
+    Close it before its handle."""
+
+    def __init__(self, handle, num_path):
+        self._L = lib()
+        if not hasattr(self._L, "mpcmmd_tick_create"):
+            raise NativeError(f"{LIB_PATH} has no mpcmmd_tick_create (built before the entry point existed): rebuild it")
+        self.handle = handle
+        self.num_path = int(num_path)
+        t = C.c_void_p()
+        check(self._L.mpcmmd_tick_create(handle._h, self.num_path, C.byref(t)))
+        self._t = t
+        self._keep = None
+        handle._ticks.append(self)   # Handle.close frees its tick contexts first
+
+    def close(self):
+        if getattr(self, "_t", None):
+            self._L.mpcmmd_tick_destroy(self._t)
+            self._t = None
+            if self in self.handle._ticks:
+                self.handle._ticks.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _args(self, cost, idx_mpc, init_state, x_wp, y_wp, obstacles, threshold, mean, cov, v_des):
+        h = self.handle
+        G = len(idx_mpc)
+        if G > h.max_configs:
+            raise ValueError(f"{G} ticks > max_configs {h.max_configs}")
+        f = lambda a, *sh: np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32), sh))
+        O, P = h.cfg.num_obs, self.num_path
+        ins = dict(idx=np.ascontiguousarray(np.asarray(idx_mpc, np.int64).astype(np.int32)),
+                   init=f(np.asarray(init_state, np.float32).reshape(G, 6), G, 6),
+                   xw=f(np.asarray(x_wp, np.float32).reshape(G, P), G, P),
+                   yw=f(np.asarray(y_wp, np.float32).reshape(G, P), G, P),
+                   ob=f(np.asarray(obstacles, np.float32).reshape(G, O, 5), G, O, 5),
+                   mean=f(mean, G, 8) if np.ndim(mean) == 2 else f(np.asarray(mean).reshape(8), G, 8),
+                   cov=f(np.asarray(cov, np.float32).reshape(-1, 64), G, 64),
+                   vd=f(np.asarray(v_des, np.float32).reshape(-1), G))
+        ins["tin"] = TickInputs(_fptr(ins["init"]), _fptr(ins["xw"]), _fptr(ins["yw"]), _fptr(ins["ob"]),
+                                float(threshold))
+        self._keep = ins
+        return G, (self._t, G, COST[cost], ins["idx"].ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ins["tin"]),
+                   _fptr(ins["mean"]), _fptr(ins["cov"]), _fptr(ins["vd"]))
+
+    def begin_batch(self, cost, idx_mpc, init_state, x_wp, y_wp, obstacles, threshold, mean, cov, v_des):
+        """mpcmmd_carla_tick_begin_batch (then the handle's iterate / finish_batch)."""
+        G, args = self._args(cost, idx_mpc, init_state, x_wp, y_wp, obstacles, threshold, mean, cov, v_des)
+        check(self._L.mpcmmd_carla_tick_begin_batch(*args))
+        self.handle._G = G
+
+    def solve_batch(self, cost, idx_mpc, init_state, x_wp, y_wp, obstacles, threshold, mean, cov, v_des):
+        """begin_batch, iterate(0, T), finish_batch: one result dict per tick,
+        bit-equal to ``Handle.carla_solve_batch`` on the host helpers' outputs."""
+        self.begin_batch(cost, idx_mpc, init_state, x_wp, y_wp, obstacles, threshold, mean, cov, v_des)
+        self.handle.iterate(0, self.handle.cfg.maxiter_cem)
+        return self.handle.finish_batch()
+
+    def path(self, g):
+        """The device-made path of tick g of the last begin: a dict of PATH_KEYS."""
+        img = self.handle.read("path").reshape(-1, 6, MAX_PATH)[g, :, :self.num_path]
+        return {k: img[i].copy() for i, k in enumerate(PATH_KEYS)}
+
+
 class Handle:
     """Owns one mpcmmd_handle (one device, one stream).  ``max_configs`` > 1
     sizes it for ``solve_batch`` (that many configurations per launch)."""
@@ -499,9 +610,12 @@ class Handle:
         check(self._L.mpcmmd_create_batch(C.byref(cfg), self.max_configs, C.byref(h)))
         self._h = h
         self._keep = []
+        self._ticks = []
 
     def close(self):
         if getattr(self, "_h", None):
+            for t in list(self._ticks):
+                t.close()
             self._L.mpcmmd_destroy(self._h)
             self._h = None
 
