@@ -139,7 +139,11 @@ const char* mpcmmd_last_error(void);
 int32_t mpcmmd_device_count(void);
 
 /* CEM.__init__: allocates every device buffer and uploads the
- * batch-invariant matrices.  No allocation happens after this. */
+ * batch-invariant matrices.  No allocation happens after this.
+ * MPCMMD_E_UNSUPPORTED for num_reduced > 1024, num_obs * num_prime > 8192, or
+ * (static / dynamic variants) a shape whose baseline risk stage needs more LDS
+ * per workgroup than the device has (never on an MI355X: the largest accepted
+ * shape needs 150 KiB of its 160). */
 int mpcmmd_create(const mpcmmd_config* cfg, mpcmmd_handle** out);
 void mpcmmd_destroy(mpcmmd_handle* h);
 

@@ -79,6 +79,17 @@ int mpcmmd_create_batch(const mpcmmd_config* cfg, int32_t max_configs, mpcmmd_ha
     HIPC(hipGetDeviceCount(&ndev));
     if (c.device < 0 || c.device >= ndev) throw std::invalid_argument("device ordinal out of range");
     HIPC(hipSetDevice(c.device));
+    // the baseline risk stage keeps 4 O H + 2 H + 3 S floats and S sort pairs in LDS: a
+    // shape the device cannot launch is refused here, not at the first risk stage
+    // (never on an MI355X: the largest accepted shape needs 150 KiB of its 160)
+    if (c.variant == MPCMMD_VARIANT_STATIC || c.variant == MPCMMD_VARIANT_DYNAMIC) {  // CARLA: its own risk kernels
+      int lds_max = 0;
+      HIPC(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c.device));
+      const size_t need = risk_lds_bytes(c.num_obs, c.num_prime, c.num_reduced);
+      if (need > size_t(lds_max))
+        return fail(MPCMMD_E_UNSUPPORTED, "the risk stage's workgroup needs " + std::to_string(need) +
+                                              " B of LDS, the device has " + std::to_string(lds_max));
+    }
     HIPC(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->own_stream = true;
     h->pc = build_constants(c.num_prime, c.variant);

@@ -105,7 +105,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8))) void k
   }
   __syncthreads();
   // each step's obstacles sorted by x (insertion sort, a thread per step);
-  // a NaN obstacle coordinate keeps the full scan for the whole candidate
+  // a NaN obstacle coordinate keeps the full scan for the whole candidate (there every
+  // sample's residual of that step is NaN, as np.maximum(0, NaN) is in the reference)
   constexpr int kWindowMaxObs = 64;  // above: the full scan (the sort is O^2 per step)
   bool any_nan = O > kWindowMaxObs;
   for (int h = threadIdx.x; h < H && O <= kWindowMaxObs; h += blockDim.x) {
@@ -131,7 +132,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8))) void k
   for (int r = threadIdx.x; r < S; r += blockDim.x) {
     float x = cf.st0[0], y = cf.st0[1], vx = cf.st0[2], vy = cf.st0[3], psi = cf.st0[4];
     float cb = 0.0f, lb = 0.0f, ub = 0.0f;
-    bool nan = false;
+    // fmaxf drops a NaN operand where jnp.maximum keeps it: a NaN residual (a NaN obstacle
+    // coordinate or rollout state) makes the sample's obstacle maximum NaN, a NaN y its lane
+    // bars; an obstacle's NaN never reaches the lane bars (compute_lane_bar reads y alone)
+    bool nan = false, nan_y = false;
     // the step's three noise values (gaussian: acc / steer / const normals,
     // beta: the two Beta draws and the const normal), the next step's loads
     // issued one step ahead so the scan does not wait on L2 every step
@@ -164,16 +168,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8))) void k
         }
       } else {
         for (int o = 0; o < O; ++o) {
-          const float xo = L.xo[o * H + h];
-          if (!(fabsf(x - xo) >= kObsA)) {
-            const float c = f_bar(x, y, xo, L.yo[o * H + h]);
+          const float xo = L.xo[o * H + h], yo = L.yo[o * H + h];
+          if (!(fabsf(x - xo) >= kObsA) || yo != yo) {  // a NaN coordinate is never skipped
+            const float c = f_bar(x, y, xo, yo);
             nan |= (c != c);
             cb = fmaxf(cb, c);
           }
         }
       }
       const float l1 = -y + p.y_lb, u1 = y - p.y_ub;
-      nan |= (y != y) | (x != x);
+      nan |= (x != x);
+      nan_y |= (y != y);
       lb = fmaxf(lb, l1);
       ub = fmaxf(ub, u1);
       if (h == H - 1) break;  // the last step's state is never recorded
@@ -185,9 +190,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8))) void k
       c0 = f0, c1 = f1, c2 = f2;
     }
     const float qnan = __int_as_float(0x7fc00000);
-    L.cbar[r] = nan ? qnan : cb;
-    L.lb[r] = nan ? qnan : lb;
-    L.ub[r] = nan ? qnan : ub;
+    L.cbar[r] = (nan || nan_y) ? qnan : cb;
+    L.lb[r] = nan_y ? qnan : lb;
+    L.ub[r] = nan_y ? qnan : ub;
   }
   __syncthreads();
   MPCMMD_STAMPW(p, 2);

@@ -197,6 +197,8 @@ void launch_front(const Params& p, int t, hipStream_t s);
 // (draws.hpp: kAheadNoise | kAheadGamma) in spare workgroups
 void launch_select(const Params& p, int t, hipStream_t s, int ahead_t = -1, int kind = 0);
 void launch_risk_baseline(const Params& p, int t, hipStream_t s);
+// k_risk_baseline's dynamic LDS per workgroup (mpcmmd_create_batch checks it against the device)
+size_t risk_lds_bytes(int O, int H, int S);
 
 // Monte-Carlo validation (k_validate.hip; S/validation.py:134-171)
 struct ValidateParams {

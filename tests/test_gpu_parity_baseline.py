@@ -91,10 +91,16 @@ def test_stage_lockstep(native, cost, noise):
 BETA_RTOL, BETA_ATOL = 1e-5, 3e-7
 
 
-def test_beta_planes(native, monkeypatch):
+# (B, S, H): the lockstep shape (one partial candidate group, one partial
+# chunk of 32 rows); candidate groups of 64 + 36, row chunks 32 + 32 + 1 and
+# H - 1 = 1 drawn step plus the dump step; 16 full chunks and one row
+@pytest.mark.parametrize("B,N_S,H", [(B, N_S, H), (100, 65, 2), (20, 513, 8)])
+def test_beta_planes(native, monkeypatch, B, N_S, H):
     """The Beta draws of the baseline rollouts (the planes k_risk_baseline's
     row lanes read) against the oracle's.  MPCMMD_BETA_DUMP makes the plane
-    kernel draw the last step too, which no rollout applies."""
+    kernel draw the last step too, which no rollout applies.  At every size
+    some elements are ones the fp32 path cannot decide, written by k_beta_fix
+    (bfix_n counts them per iteration)."""
     from oracle.rng import (STREAM_GAMMA_ACC_A, STREAM_GAMMA_ACC_B, STREAM_GAMMA_STEER_A, STREAM_GAMMA_STEER_B,
                             beta_draws, iteration_key)
     monkeypatch.setenv("MPCMMD_BETA_DUMP", "1")   # read when the handle is created
@@ -103,9 +109,11 @@ def test_beta_planes(native, monkeypatch):
     nat.begin("cvar", 123, DEFAULT_INIT, DEFAULT_MEAN, DEFAULT_COV, xo, yo, 15.0, draws)
     p = ora.prob
     worst = 0.0
+    fixed = 0
     for t in range(2):
         nat.run_stage(1, t)
         nat.run_stage(2, t)
+        fixed += int(nat.read("bfix_n", np.uint32)[0])
         acc = nat.read("acc").reshape(B, 100)[:, :H]
         steer = nat.read("steer").reshape(B, 100)[:, :H]
         planes = nat.read("bplane", np.float32, (B, 2, H, N_S))
@@ -123,7 +131,8 @@ def test_beta_planes(native, monkeypatch):
             assert np.all(err <= lim), f"beta plane {k} t={t}: {int((err > lim).sum())} outside, worst {err.max():.3g}"
             worst = max(worst, float((err / np.maximum(np.abs(ref), 1e-30)).max()))
         nat.run_stage(3, t)
-    print(f"Beta draws: worst relative difference {worst:.3g}")
+    print(f"Beta draws: worst relative difference {worst:.3g}; {fixed} of {2 * B * H * N_S} elements through k_beta_fix")
+    assert 1 <= fixed <= 2 * B * H * N_S, f"{fixed} elements went through k_beta_fix"
 
 
 def run_iteration_lockstep(native, cost, noise, Tf=20, n=N_S, B=B, H=H, O=O, seed=7, idx=5):
