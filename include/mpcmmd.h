@@ -177,6 +177,8 @@ int32_t mpcmmd_max_configs(mpcmmd_handle* h);
  *   "fused_small"  1: small batches run the 20 beta-iterations as one launch
  *                  (k_bcem_small; same bits as the per-iteration kernels)
  *   "groups"       beta-CEM candidate groups on their own streams (same bits)
+ *   "ker_path"     MPCMMD_KER_PATH as read at create: how k_bkernel forms K_red
+ *                  (0 table or gather by union size, 1 union image, 2 gather; same bits)
  *   "capacity"     max_configs * num_batch
  * Writes *value; MPCMMD_E_INVALID for an unknown name. */
 int mpcmmd_handle_info(mpcmmd_handle* h, const char* name, int64_t* value);

@@ -147,7 +147,8 @@ struct LdsTake {  // consecutive 16-byte aligned LDS pieces
 // staged), -log2 e / sigma, 1 / sigma, the entry table (k | kk << 8), union
 // rank of a row, row of a rank; scratch (`scratch` bytes, chosen at launch):
 // the union flags, then the union's series records, then the distance table
-// and the union's feature rows, or the waves' per-sample feature rows
+// and the union's feature rows, or the waves' per-sample feature rows (or
+// the union's feature rows alone: MPCMMD_KER_PATH=1)
 struct KerLds {
   size_t sel, csg, csd, tri, urank, urow, misc, scratch, total;
 };
@@ -165,20 +166,39 @@ HDI KerLds ker_lds(int M, int n, size_t scratch) {
   L.total = take.o;
   return L;
 }
-HDI size_t ker_sample_bytes(int n) { return size_t(kKerWaves) * n * kFeatStride * 4; }
+// floats per feature row staged for K_red outside the table (the waves'
+// per-sample slices, the union image): 7 float4s, not kFeatStride's 6.  A
+// ds_read_b128 is served per 16-lane group from sixteen 16-byte bank slots; the
+// lanes of a group read rows kk, kk + 1, .. of the slice, and at an odd pitch
+// those start in distinct slots (at 6 float4s rows kk and kk + 8 share one: every
+// second-row read ran 2-way conflicted)
+constexpr int kKerRowPitch = 28;
+HDI size_t ker_sample_bytes(int n) { return size_t(kKerWaves) * n * kKerRowPitch * 4; }
 HDI size_t ker_tab_bytes(int U) { return ((size_t(U) * (U - 1) / 2 * 4 + 15) & ~size_t(15)) + size_t(U) * kFeatStride * 4; }
-constexpr size_t kKerTabBytes = 55 * 1024;  // the table of a union of <= 144 rows
+// the union table's LDS budget: what two workgroups per CU (160 KB, less
+// allocation slack) leave after the persistent pieces, between 55 KB (unions
+// of <= 144 rows; every size gets it, as before) and 71 KB (<= 165 rows: n = 22,
+// where 64% of the candidates of beta-iteration 4 have 145..165 rows)
+constexpr size_t kKerTabBytes = 55 * 1024, kKerTabMax = 71 * 1024, kKerHalfLds = 79 * 1024;
+HDI size_t ker_tab_budget(int M, int n) {
+  const size_t fixed = ker_lds(M, n, 0).total;
+  const size_t left = kKerHalfLds > fixed ? (kKerHalfLds - fixed) & ~size_t(15) : 0;
+  return left < kKerTabBytes ? kKerTabBytes : (left > kKerTabMax ? kKerTabMax : left);
+}
 // scratch: the series records of every mother row (up to kKerRecBytes;
-// larger unions read them from global memory), and the union table (up to
-// kKerTabBytes) from the second beta-iteration on (the first one's 100 fresh
-// samples select nearly every mother row)
+// larger unions read them from global memory), and the union table (its
+// budget) from the second beta-iteration on (the first one's 100 fresh
+// samples select nearly every mother row).  MPCMMD_KER_PATH=1 launches the
+// first iteration with that size too, for the image of its union.  `tab`:
+// k_bkernel passes ker_tab_budget; k_bcem_small keeps the 55 KB (the larger
+// budget cost CARLA n = 10 1% in three of three alternated runs)
 constexpr size_t kKerRecBytes = 64 * 1024;
-HDI size_t ker_scratch(int M, int n, int tb) {
+HDI size_t ker_scratch(int M, int n, int tb, size_t tab = kKerTabBytes) {
   size_t sc = ker_sample_bytes(n);
   size_t rec = size_t(M) * kMomStride * 4;
   if (rec > kKerRecBytes) rec = kKerRecBytes;
   if (rec > sc) sc = rec;
-  if (tb > 0 && kKerTabBytes > sc) sc = kKerTabBytes;
+  if (tb > 0 && tab > sc) sc = tab;
   return sc;
 }
 

@@ -21,8 +21,11 @@
 //            rows b < a as LDS broadcasts) and each sample's entries are
 //            exponentials of table lookups (a wave per sample, the lookups of
 //            all its entries in flight together); otherwise a wave per sample
-//            stages its n feature rows in LDS and forms its n (n - 1) / 2
-//            distances, one lane per entry.
+//            stages its n feature rows in LDS (rows kKerRowPitch floats apart:
+//            conflict-free reads) and forms its n (n - 1) / 2 distances, one
+//            lane per entry.  Params::ker_path (MPCMMD_KER_PATH; tests, A/B
+//            timing) forces the gather, or a third path: the union's feature
+//            rows staged once per workgroup, each entry from two of them.
 // k_bdirect, workgroup = (candidate, part of its rows), only when a candidate
 // has flagged pairs (a > 1: mostly the first beta-iteration, whose samples
 // clipped to sigma = 0.01 have a ~ 100): the flagged pairs counting-sorted by
@@ -60,6 +63,24 @@ DEVI float series_sum(const float4 (&q)[3], double na) {
   return float(double(__builtin_amdgcn_exp2f(float(na * kLog2e))) * h);
 }
 static_assert(kMomR == 12 && kMom == 12, "record layout: P_0..P_11 in float4s 0..2, R in float4 3");
+
+// L1 distance of two feature rows (LDS) in k_bdist's order: features 0..21,
+// one sequential fp32 sum (22, 23 are padding)
+DEVI float feat_l1(const float4* A, const float4* Bv) {
+  constexpr int Q = kFeatStride / 4;
+  float dd = 0.0f;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const float4 x = A[q], y = Bv[q];
+    dd = q == 0 ? fabsf(x.x - y.x) : dd + fabsf(x.x - y.x);
+    dd = dd + fabsf(x.y - y.y);
+    if (q < Q - 1) {
+      dd = dd + fabsf(x.z - y.z);
+      dd = dd + fabsf(x.w - y.w);
+    }
+  }
+  return dd;
+}
 
 // The body of k_bkernel for part `part` of candidate `cand` (of `split`),
 // kKerWaves waves (k_bkernel and the small-batch fused kernel k_bcem_small).
@@ -181,7 +202,16 @@ DEVI void bkernel_body(const Params& p, int tb, int cand, int part, int split, i
   MPCMMD_STAMPW(p, 2);
   const float4* fg = feat_l ? feat_l : reinterpret_cast<const float4*>(p.featr + size_t(b) * M * kFeatStride);
   float* kbase = p.bkred + size_t(b) * kBetaSamples * ntri;
-  if (ker_tab_bytes(Uu) <= size_t(scratch)) {  // block-uniform
+  // block-uniform.  Params::ker_path 0: the table when it fits, else the
+  // per-sample gather; 1: the union image when it fits, else the gather (never
+  // the table); 2: the gather.  The image is not a default path: at n = 22 its
+  // two random rows per entry conflict in the LDS banks more than the gather's
+  // compact slice and it measured slower; it is kept as the
+  // third way to the same bits that tests/test_gpu_kred_paths.py compares
+  constexpr int Qr = kKerRowPitch / 4;
+  const bool table = p.ker_path == 0 && ker_tab_bytes(Uu) <= size_t(scratch);
+  const bool image = p.ker_path == 1 && size_t(Uu) * kKerRowPitch * 4 <= size_t(scratch);
+  if (table) {
     float* T = reinterpret_cast<float*>(smem + C.scratch);
     float4* Fu = reinterpret_cast<float4*>(smem + C.scratch + ((size_t(Uu) * (Uu - 1) / 2 * 4 + 15) & ~size_t(15)));
     for (int i = tid; i < Uu * Q; i += NT) {
@@ -298,33 +328,54 @@ DEVI void bkernel_body(const Params& p, int tb, int cand, int part, int split, i
         }
       }
     }
+  } else if (image) {
+    // the union's feature rows once per workgroup (the union records are
+    // dead); sl holds union ranks, so entry (k, kk) of sample s reads rows
+    // sl[s n + k] and sl[s n + kk] of the image.  A wave's samples are
+    // independent: nothing is staged per sample, no wave_sync between them
+    float4* Fu = reinterpret_cast<float4*>(smem + C.scratch);
+    constexpr int kJ = 3;  // 478 rows (n = 22, first beta-iteration): 2868 float4s, 3 per thread in flight
+    for (int i0 = tid; i0 < Uu * Q; i0 += NT * kJ) {
+      float4 v[kJ];
+#pragma unroll
+      for (int j = 0; j < kJ; ++j) {
+        const int i = min(i0 + NT * j, Uu * Q - 1), u = i / Q;
+        v[j] = fg[size_t(urow[u]) * Q + (i - u * Q)];
+      }
+#pragma unroll
+      for (int j = 0; j < kJ; ++j)
+        if (i0 + NT * j < Uu * Q) {
+          const int i = i0 + NT * j, u = i / Q;
+          Fu[u * Qr + (i - u * Q)] = v[j];
+        }
+    }
+    __syncthreads();
+    MPCMMD_STAMPW(p, 3);
+    for (int s = s_lo + part + split * w; s < kBetaSamples; s += split * kKerWaves) {
+      const short* su = sl + s * n;
+      const float cs = csg[s];
+      float* kr = kbase + size_t(s) * ntri;
+      for (int e = lane; e < nent; e += 64) {
+        const int kk2 = tri[e];
+        const float dd = feat_l1(Fu + su[kk2 & 0xFF] * Qr, Fu + su[kk2 >> 8] * Qr);
+        kr[e] = __builtin_amdgcn_exp2f(dd * cs);
+      }
+    }
   } else {
     // per-sample: the union records are dead, sl holds union ranks (urow maps back)
-    float4* Fw = reinterpret_cast<float4*>(smem + C.scratch) + size_t(w) * n * Q;
+    float4* Fw = reinterpret_cast<float4*>(smem + C.scratch) + size_t(w) * n * Qr;
     for (int s = s_lo + part + split * w; s < kBetaSamples; s += split * kKerWaves) {
       for (int k = lane; k < n; k += 64) {
         const float4* src = fg + size_t(urow[sl[s * n + k]]) * Q;
 #pragma unroll
-        for (int q = 0; q < Q; ++q) Fw[k * Q + q] = src[q];
+        for (int q = 0; q < Q; ++q) Fw[k * Qr + q] = src[q];
       }
       wave_sync();  // one wave's LDS operations run in order
       const float cs = csg[s];
       float* kr = kbase + size_t(s) * ntri;
       for (int e = lane; e < nent; e += 64) {
         const int kk2 = tri[e];
-        const float4* A = Fw + (kk2 & 0xFF) * Q;
-        const float4* Bv = Fw + (kk2 >> 8) * Q;
-        float dd = 0.0f;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-          const float4 x = A[q], y = Bv[q];
-          dd = q == 0 ? fabsf(x.x - y.x) : dd + fabsf(x.x - y.x);
-          dd = dd + fabsf(x.y - y.y);
-          if (q < Q - 1) {  // features 22, 23 are padding
-            dd = dd + fabsf(x.z - y.z);
-            dd = dd + fabsf(x.w - y.w);
-          }
-        }
+        const float dd = feat_l1(Fw + (kk2 & 0xFF) * Qr, Fw + (kk2 >> 8) * Qr);
         kr[e] = __builtin_amdgcn_exp2f(dd * cs);
       }
       wave_sync();  // the reads are done before the next sample's rows overwrite them

@@ -189,6 +189,7 @@ int mpcmmd_create_batch(const mpcmmd_config* cfg, int32_t max_configs, mpcmmd_ha
     // parts per candidate only below 128 candidates per launch (B = 100: 8 -> 2 parts)
     p.ker_target = env_clamped("MPCMMD_KER_TARGET", 128, 1, kNoMax);
     p.dir_target = env_clamped("MPCMMD_DIR_TARGET", 2048, 1, kNoMax);
+    p.ker_path = env_clamped("MPCMMD_KER_PATH", 0, 0, 2);
     p.beta_dump = env_flag("MPCMMD_BETA_DUMP", p.beta_dump != 0);
     h->groups = env_clamped("MPCMMD_GROUPS", h->groups, 1, kMaxG);
     if (h->groups > 1) {
@@ -276,6 +277,7 @@ int mpcmmd_handle_info(mpcmmd_handle* h, const char* name, int64_t* value) {
   else if (k == "select_prep") *value = h->prep_on && !h->carla ? 1 : 0;
   else if (k == "fused_small") *value = h->fused_small ? 1 : 0;
   else if (k == "groups") *value = h->groups;
+  else if (k == "ker_path") *value = h->p.ker_path;
   else if (k == "capacity") *value = int64_t(h->Gmax) * h->B;
   else return fail(MPCMMD_E_INVALID, "unknown handle_info name " + k);
   return MPCMMD_OK;

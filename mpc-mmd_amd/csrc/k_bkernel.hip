@@ -52,7 +52,7 @@ bool mmdopt_supported(int n, int H, int O, std::string* why) {
     if (why) *why = "mmd_opt needs num_reduced <= 64";
     return false;
   }
-  if (dir_lds(M, n).total > kLdsBudget || ker_lds(M, n, ker_scratch(M, n, 1)).total > kLdsBudget) {
+  if (dir_lds(M, n).total > kLdsBudget || ker_lds(M, n, ker_scratch(M, n, 1, ker_tab_budget(M, n))).total > kLdsBudget) {
     if (why) *why = "mmd_opt: num_reduced^2 too large for the kernel-sum stage";
     return false;
   }
@@ -80,7 +80,7 @@ int ker_split(int nb, int target) {
 bool use_pairs(const Params& p) { return p.dir_pairs && p.nb <= 256; }
 
 void launch_bkernel(const Params& p, int tb, hipStream_t s) {
-  const size_t sc = ker_scratch(p.M, p.n, tb);
+  const size_t sc = ker_scratch(p.M, p.n, p.ker_path == 1 ? 1 : tb, ker_tab_budget(p.M, p.n));
   const dim3 grid(p.nb * ker_split(p.nb, p.ker_target)), block(64 * kKerWaves);
   const size_t lds = ker_lds(p.M, p.n, sc).total;
   if (use_pairs(p))

@@ -54,6 +54,9 @@ struct Params {
   int32_t sel_cap;         // k_bselect: at most this many single-wave workgroups per candidate (default 64)
   int32_t ker_target;      // k_bkernel parts: enough for this many workgroups per launch (default 128)
   int32_t dir_target;      // k_bdirect parts: enough for this many workgroups per launch (default 2048)
+  int32_t ker_path;        // k_bkernel's K_red (MPCMMD_KER_PATH; tests, A/B timing): 0 the union table when it fits,
+                           // else the per-sample gather; 1: an LDS image of the union's feature rows when it fits,
+                           // else the gather; 2: the gather always.  Same bits
   int32_t mom_rows;        // 1 (default): k_bmoment_rows (16 lanes per distance row, 4 rows per wave); 0: a wave
                            // per row (MPCMMD_MOM_ROWS=0)
   double mom_amax;         // k_bmoment's first-iteration direct test a > mom_amax: kSeriesAMax (1.0), k_bkernel's;

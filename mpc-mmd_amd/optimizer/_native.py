@@ -808,7 +808,7 @@ class Handle:
 
     def info(self, name):
         """mpcmmd_handle_info: the handle's implementation choices ("gen_wave",
-        "select_prep", "fused_small", "groups", "capacity")."""
+        "select_prep", "fused_small", "groups", "ker_path", "capacity")."""
         v = C.c_int64()
         check(self._L.mpcmmd_handle_info(self._h, name.encode(), C.byref(v)))
         return v.value
