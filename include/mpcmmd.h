@@ -691,6 +691,154 @@ int mpcmmd_validate_carla_risk(const mpcmmd_validate_carla_risk_args* args);
  * quantile = v[lo] w_lo + v[hi] w_hi.  Host only, no GPU needed. */
 int mpcmmd_quantile_position(int32_t n, float alpha, int32_t* lo, int32_t* hi, float* w_lo, float* w_hi);
 
+/* ---- Surrogate world of a closed CARLA loop ----------------------------------
+ * One step of the world model of DESIGN.md section 19 (a model of this
+ * library's, not CARLA physics): from the plan of tick k (cx, cy and the first
+ * four steerings of a CARLA result) to the raw inputs of tick k + 1 as
+ * mpcmmd_tick_inputs carries them, plus the first population of that tick's
+ * CEM and one log row.  Controller (main_carla.py:408-413), perturbation
+ * (:415-436) from four given variates, bicycle step (compute_rollout_one_step
+ * with the world's dt), constant-velocity vehicles, the flags, the waypoints
+ * (waypoint_generator) and the nearest obstacles (compute_obs_data).  fp32 in
+ * the order DESIGN.md states, transcendentals evaluated in fp64 and rounded
+ * once, positions, distances and the spline in fp64.
+ *
+ * The variates u[4] are given, or drawn where the controls are known (u NULL):
+ * Philox streams keyed (episode key, seed) at stream ids 40..44 (csrc/rng.hpp),
+ * element = tick.  gaussian: u0, u2, u3 = normals 0, 2, 3 of block `tick` of
+ * stream 40.  beta: u0 ~ Beta(2|a_c|, 5|a_c|) (streams 41, 42), u1 ~
+ * Beta(2|s_c|, 5|s_c|) (43, 44) by the validators' fp64 sampler, with its
+ * |control| = 0 limit rule (DESIGN.md Numerics), rounded once; u2, u3 as above.
+ * The log row holds the variates used.
+ *
+ * mpcmmd_world_step_host steps one episode on the host (no GPU needed).
+ * mpcmmd_world_step_device steps n_episodes independent episodes with one
+ * launch of k_world_step (one workgroup per episode, k_world.hip) on device
+ * `device`, every array with a leading episode axis; each episode's outputs
+ * are bit-equal to the host step's (tests/test_gpu_world.py).  It uploads and
+ * reads back every array, so it is the kernel's reference harness, not a fast
+ * path: that is the world context below.  ABI version unchanged: detect the
+ * entry points by their symbols.
+ *
+ * Before any HIP call: MPCMMD_E_INVALID for a NULL argument or array,
+ * num_path outside 2..2048, num_obs outside 1..64, total_obs outside 0..64,
+ * num_route < 2, goal_index outside 0..num_route-1, num_batch < 1, a noise
+ * other than 0 / 1, n_episodes < 1. */
+typedef struct mpcmmd_world_model {
+  int32_t num_path;   /* waypoints per tick */
+  int32_t num_obs;    /* obstacles the optimizer sees */
+  int32_t total_obs;  /* vehicles in the world, 0..64 */
+  int32_t num_route;  /* points of the (extended) route */
+  int32_t goal_index; /* route point whose 7 m neighbourhood is the goal (len_path - 1, main_carla.py:329) */
+  int32_t num_batch;  /* rows of the first population */
+  int32_t noise;      /* 0 gaussian, 1 beta (u[0], u[1] are then Beta variates) */
+  float dt;           /* tick length (replay: 0.05) */
+  float sigma_acc, sigma_steer, acc_const, steer_const; /* the driver's noise model */
+  float steer_max;    /* 0.6 */
+  float a_obs, b_obs; /* half axes of the keep-out ellipse (4.5, 3) */
+  float y_lb, y_ub;   /* lane bounds of the signed lateral offset */
+  const double* route_x;   /* [num_route] */
+  const double* route_y;
+  const double* route_arc; /* [num_route] the splines' breakpoints, strictly increasing */
+  const double* spline_x;  /* [4][num_route-1]: scipy CubicSpline(route_arc, route_x).c */
+  const double* spline_y;
+  const double* pdot4;     /* [4][11]: rows 0..3 of Pdot (mpcmmd_host_constant) */
+  const double* chol;      /* [8][8] lower Cholesky factor of the run's covariance, row-major */
+  const float* pop0;       /* [num_batch][8] standard normals of the first population */
+  uint32_t seed;           /* key word 1 of the drawn variates' Philox streams (the world context: the handle's) */
+} mpcmmd_world_model;
+
+#define MPCMMD_WORLD_LOG_D 3  /* x, y (global, after the step), arc of the closest route point */
+#define MPCMMD_WORLD_LOG_F 13 /* v, psi, psidot, a_c, s_c, a, s, u[4], clear, d */
+#define MPCMMD_WORLD_LOG_I 4  /* idx, lane_out, collided, goal */
+
+typedef struct mpcmmd_world_step_io { /* leading axis n_episodes for the device step */
+  /* the plan and the variates of this tick */
+  const float* cx;    /* [11] */
+  const float* cy;    /* [11] */
+  const float* steer; /* [4] the plan's first four steerings */
+  const float* u;     /* [4] the variates, or NULL: drawn from (key, seed, tick) once a_c and s_c are known */
+  const float* mean;  /* [8] mean_param as the solve left it */
+  /* the episode's state, updated in place unless it is frozen */
+  double* pos;        /* [2] global x, y */
+  float* ego;         /* [3] v, psi, psidot */
+  float* vehicles;    /* [total_obs][5] x, y, vx, vy, psi */
+  int32_t* done_tick; /* [1] -1 while the episode runs; the tick that set collided or goal */
+  /* the next tick */
+  float* init_state;  /* [6] */
+  float* x_wp;        /* [num_path] */
+  float* y_wp;
+  float* obstacles;   /* [num_obs][5] */
+  float* pop;         /* [num_batch][8] */
+  /* the log row */
+  double* log_d;      /* [MPCMMD_WORLD_LOG_D] */
+  float* log_f;       /* [MPCMMD_WORLD_LOG_F] */
+  int32_t* log_i;     /* [MPCMMD_WORLD_LOG_I] */
+  const uint32_t* key; /* [1] the episode's key; needed when u is NULL */
+} mpcmmd_world_step_io;
+
+int mpcmmd_world_step_host(const mpcmmd_world_model* m, int32_t tick, const mpcmmd_world_step_io* io);
+int mpcmmd_world_step_device(const mpcmmd_world_model* m, int32_t device, int32_t n_episodes, int32_t tick,
+                             const mpcmmd_world_step_io* io);
+
+/* The chained route: E <= max_configs closed-loop episodes on a tick context's
+ * handle with nothing crossing the host between two solves.  A world context
+ * belongs to one tick context (its num_path and its handle's num_obs must be
+ * the model's; num_batch, chol and pop0 of the model are not read: the
+ * population is the handle's, from its own pop0 normals and the Cholesky
+ * factor of the covariance given at reset).  It owns its device memory (route,
+ * spline pieces, the episodes' state, the variates, the log); none of it is in
+ * the handle's buffer list.  Destroy it before its tick context.
+ *
+ * mpcmmd_world_reset uploads the episodes' start states (pos [E][2], ego
+ * [E][3] = v, psi, psidot, vehicles [E][total_obs][5]), their means [E][8]
+ * (into the handle's mean), the run's covariance [64] (factored on the host as
+ * initial_population factors it), the episodes' keys [E] and the variates u
+ * [max_ticks][E][4] -- or u NULL: k_world_step then draws each tick's variates
+ * itself from (keys[e], the handle's seed, tick), after that tick's solve, which
+ * is what Beta noise needs (its parameters are the controls) -- and
+ * enqueues one k_world_step in reset mode, which writes tick 0's raw inputs
+ * into the tick context's input image, the handle's st0 and iteration 0's
+ * population from the start states.  Episode e solves tick k with idx_mpc =
+ * k + keys[e].
+ *
+ * mpcmmd_world_run enqueues, for each tick of [tick_begin, tick_begin +
+ * count): the chained begin (begin_impl through the tick route with the raw
+ * inputs, st0, the population and the mean already on the device: idx_mpc,
+ * v_des [E], cov and the init_eps normals are still staged), the T CEM
+ * iterations, and k_world_step, which reads the plan from the handle's result
+ * buffers (results, res_steer, mean) and writes the next tick's inputs where
+ * the next begin finds them.  No device-to-host copy and no stream
+ * synchronisation inside the loop beyond the staging-event waits every begin
+ * makes; begin k + 1 waits for begin k's staging event, which lies behind tick
+ * k - 1's solve and step in the stream, so the host runs at most about one
+ * tick ahead of the device.  Ticks run in order; a run may be split (run(0, 3) then run(3, 3)).
+ * After a run the handle holds the last tick's solve (mpcmmd_finish_batch,
+ * mpcmmd_read(h, "path")).
+ *
+ * mpcmmd_world_log synchronises and reads back the first `ticks` rows: log_d
+ * [ticks][E][3], log_f [ticks][E][13], log_i [ticks][E][4], plan
+ * [ticks][E][34] (cx, cy, the first four steerings and mean_param of the solve
+ * the step consumed) and done_tick [E].  Every row equals the host-stepped
+ * loop's (mpcmmd_carla_tick_solve_batch + mpcmmd_world_step_host) bit for bit
+ * (tests/test_gpu_closed_loop.py).
+ *
+ * Before any HIP call: MPCMMD_E_INVALID for NULL arguments, a model out of
+ * range or not matching the tick context, n_episodes outside 1..max_configs,
+ * a covariance that is not positive definite, a tick range outside
+ * [0, max_ticks]; MPCMMD_E_STATE for a run before a reset; then the tick
+ * begin's own errors. */
+typedef struct mpcmmd_world mpcmmd_world;
+int mpcmmd_world_create(mpcmmd_tick* t, const mpcmmd_world_model* m, int32_t max_ticks, mpcmmd_world** out);
+void mpcmmd_world_destroy(mpcmmd_world* w);
+int mpcmmd_world_reset(mpcmmd_world* w, int32_t n_episodes, const double* pos, const float* ego,
+                       const float* vehicles, const float* mean, const float* cov, const float* u,
+                       const int32_t* keys);
+int mpcmmd_world_run(mpcmmd_world* w, int32_t cost_kind, int32_t tick_begin, int32_t count, const float* cov,
+                     const float* v_des, float threshold);
+int mpcmmd_world_log(mpcmmd_world* w, int32_t ticks, double* log_d, float* log_f, int32_t* log_i, float* plan,
+                     int32_t* done_tick);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,166 @@
+"""Closed-loop CARLA episodes on the surrogate world.
+
+The reference's CARLA experiment is closed-loop (``carla/main_carla.py:
+329-457``): each tick the plan's first controls are averaged, perturbed by the
+noise model and applied, the ego moves, and the next tick is solved from where
+it ended up.  Here the simulator is replaced by a world model of this
+project's (a kinematic bicycle, constant-velocity vehicles, the route's
+splines), and E independent episodes run in lockstep on one CARLA batch handle.
+By default the whole loop is enqueued on the GPU (mpcmmd_world_run: per tick the
+chained begin, the CEM iterations and k_world_step, nothing crossing the host,
+one readback of the log at the end).  With ``--host-step`` each tick is one
+batched solve through the tick route (mpcmmd_carla_tick_solve_batch) and one
+host step (mpcmmd_world_step_host); the files are equal.
+
+    cd mpc-mmd_amd/carla
+    python -m closed_loop --synthetic --episodes 8 --ticks 200 --costs cvar det --out stats
+
+The synthetic route and spawns are those of ``replay.py``.  Episodes differ by
+their key (the solver's streams and the perturbation's variates, which the
+library draws after each tick's solve, normals or Beta(2 |control|, 5 |control|)
+with ``--noise beta``) and, with
+``--start-spread S``, by a start offset of up to S m along the route.  Per cost
+``closed_loop_<cost>.npz`` holds the log arrays ``log_d`` [T, E, 3] (x, y, arc),
+``log_f`` [T, E, 13] (v, psi, psidot, a_c, s_c, a, s, u[4], clear, d), ``log_i``
+[T, E, 4] (idx, lane_out, collided, goal) and ``done_tick``, ``collided``,
+``goal`` [E]; one line per cost gives the collision share, the mean minimum
+-clear, the lane-departure share and the mean progress, each as mean +- sample
+standard deviation over the episodes.
+
+The episode runner is a parameter of ``closed_loop`` (``run=``), so the
+accounting is testable without a GPU.
+"""
+from __future__ import annotations
+
+import argparse
+import importlib.util
+import os
+import sys
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+COSTS = ("mmd", "cvar", "det")
+V_DES = 10.0
+LOG_KEYS = ("log_d", "log_f", "log_i", "done_tick", "collided", "goal")
+
+
+def _replay():
+    name = "mpcmmd_carla_replay"
+    if name not in sys.modules:
+        spec = importlib.util.spec_from_file_location(name, os.path.join(_HERE, "replay.py"))
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules[name] = mod
+        spec.loader.exec_module(mod)
+    return sys.modules[name]
+
+
+def synthetic_world(town="Town05"):
+    """The route and spawns of ``replay.record_synthetic``: ((x, y) of the
+    extended route, goal_index = len_path - 1, vehicles [total_obs, 5])."""
+    R = _replay()
+    offs, lanes = R.SPAWN["Town10HD" if town.startswith("Town10") else "Town05"]
+    rx, ry = R.synthetic_route()
+    rt = R.Route(rx, ry)
+    ox, oy, opsi = rt.at(offs.copy(), np.array([lanes[i % 2] for i in range(offs.size)]))
+    vehicles = np.zeros((offs.size, 5), np.float32)
+    vehicles[:, 0], vehicles[:, 1], vehicles[:, 4] = ox, oy, np.arctan2(np.sin(opsi), np.cos(opsi))
+    return R.extend_route(rx, ry), rx.size - 1, vehicles
+
+
+def synthetic_starts(route, episodes, spread=0.0, v0=0.1):
+    """[E, 4] = x, y, v, psi: on the route, episode e ``spread`` e / E m along it, heading along it."""
+    R = _replay()
+    rt = R.Route(*route)
+    s = spread * np.arange(episodes) / max(episodes, 1)
+    x, y, psi = rt.at(s)
+    return np.stack([x, y, np.full(episodes, v0), np.arctan2(np.sin(psi), np.cos(psi))], 1)
+
+
+def _run(prob, cost, route, goal_index, vehicles, starts, ticks, **kw):
+    return prob.run_episodes(cost, route, vehicles, starts, ticks, goal_index=goal_index, **kw)
+
+
+def _mean_std(v):
+    v = np.asarray(v, np.float64)
+    return float(v.mean()) if v.size else 0.0, float(v.std(ddof=1)) if v.size > 1 else 0.0
+
+
+def summarise(res):
+    """The four figures of one cost's episodes, each (mean, sample sd) over the
+    episodes.  Rows after an episode's ``done_tick`` repeat its frozen state and
+    are left out."""
+    log_f, log_i, log_d = res["log_f"], res["log_i"], res["log_d"]
+    T, E = log_i.shape[:2]
+    done = np.asarray(res["done_tick"])
+    last = np.where(done >= 0, done, T - 1)
+    live = np.arange(T)[:, None] <= last[None, :]
+    neg_clear = np.where(live, -log_f[:, :, 11].astype(np.float64), np.inf)
+    return dict(collision=_mean_std(np.asarray(res["collided"], float)),
+                min_neg_clear=_mean_std(neg_clear.min(axis=0) if T else np.zeros(E)),
+                lane_departure=_mean_std((log_i[:, :, 1].astype(bool) & live).any(axis=0).astype(float)),
+                progress=_mean_std(log_d[last, np.arange(E), 2] - log_d[0, :, 2] if T else np.zeros(E)))
+
+
+def closed_loop(prob, costs, route, goal_index, vehicles, starts, ticks, out_dir=None, run=None, log=print, **kw):
+    """Runs ``run(prob, cost, route, goal_index, vehicles, starts, ticks, **kw)``
+    (default: ``prob.run_episodes``) per cost, writes the files and prints the
+    lines of the module docstring.  Returns {cost: (the result, its summary)}."""
+    run = run or _run
+    results = {}
+    for cost in costs:
+        if cost not in COSTS:
+            raise ValueError(f"cost must be one of {sorted(COSTS)}")
+        res = run(prob, cost, route, goal_index, vehicles, starts, ticks, **kw)
+        if out_dir is not None:
+            os.makedirs(out_dir, exist_ok=True)
+            np.savez(os.path.join(out_dir, f"closed_loop_{cost}.npz"), **{k: res[k] for k in LOG_KEYS})
+        s = summarise(res)
+        E = np.asarray(res["done_tick"]).size
+        log(f"{cost}: {E} episodes x {int(ticks)} ticks, collision share = {s['collision'][0]:.4f} +- "
+            f"{s['collision'][1]:.4f}, mean min -clear = {s['min_neg_clear'][0]:.4f} +- {s['min_neg_clear'][1]:.4f}, "
+            f"lane departure share = {s['lane_departure'][0]:.4f} +- {s['lane_departure'][1]:.4f}, "
+            f"mean progress = {s['progress'][0]:.2f} +- {s['progress'][1]:.2f} m")
+        results[cost] = (res, s)
+    return results
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="closed-loop CARLA episodes on the surrogate world")
+    ap.add_argument("--synthetic", action="store_true", help="the synthetic route and spawns of replay.py")
+    ap.add_argument("--town", default="Town05")
+    ap.add_argument("--episodes", type=int, default=8)
+    ap.add_argument("--ticks", type=int, default=200)
+    ap.add_argument("--costs", nargs="+", default=["mmd", "cvar", "det"], choices=sorted(COSTS))
+    ap.add_argument("--host-step", action="store_true", help="solve tick by tick and step the world on the host (mpcmmd_world_step_host)")
+    ap.add_argument("--start-spread", type=float, default=0.0, metavar="S")
+    ap.add_argument("--out", default="stats_carla")
+    ap.add_argument("--num-reduced", type=int, default=10)
+    ap.add_argument("--num-obs", type=int, default=3)
+    ap.add_argument("--num-prime", type=int, default=60)
+    ap.add_argument("--num-path", type=int, default=600)
+    ap.add_argument("--noise", default="gaussian", choices=["gaussian", "beta"])
+    ap.add_argument("--noise-level", type=float, default=0.1)
+    ap.add_argument("--acc-const-noise", type=float, default=0.0)
+    ap.add_argument("--steer-const-noise", type=float, default=0.0)
+    ap.add_argument("--num-batch", type=int, default=100)
+    ap.add_argument("--maxiter-cem", type=int, default=20)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args(argv)
+    if not a.synthetic:
+        ap.error("only --synthetic worlds are built in")
+    if sys.path[0] != _HERE:
+        sys.path.insert(0, _HERE)
+    from optimizer import cem
+    route, goal_index, vehicles = synthetic_world(a.town)
+    prob = cem.CEM(a.num_reduced, 1, a.num_obs, a.noise_level, a.num_prime, a.noise, a.town, a.acc_const_noise,
+                   a.steer_const_noise, num_batch=a.num_batch, maxiter_cem=a.maxiter_cem, seed=a.seed,
+                   max_configs=a.episodes)
+    closed_loop(prob, a.costs, route, goal_index, vehicles, synthetic_starts(route, a.episodes, a.start_spread),
+                a.ticks, a.out, num_path=a.num_path, v_des=V_DES, seed=a.seed, chained=not a.host_step,
+                device_step=False)
+    prob.close()
+
+
+if __name__ == "__main__":
+    main()

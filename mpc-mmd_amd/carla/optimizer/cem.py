@@ -157,6 +157,122 @@ class CEM:
         return ([(r["cx"], r["cy"], r["v_best"].copy(), r["steering"].copy(), r["mean_param"]) for r in rs],
                 [tk.path(g) for g in range(len(rs))])
 
+    def world_model(self, route, total_obs, goal_index=None, num_path=600, cov=None, dt=0.05, seed=0):
+        """(the surrogate world's ``_native.WorldModel`` for this optimizer on
+        ``route`` = (x, y) of the extended route, the tick context of
+        ``num_path``): the splines are ``path_spline``'s, the noise model, lane
+        bounds and ellipse the optimizer's own."""
+        N = native()
+        rx, ry = (np.ascontiguousarray(a, np.float64) for a in route)
+        fit = getattr(self, "_route_fit", None)   # the last route's splines: a 21 k-point fit costs milliseconds
+        if fit is None or not (np.array_equal(fit[0], rx) and np.array_equal(fit[1], ry)):
+            fit = self._route_fit = (rx, ry, *self.cem_helper.path_spline(rx, ry))
+        csx, csy, arc = fit[2], fit[3], fit[6]
+        cov = np.diag([20.0] * 4 + [100.0] * 4).astype(np.float32) if cov is None else np.asarray(cov, np.float32)
+        pop0 = np.random.default_rng([seed, 1]).standard_normal((self.num_batch, 8))
+        pdot = N.host_constant(self._cfg, "Pdot").reshape(self.num, 11)   # plan_speed's basis
+        model = N.WorldModel(rx, ry, arc, csx.c, csy.c, pdot[:4], cov, pop0, num_path, self.num_obs,
+                             rx.size - 1 if goal_index is None else goal_index, self.y_lb, self.y_ub,
+                             total_obs, noise=self.noise, dt=dt, sigma_acc=self.sigma_acc,
+                             sigma_steer=self.sigma_steer, acc_const=self.acc_const_noise,
+                             steer_const=self.steer_const_noise, steer_max=self.steer_max, a_obs=self.a_obs,
+                             b_obs=self.b_obs, seed=self._cfg.seed)
+        if num_path not in self._ticks:
+            self._ticks[num_path] = N.Tick(self._h, num_path)
+        return model, self._ticks[num_path]
+
+    def run_episodes(self, cost, route, vehicles, starts, ticks, *, goal_index=None, num_path=600, mean=None, cov=None,
+                     v_des=10.0, dt=0.05, threshold=0.1, u=None, key_base=0, key_stride=100000, seed=0,
+                     device_step=True, chained=False):
+        """E closed-loop episodes of ``ticks`` ticks on the surrogate world
+        (DESIGN.md section 19): each tick all E episodes are ONE batched solve
+        through the tick route (E <= max_configs), then one world step turns
+        the plans into the next tick's raw inputs -- k_world_step on the GPU
+        (``device_step``) or mpcmmd_world_step_host; the two give the same bits.
+        There the step's arrays cross the host between solve and step.  With
+        ``chained`` the whole loop is enqueued on the device (mpcmmd_world_run:
+        begin, CEM and k_world_step per tick, nothing crossing the host, one
+        readback of the log at the end) and gives the same bits again;
+        ``chained`` may be a sequence of tick counts to split the run into.
+
+        route (x, y) float64 of the extended route, goal_index its goal point
+        (default: the last); vehicles [total_obs, 5] = x, y, vx, vy, psi;
+        starts [E, 4] = x, y, v, psi.  Episode e has the key key_base +
+        key_stride e: it solves tick k with idx_mpc = k + key and carries its
+        own mean_param.  The perturbation's variates are drawn by the library
+        from (key, the optimizer's seed, tick) after each tick's solve --
+        normals, or for Beta noise Beta(2 |a_c|, 5 |a_c|) and Beta(2 |s_c|,
+        5 |s_c|) of that tick's controls -- unless u [ticks, E, 4] is given.  Returns log_d [T, E, 3], log_f [T, E, 13], log_i [T, E, 4]
+        (``_native.WORLD_LOG_*`` name the columns), done_tick, collided, goal
+        [E] and, per tick, cx, cy [T, E, 11], steering [T, E, 4], mean_param
+        [T, E, 8]."""
+        N = native()
+        kinds = {"mmd": "mmd_opt", "cvar": "cvar", "det": "det"}
+        if cost not in kinds:
+            raise ValueError("cost must be 'mmd', 'cvar' or 'det'")
+        starts = np.asarray(starts, np.float64).reshape(-1, 4)
+        E, T = starts.shape[0], int(ticks)
+        if E > self.max_configs:
+            raise ValueError(f"{E} episodes > max_configs {self.max_configs}")
+        if T < 1:
+            raise ValueError("ticks must be >= 1")
+        if u is not None:
+            u = np.asarray(u, np.float32).reshape(T, E, 4)
+        keys = int(key_base) + int(key_stride) * np.arange(E)
+        mean = np.array([v_des] * 4 + [0.0] * 4, np.float32) if mean is None else np.asarray(mean, np.float32)
+        cov = np.diag([20.0] * 4 + [100.0] * 4).astype(np.float32) if cov is None else np.asarray(cov, np.float32)
+        vehicles = np.asarray(vehicles, np.float32).reshape(-1, 5)
+        model, tk = self.world_model(route, vehicles.shape[0], goal_index, num_path, cov, dt, seed)
+        if chained:
+            world = N.World(tk, model, T)
+            try:
+                world.reset(starts[:, :2], np.stack([starts[:, 2], starts[:, 3], np.zeros(E)], 1),
+                            np.tile(vehicles[None], (E, 1, 1)), np.tile(mean.reshape(1, 8), (E, 1)), cov, u, keys)
+                k0 = 0
+                for count in ([T] if chained is True else [int(c) for c in chained]):   # a run may be split
+                    world.run(kinds[cost], k0, count, cov, v_des, threshold)
+                    k0 += count
+                if k0 != T:
+                    raise ValueError("chained: the tick counts must add up to ticks")
+                out = world.log(T)
+            finally:
+                world.close()
+            done = np.where(out["done_tick"] >= 0, out["done_tick"], T - 1)
+            at_end = out["log_i"][done, np.arange(E)]
+            out["collided"], out["goal"] = at_end[:, 2].astype(bool), at_end[:, 3].astype(bool)
+            return out
+        dev = self._cfg.device if device_step else None
+        st = dict(pos=starts[:, :2].copy(), ego=np.stack([starts[:, 2], starts[:, 3], np.zeros(E)], 1),
+                  vehicles=np.tile(vehicles[None], (E, 1, 1)), done_tick=np.full(E, -1, np.int32))
+        means = np.tile(mean.reshape(1, 8), (E, 1))
+        # a frozen step leaves the state alone and writes the raw inputs of the state it is given: tick 0's
+        zero = lambda n: np.zeros((E, n), np.float32)
+        nxt = N.world_step(model, -1, zero(11), zero(11), zero(4), zero(4), means, st["pos"], st["ego"],
+                           st["vehicles"], np.zeros(E, np.int32), device=dev)
+        out = dict(log_d=np.empty((T, E, 3)), log_f=np.empty((T, E, 13), np.float32),
+                   log_i=np.empty((T, E, 4), np.int32), cx=np.empty((T, E, 11), np.float32),
+                   cy=np.empty((T, E, 11), np.float32), steering=np.empty((T, E, 4), np.float32),
+                   mean_param=np.empty((T, E, 8), np.float32))
+        for k in range(T):
+            idx = [k + int(key) for key in keys]
+            rs = tk.solve_batch(kinds[cost], idx, nxt["init_state"], nxt["x_wp"], nxt["y_wp"], nxt["obstacles"],
+                                threshold, means, cov, v_des)
+            out["cx"][k] = [r["cx"] for r in rs]
+            out["cy"][k] = [r["cy"] for r in rs]
+            out["steering"][k] = [np.asarray(r["steering"])[:4] for r in rs]
+            means = np.array([r["mean_param"] for r in rs], np.float32)
+            out["mean_param"][k] = means
+            nxt = N.world_step(model, k, out["cx"][k], out["cy"][k], out["steering"][k], None if u is None else u[k],
+                               means, st["pos"], st["ego"], st["vehicles"], st["done_tick"], device=dev, keys=keys)
+            st = {key: nxt[key] for key in st}
+            for key in ("log_d", "log_f", "log_i"):
+                out[key][k] = nxt[key]
+        out["done_tick"] = st["done_tick"]
+        done = np.where(st["done_tick"] >= 0, st["done_tick"], T - 1)
+        at_end = out["log_i"][done, np.arange(E)]
+        out["collided"], out["goal"] = at_end[:, 2].astype(bool), at_end[:, 3].astype(bool)
+        return out
+
     def close(self):
         """Free the tick contexts, then the handle."""
         for tk in self._ticks.values():

@@ -138,6 +138,7 @@ int mpcmmd::begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const
     std::vector<double> sc(size_t(G) * 4 * kNvar);
     std::vector<float> st0(size_t(G) * 8), ob(size_t(G) * 2 * O * H), pop(size_t(G) * B * 8);
     const bool det = cost_kind == MPCMMD_COST_DET;  // the det projection's own KKT
+    const bool chained = tick && tick->chained;     // the world route: st0, pop and mean are on the device
     const double* pkx = det ? h->det_kx.data() : h->pc.proj_kinv_x.data();
     const double* pky = det ? h->det_ky.data() : h->pc.proj_kinv_y.data();
     CarlaBatch cb;  // CARLA: the noisy initial rows, path and det track images of every configuration
@@ -182,7 +183,8 @@ int mpcmmd::begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const
         obstacle_transpose(x_obs + size_t(g) * O * kNum, y_obs + size_t(g) * O * kNum, O, H,
                            ob.data() + size_t(g) * 2 * O * H);
       }
-      initial_population(mean + size_t(g) * 8, cov + size_t(g) * 64, z0.data(), B, pop.data() + size_t(g) * B * 8);
+      if (!chained)
+        initial_population(mean + size_t(g) * 8, cov + size_t(g) * 64, z0.data(), B, pop.data() + size_t(g) * B * 8);
     }
     if (!tick) upload_staged(h, p.solve_c, sc.data(), sc.size() * 8);
     if (h->carla) {
@@ -203,10 +205,12 @@ int mpcmmd::begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const
         HIPC(hipMemsetAsync(p.lane_des, 0, size_t(G) * B * 4, h->stream));
       }
     }
-    upload_staged(h, p.st0, st0.data(), st0.size() * 4);
+    if (!chained) upload_staged(h, p.st0, st0.data(), st0.size() * 4);
     if (!tick) upload_staged(h, p.obs, ob.data(), ob.size() * 4);
-    upload_staged(h, p.pop, pop.data(), pop.size() * 4);  // iteration 0's half: [0][G B][8]
-    upload_staged(h, p.mean, mean, cfg_bytes(h, p.mean, G));
+    if (!chained) {
+      upload_staged(h, p.pop, pop.data(), pop.size() * 4);  // iteration 0's half: [0][G B][8]
+      upload_staged(h, p.mean, mean, cfg_bytes(h, p.mean, G));
+    }
     upload_staged(h, p.cov, cov, cfg_bytes(h, p.cov, G));
     HIPC(hipMemsetAsync(p.lam_x, 0, cfg_bytes(h, p.lam_x, G), h->stream));
     HIPC(hipMemsetAsync(p.lam_y, 0, cfg_bytes(h, p.lam_y, G), h->stream));

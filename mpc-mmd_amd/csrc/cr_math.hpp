@@ -11,6 +11,7 @@ namespace mpcmmd {
 
 DEVI float cr_atan2(float y, float x) { return float(atan2(double(y), double(x))); }
 DEVI float cr_sin(float a) { return float(sin(double(a))); }
+DEVI float cr_tan(float a) { return float(tan(double(a))); }
 // cos and sin from one fp64 sincos (OCML: one argument reduction, the values
 // of cos and sin), each rounded once
 DEVI void cr_sincos(float a, float& s, float& c) {

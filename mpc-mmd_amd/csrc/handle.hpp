@@ -193,6 +193,9 @@ struct TickRoute {
   int num_path;
   void* ctx;
   void (*enqueue)(void* ctx, int G, int cost_kind, int R, const float* const* eps);
+  // the world route: init_state, st0, the first population and the mean are on the device already
+  // (k_world_step wrote them), so begin_impl uploads none of them
+  bool chained = false;
 };
 
 // mpcmmd_begin for n_cfg configurations (begin.hip).  path: n_cfg paths (the

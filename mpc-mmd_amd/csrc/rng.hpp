@@ -43,6 +43,13 @@ enum Stream : uint32_t {
   kStreamVcGammaSteerA = 37,
   kStreamVcGammaSteerB = 38,
   kStreamVcInitEps = 39,
+  // the surrogate world's perturbation (world_draw.hpp), key (episode key, seed), element = tick: block `tick`
+  // of the normals (u0, -, u2, u3; Beta noise takes u2, u3 only) and the Beta gammas of u0 (acc) and u1 (steer)
+  kStreamWorldNormal = 40,
+  kStreamWorldGammaAccA = 41,
+  kStreamWorldGammaAccB = 42,
+  kStreamWorldGammaSteerA = 43,
+  kStreamWorldGammaSteerB = 44,
 };
 constexpr uint32_t kFixedKey0 = 0xFFFFFFFFu;
 constexpr int kGammaMaxAttempts = 32;

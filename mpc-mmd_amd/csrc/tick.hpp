@@ -51,3 +51,19 @@ void launch_tick_path(const TickParams& t, hipStream_t s);
 void launch_tick_setup(const TickParams& t, hipStream_t s);
 
 }  // namespace mpcmmd
+
+// What the world route (world_api.hip) needs of a tick context (tick_api.hip).
+struct mpcmmd_tick;
+struct mpcmmd_handle;
+namespace mpcmmd {
+mpcmmd_handle* tick_handle(mpcmmd_tick* t);
+int tick_num_path(const mpcmmd_tick* t);
+TickLayout tick_layout_of(const mpcmmd_tick* t);
+float* tick_inputs_device(mpcmmd_tick* t);  // [Gmax][stride]
+// mpcmmd_carla_tick_begin_batch on raw inputs that k_world_step has already
+// written to the context's input image, with st0, the first population and
+// the mean on the device too: only idx_mpc, v_des, cov and the init_eps
+// normals are staged.  Argument checks as the tick begin's, before any HIP call.
+int tick_begin_chained(mpcmmd_tick* t, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc, const float* cov,
+                       const float* v_des, float threshold);
+}  // namespace mpcmmd

@@ -25,6 +25,7 @@ struct mpcmmd_tick {
   hipEvent_t ev = nullptr;
   bool pending = false;
   const mpcmmd_tick_inputs* cur = nullptr;  // the inputs of the begin in progress
+  float chained_threshold = 0.0f;           // that of the chained begin in progress
 };
 
 namespace {
@@ -39,6 +40,29 @@ std::vector<double> kkt_columns(const ProblemConsts& pc, const double* pkx, cons
     for (int e = 0; e < 4; ++e) out[(3 * kNvar + k) * 4 + e] = pky[k * 15 + kNvar + e];
   }
   return out;
+}
+
+// the two kernels of a begin on inputs that are in t->in
+void launch_kernels(mpcmmd_tick* t, int G, int cost_kind, int R, float threshold) {
+  mpcmmd_handle* h = t->h;
+  const bool det = cost_kind == MPCMMD_COST_DET;
+  TickParams q{};
+  q.G = G, q.P = t->P, q.O = h->O, q.H = h->H, q.R = R, q.R0 = h->R0, q.det = det ? 1 : 0;
+  q.thr = threshold;
+  q.lay = t->lay;
+  q.mu_x = float(h->pc.init_mu_x), q.mu_y = float(h->pc.init_mu_y);
+  q.sg_x = float(h->pc.init_sigma_x), q.sg_y = float(h->pc.init_sigma_y);
+  q.inv = t->inv;
+  q.kcol = t->kcol + (det ? size_t(4) * kNvar * 4 : 0);
+  q.in = t->in;
+  q.fr = t->fr;
+  // the kernels write the handle's buffers (Params holds them as inputs of the solve)
+  auto out = [&](const void* member) { return h->buf_of(member).ptr; };
+  q.path = static_cast<float*>(out(h->p.path)), q.st0r = static_cast<float*>(out(h->p.st0r));
+  q.obs = static_cast<float*>(out(h->p.obs)), q.obs_full = static_cast<float*>(out(h->p.obs_full));
+  q.solve_c = static_cast<double*>(out(h->p.solve_c));
+  h->launch(kKTickPath, [&] { launch_tick_path(q, h->stream); });
+  h->launch(kKTickSetup, [&] { launch_tick_setup(q, h->stream); });
 }
 
 // begin_impl's callback: stage and upload the raw inputs of G ticks, then the two kernels
@@ -62,24 +86,29 @@ void enqueue(void* ctx, int G, int cost_kind, int R, const float* const* eps) {
   HIPC(hipMemcpyAsync(t->in, t->stage, size_t(G) * l.stride * 4, hipMemcpyHostToDevice, h->stream));
   HIPC(hipEventRecord(t->ev, h->stream));
   t->pending = true;
-  const bool det = cost_kind == MPCMMD_COST_DET;
-  TickParams q{};
-  q.G = G, q.P = P, q.O = O, q.H = h->H, q.R = R, q.R0 = h->R0, q.det = det ? 1 : 0;
-  q.thr = in.threshold;
-  q.lay = l;
-  q.mu_x = float(h->pc.init_mu_x), q.mu_y = float(h->pc.init_mu_y);
-  q.sg_x = float(h->pc.init_sigma_x), q.sg_y = float(h->pc.init_sigma_y);
-  q.inv = t->inv;
-  q.kcol = t->kcol + (det ? size_t(4) * kNvar * 4 : 0);
-  q.in = t->in;
-  q.fr = t->fr;
-  // the kernels write the handle's buffers (Params holds them as inputs of the solve)
-  auto out = [&](const void* member) { return h->buf_of(member).ptr; };
-  q.path = static_cast<float*>(out(h->p.path)), q.st0r = static_cast<float*>(out(h->p.st0r));
-  q.obs = static_cast<float*>(out(h->p.obs)), q.obs_full = static_cast<float*>(out(h->p.obs_full));
-  q.solve_c = static_cast<double*>(out(h->p.solve_c));
-  h->launch(kKTickPath, [&] { launch_tick_path(q, h->stream); });
-  h->launch(kKTickSetup, [&] { launch_tick_setup(q, h->stream); });
+  launch_kernels(t, G, cost_kind, R, in.threshold);
+}
+
+// the chained begin's callback (the world route): init_state, waypoints and
+// obstacles are already in t->in, written by k_world_step; only the init_eps
+// normals are staged, into each tick's eps slice (one strided copy)
+void enqueue_chained(void* ctx, int G, int cost_kind, int R, const float* const* eps) {
+  mpcmmd_tick* t = static_cast<mpcmmd_tick*>(ctx);
+  mpcmmd_handle* h = t->h;
+  if (t->pending) HIPC(hipEventSynchronize(t->ev));
+  t->pending = false;
+  const TickLayout& l = t->lay;
+  const size_t width = size_t(l.stride - l.eps) * 4, pitch = size_t(l.stride) * 4;
+  for (int g = 0; g < G; ++g) {
+    float* s = t->stage + size_t(g) * l.stride + l.eps;
+    std::memset(s, 0, width);
+    std::memcpy(s, eps[g], size_t(R) * 4 * 4);
+  }
+  HIPC(hipMemcpy2DAsync(t->in + l.eps, pitch, t->stage + l.eps, pitch, width, size_t(G), hipMemcpyHostToDevice,
+                        h->stream));
+  HIPC(hipEventRecord(t->ev, h->stream));
+  t->pending = true;
+  launch_kernels(t, G, cost_kind, R, t->chained_threshold);
 }
 
 int check_begin(mpcmmd_tick* t, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc, const mpcmmd_tick_inputs* in,
@@ -101,6 +130,27 @@ int check_begin(mpcmmd_tick* t, int32_t n_cfg, int32_t cost_kind, const int32_t*
 }
 
 }  // namespace
+
+// ---- what the world route (world_api.hip) needs of a tick context ----------------
+mpcmmd_handle* mpcmmd::tick_handle(mpcmmd_tick* t) { return t->h; }
+int mpcmmd::tick_num_path(const mpcmmd_tick* t) { return t->P; }
+TickLayout mpcmmd::tick_layout_of(const mpcmmd_tick* t) { return t->lay; }
+float* mpcmmd::tick_inputs_device(mpcmmd_tick* t) { return t->in; }
+
+int mpcmmd::tick_begin_chained(mpcmmd_tick* t, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc,
+                               const float* cov, const float* v_des, float threshold) {
+  // init_state and mean are on the device already: begin_impl reads neither on the chained route
+  const std::vector<float> zeros(size_t(n_cfg > 0 ? n_cfg : 1) * 8, 0.0f);
+  mpcmmd_tick_inputs in{};
+  in.init_state = in.x_wp = in.y_wp = in.obstacles = zeros.data();
+  in.threshold = threshold;
+  if (int rc = check_begin(t, n_cfg, cost_kind, idx_mpc, &in, zeros.data(), cov, v_des)) return rc;
+  t->chained_threshold = threshold;
+  TickRoute route{t->P, t, enqueue_chained};
+  route.chained = true;
+  return begin_impl(t->h, n_cfg, cost_kind, idx_mpc, zeros.data(), zeros.data(), cov, nullptr, nullptr, v_des, nullptr,
+                    nullptr, &route);
+}
 
 extern "C" {
 

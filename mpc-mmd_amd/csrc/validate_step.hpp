@@ -19,8 +19,9 @@ constexpr int kValMaxH = 100;
 // uniform-free Beta(a, b) straight from the Philox attempt streams
 // (rng.hpp: gamma_attempt), log-space ratio as beta_draw_tab.  The values
 // are log of gamma_direct's g (rng.hpp); the loop stays here with a log at
-// each exit, the form k_validate's instruction stream was measured in
-DEVI void log_gamma_direct(double alpha, uint32_t k0, uint32_t k1, uint32_t stream, uint32_t elem, double& lg,
+// each exit, the form k_validate's instruction stream was measured in.
+// Host-callable too: the surrogate world's host twin draws with it (world_draw.hpp).
+HDI void log_gamma_direct(double alpha, uint32_t k0, uint32_t k1, uint32_t stream, uint32_t elem, double& lg,
                            double& lub) {
   const MtConst mc = mt_const(alpha);
   lg = log(mc.d);
@@ -39,7 +40,7 @@ DEVI void log_gamma_direct(double alpha, uint32_t k0, uint32_t k1, uint32_t stre
   }
 }
 
-DEVI double beta_direct(double a, double b, uint32_t k0, uint32_t k1, uint32_t sa, uint32_t sb, uint32_t elem) {
+HDI double beta_direct(double a, double b, uint32_t k0, uint32_t k1, uint32_t sa, uint32_t sb, uint32_t elem) {
   double ga, ua, gb, ub;
   log_gamma_direct(a, k0, k1, sa, elem, ga, ua);
   log_gamma_direct(b, k0, k1, sb, elem, gb, ub);

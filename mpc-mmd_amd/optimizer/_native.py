@@ -32,6 +32,8 @@ SYMBOLS = (
     "mpcmmd_validate_risk", "mpcmmd_quantile_position", "mpcmmd_validate_carla_risk",
     "mpcmmd_carla_begin_batch", "mpcmmd_carla_solve_batch", "mpcmmd_tick_create", "mpcmmd_tick_destroy",
     "mpcmmd_carla_tick_begin_batch", "mpcmmd_carla_tick_solve_batch", "mpcmmd_carla_tick_host",
+    "mpcmmd_world_step_host", "mpcmmd_world_step_device", "mpcmmd_world_create", "mpcmmd_world_destroy",
+    "mpcmmd_world_reset", "mpcmmd_world_run", "mpcmmd_world_log",
 )
 
 
@@ -121,6 +123,29 @@ class ValidateCarlaRiskArgs(C.Structure):
         ("elapsed_ms", C.POINTER(C.c_float))]
 
 
+class WorldModelStruct(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("num_path", "num_obs", "total_obs", "num_route", "goal_index", "num_batch",
+                                          "noise")] +
+                [(k, C.c_float) for k in ("dt", "sigma_acc", "sigma_steer", "acc_const", "steer_const", "steer_max",
+                                          "a_obs", "b_obs", "y_lb", "y_ub")] +
+                [(k, C.POINTER(C.c_double)) for k in ("route_x", "route_y", "route_arc", "spline_x", "spline_y",
+                                                      "pdot4", "chol")] +
+                [("pop0", C.POINTER(C.c_float)), ("seed", C.c_uint32)])
+
+
+class WorldStepIO(C.Structure):
+    _fields_ = ([(k, C.POINTER(C.c_float)) for k in ("cx", "cy", "steer", "u", "mean")] +
+                [("pos", C.POINTER(C.c_double)), ("ego", C.POINTER(C.c_float)), ("vehicles", C.POINTER(C.c_float)),
+                 ("done_tick", C.POINTER(C.c_int32))] +
+                [(k, C.POINTER(C.c_float)) for k in ("init_state", "x_wp", "y_wp", "obstacles", "pop")] +
+                [("log_d", C.POINTER(C.c_double)), ("log_f", C.POINTER(C.c_float)), ("log_i", C.POINTER(C.c_int32)),
+                 ("key", C.POINTER(C.c_uint32))])
+
+
+WORLD_LOG_D = ("x", "y", "arc")
+WORLD_LOG_F = ("v", "psi", "psidot", "a_c", "s_c", "a", "s", "u0", "u1", "u2", "u3", "clear", "d")
+WORLD_LOG_I = ("idx", "lane_out", "collided", "goal")
+
 assert ValidateCarlaRiskArgs._fields_[20][0] == "keys"   # the inputs of ValidateCarlaArgs, up to the keys
 
 RISK_CHANNELS = ("obs", "lane_lb", "lane_ub")
@@ -199,6 +224,17 @@ def lib():
         L.mpcmmd_carla_tick_begin_batch.argtypes = targs
         L.mpcmmd_carla_tick_solve_batch.argtypes = targs + [C.POINTER(Result)]
         L.mpcmmd_carla_tick_host.argtypes = [C.c_int32, C.c_int32, fp, fp, fp, fp, C.c_float, fp, fp, fp]
+    if hasattr(L, "mpcmmd_world_step_host"):   # an older library lacks the world: world_step raises
+        L.mpcmmd_world_step_host.argtypes = [C.POINTER(WorldModelStruct), C.c_int32, C.POINTER(WorldStepIO)]
+        L.mpcmmd_world_step_device.argtypes = [C.POINTER(WorldModelStruct), C.c_int32, C.c_int32, C.c_int32,
+                                               C.POINTER(WorldStepIO)]
+        dp = C.POINTER(C.c_double)
+        L.mpcmmd_world_create.argtypes = [vp, C.POINTER(WorldModelStruct), C.c_int32, C.POINTER(vp)]
+        L.mpcmmd_world_destroy.argtypes = [vp]
+        L.mpcmmd_world_destroy.restype = None
+        L.mpcmmd_world_reset.argtypes = [vp, C.c_int32, dp, fp, fp, fp, fp, fp, ip]
+        L.mpcmmd_world_run.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp, fp, C.c_float]
+        L.mpcmmd_world_log.argtypes = [vp, C.c_int32, dp, fp, ip, fp, ip]
     L.mpcmmd_path_smoothing.argtypes = [C.c_int32, fp, fp, C.c_float, fp, fp]
     L.mpcmmd_path_parameters.argtypes = [C.c_int32, fp, fp, fp, fp, fp, fp, fp, fp, fp]
     L.mpcmmd_global_to_frenet.argtypes = [C.POINTER(Path), C.c_int32, fp, fp, fp, fp, fp, fp, fp]
@@ -523,6 +559,150 @@ def carla_tick_host(init_state, x_wp, y_wp, obstacles, threshold=0.1):
     return dict(zip(PATH_KEYS, p6)), xo, yo
 
 
+class WorldModel:
+    """mpcmmd_world_model: the constants of a surrogate world (DESIGN.md section
+    19).  route_x / route_y / route_arc [R] float64 (the extended route and its
+    splines' breakpoints), spline_x / spline_y the ``.c`` [4, R - 1] of scipy's
+    ``CubicSpline(route_arc, route_x)``, pdot4 rows 0..3 of Pdot
+    (``host_constant(cfg, "Pdot")``), cov the run's [8, 8] covariance (factored
+    here as ``initial_population`` factors it), pop0 [B, 8] standard normals."""
+
+    def __init__(self, route_x, route_y, route_arc, spline_x, spline_y, pdot4, cov, pop0, num_path, num_obs,
+                 goal_index, y_lb, y_ub, total_obs, noise="gaussian", dt=0.05, sigma_acc=0.0, sigma_steer=0.0,
+                 acc_const=0.0, steer_const=0.0, steer_max=0.6, a_obs=4.5, b_obs=3.0, seed=0):
+        d = lambda a, *sh: np.ascontiguousarray(np.asarray(a, np.float64).reshape(*sh))
+        R = np.asarray(route_x).size
+        self.arrays = dict(route_x=d(route_x, R), route_y=d(route_y, R), route_arc=d(route_arc, R),
+                           spline_x=d(spline_x, 4, R - 1), spline_y=d(spline_y, 4, R - 1),
+                           pdot4=d(np.asarray(pdot4, np.float64).reshape(-1)[:44], 4, 11),
+                           chol=np.ascontiguousarray(np.linalg.cholesky(np.asarray(cov, np.float32).astype(np.float64)
+                                                                        .reshape(8, 8))))
+        self.pop0 = np.ascontiguousarray(np.asarray(pop0, np.float32).reshape(-1, 8))
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        self.num_path, self.num_obs, self.total_obs = int(num_path), int(num_obs), int(total_obs)
+        self.num_batch = self.pop0.shape[0]
+        self.c = WorldModelStruct(self.num_path, self.num_obs, self.total_obs, R, int(goal_index), self.num_batch,
+                                  NOISE[noise], dt, sigma_acc, sigma_steer, acc_const, steer_const, steer_max, a_obs,
+                                  b_obs, y_lb, y_ub,
+                                  *(dp(self.arrays[k]) for k in ("route_x", "route_y", "route_arc", "spline_x",
+                                                                 "spline_y", "pdot4", "chol")), _fptr(self.pop0),
+                                  int(seed) & 0xFFFFFFFF)
+
+
+def world_step(model, tick, cx, cy, steer, u, mean, pos, ego, vehicles, done_tick, device=None, keys=None):
+    """One step of E episodes of the surrogate world: mpcmmd_world_step_host per
+    episode (device None), or one k_world_step launch on GPU ``device``
+    (mpcmmd_world_step_device).  cx, cy [E, 11], steer [E, >= 4] (the plan's
+    steerings), u [E, 4] -- or None: drawn by the library from (keys [E], the
+    model's seed, tick) once the controls are known -- mean [E, 8]; the state pos [E, 2] float64, ego
+    [E, 3] = v, psi, psidot, vehicles [E, total_obs, 5], done_tick [E] is not
+    modified.  Returns a dict: the new state under the same names, the next
+    tick's init_state [E, 6], x_wp, y_wp [E, P], obstacles [E, O, 5], pop
+    [E, B, 8] and the log row log_d [E, 3], log_f [E, 13], log_i [E, 4]
+    (WORLD_LOG_D / _F / _I name the columns)."""
+    L = lib()
+    if not hasattr(L, "mpcmmd_world_step_host"):
+        raise NativeError(f"{LIB_PATH} has no mpcmmd_world_step_host (built before the entry point existed): rebuild it")
+    E = np.asarray(pos).reshape(-1, 2).shape[0]
+    m = model
+    f = lambda a, *sh: np.array(np.asarray(a, np.float32).reshape(E, *sh), np.float32, order="C")
+    if u is None and keys is None:
+        raise ValueError("world_step: give the variates u or the episodes' keys")
+    a = dict(cx=f(cx, 11), cy=f(cy, 11), steer=f(np.asarray(steer, np.float32).reshape(E, -1)[:, :4], 4),
+             u=np.zeros((0, 4), np.float32) if u is None else f(u, 4),
+             key=np.zeros(0, np.uint32) if keys is None else
+             np.array(np.asarray(keys, np.int64).reshape(E) & 0xFFFFFFFF, np.uint32),
+             mean=f(mean, 8), pos=np.array(np.asarray(pos, np.float64).reshape(E, 2), order="C"), ego=f(ego, 3),
+             vehicles=f(vehicles, m.total_obs, 5),
+             done_tick=np.array(np.asarray(done_tick).reshape(E), np.int32, order="C"),
+             init_state=np.empty((E, 6), np.float32), x_wp=np.empty((E, m.num_path), np.float32),
+             y_wp=np.empty((E, m.num_path), np.float32), obstacles=np.empty((E, m.num_obs, 5), np.float32),
+             pop=np.empty((E, m.num_batch, 8), np.float32), log_d=np.empty((E, 3), np.float64),
+             log_f=np.empty((E, 13), np.float32), log_i=np.empty((E, 4), np.int32))
+    names = [k for k, _ in WorldStepIO._fields_]
+
+    def io_of(e):
+        ptr = []
+        for k in names:
+            row = a[k][e:]   # the device call takes episode 0's address with every episode behind it
+            ptr.append(C.cast(row.ctypes.data, dict(WorldStepIO._fields_)[k]) if row.size else None)
+        return WorldStepIO(*ptr)
+
+    if device is None:
+        for e in range(E):
+            check(L.mpcmmd_world_step_host(C.byref(m.c), int(tick), C.byref(io_of(e))))
+    else:
+        check(L.mpcmmd_world_step_device(C.byref(m.c), int(device), E, int(tick), C.byref(io_of(0))))
+    for k in ("cx", "cy", "steer", "u", "mean", "key"):
+        del a[k]
+    return a
+
+
+class World:
+    """Owns one mpcmmd_world: the chained closed loop of ``tick``'s handle on the
+    surrogate world ``model`` (its num_path and num_obs must be the tick
+    context's) for up to ``max_ticks`` ticks.  ``reset`` takes the episodes'
+    start states, ``run(cost, tick_begin, count)`` enqueues begin, CEM and world
+    step per tick with nothing crossing the host, ``log(ticks)`` performs the
+    one readback.  Close it before its tick context."""
+
+    def __init__(self, tick, model, max_ticks):
+        self._L = lib()
+        if not hasattr(self._L, "mpcmmd_world_create"):
+            raise NativeError(f"{LIB_PATH} has no mpcmmd_world_create (built before the entry point existed): rebuild it")
+        self.tick, self.model, self.max_ticks = tick, model, int(max_ticks)
+        w = C.c_void_p()
+        check(self._L.mpcmmd_world_create(tick._t, C.byref(model.c), self.max_ticks, C.byref(w)))
+        self._w = w
+        self.E = 0
+        tick._worlds.append(self)   # Tick.close frees its world contexts first
+
+    def close(self):
+        if getattr(self, "_w", None):
+            self._L.mpcmmd_world_destroy(self._w)
+            self._w = None
+            if self in self.tick._worlds:
+                self.tick._worlds.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, pos, ego, vehicles, mean, cov, u, keys):
+        """pos [E, 2] float64, ego [E, 3] = v, psi, psidot, vehicles [E, total_obs, 5], mean [E, 8],
+        cov [8, 8], keys [E] (episode e solves tick k with idx_mpc = k + keys[e]), u [max_ticks, E, 4]
+        or None: the kernel draws each tick's variates from (keys[e], the handle's seed, tick)."""
+        pos = np.ascontiguousarray(np.asarray(pos, np.float64).reshape(-1, 2))
+        E = self.E = pos.shape[0]
+        f = lambda a, *sh: np.ascontiguousarray(np.asarray(a, np.float32).reshape(*sh))
+        veh = f(vehicles, E, self.model.total_obs, 5)
+        kk = np.ascontiguousarray(np.asarray(keys, np.int64).reshape(E).astype(np.int32))
+        check(self._L.mpcmmd_world_reset(self._w, E, pos.ctypes.data_as(C.POINTER(C.c_double)), _fptr(f(ego, E, 3)),
+                                         _fptr(veh) if veh.size else None, _fptr(f(mean, E, 8)), _fptr(f(cov, 64)),
+                                         None if u is None else _fptr(f(u, self.max_ticks, E, 4)),
+                                         kk.ctypes.data_as(C.POINTER(C.c_int32))))
+        self.tick.handle._G = E
+
+    def run(self, cost, tick_begin, count, cov, v_des, threshold=0.1):
+        f = lambda a, *sh: np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32), sh))
+        check(self._L.mpcmmd_world_run(self._w, COST[cost], int(tick_begin), int(count),
+                                       _fptr(np.ascontiguousarray(np.asarray(cov, np.float32).reshape(64))),
+                                       _fptr(f(np.asarray(v_des, np.float32).reshape(-1), self.E)), float(threshold)))
+
+    def log(self, ticks):
+        """The first ``ticks`` rows: dict of log_d, log_f, log_i, cx, cy, steering, mean_param, done_tick."""
+        T, E = int(ticks), self.E
+        ld, lf = np.empty((T, E, 3), np.float64), np.empty((T, E, 13), np.float32)
+        li, pl, dn = np.empty((T, E, 4), np.int32), np.empty((T, E, 34), np.float32), np.empty(E, np.int32)
+        ip = C.POINTER(C.c_int32)
+        check(self._L.mpcmmd_world_log(self._w, T, ld.ctypes.data_as(C.POINTER(C.c_double)), _fptr(lf),
+                                       li.ctypes.data_as(ip), _fptr(pl), dn.ctypes.data_as(ip)))
+        return dict(log_d=ld, log_f=lf, log_i=li, cx=pl[..., :11].copy(), cy=pl[..., 11:22].copy(),
+                    steering=pl[..., 22:26].copy(), mean_param=pl[..., 26:].copy(), done_tick=dn)
+
+
 class Tick:
     """Owns one mpcmmd_tick: the tick route of ``handle`` for paths of
     ``num_path`` points.  ``begin_batch`` / ``solve_batch`` take the raw data
@@ -541,9 +721,12 @@ class Tick:
         check(self._L.mpcmmd_tick_create(handle._h, self.num_path, C.byref(t)))
         self._t = t
         self._keep = None
+        self._worlds = []
         handle._ticks.append(self)   # Handle.close frees its tick contexts first
 
     def close(self):
+        for w in list(getattr(self, "_worlds", [])):
+            w.close()
         if getattr(self, "_t", None):
             self._L.mpcmmd_tick_destroy(self._t)
             self._t = None
