@@ -839,6 +839,70 @@ int mpcmmd_world_run(mpcmmd_world* w, int32_t cost_kind, int32_t tick_begin, int
 int mpcmmd_world_log(mpcmmd_world* w, int32_t ticks, double* log_d, float* log_f, int32_t* log_i, float* plan,
                      int32_t* done_tick);
 
+/* The validation stage of the chained route: the Monte-Carlo risk of every
+ * tick's plan, computed inside the loop from the device buffers the solve just
+ * used.  (No ABI version change: callers detect these entry points by their
+ * symbols.)
+ *
+ * mpcmmd_world_validate configures the stage (cfg NULL: turns it off) and
+ * allocates everything it needs -- the costs [E][3][R], the MMD scratch, the
+ * counters, the packed inputs and the logs [max_ticks][E]... -- so a run
+ * allocates nothing.  It synchronises the handle's stream, and it takes effect
+ * at the next mpcmmd_world_reset: a run before that reset is MPCMMD_E_STATE.
+ *
+ * With the stage on, mpcmmd_world_run enqueues per tick, in this order: the
+ * chained begin, the T CEM iterations, the validation stage, k_world_step (the
+ * step overwrites the tick's init_state and st0, so the stage comes first).
+ * The stage is k_world_validate_prep, which packs the validators' inputs on
+ * the device, two hipMemsetAsync of the integer accumulators, and then the
+ * launches of mpcmmd_validate_carla_risk unchanged, with their results pointed
+ * at the tick's log row.  No device-to-host copy, no synchronisation and no
+ * allocation is added to the loop, and the solve and the world's log are what
+ * they are without the stage.
+ *
+ * The log row of (tick k, episode e) is, bit for bit, what
+ * mpcmmd_validate_carla_risk returns for num_cfg = 1 with: init_state the
+ * tick's raw init_state; v, steer the solve's v_best and steering as
+ * mpcmmd_finish_batch returns them; x_obs, y_obs the handle's obs buffer
+ * (columns >= num_prime zero: the validator reads h < num_prime only); path the
+ * first num_path columns of the handle's path; noise, noise_level,
+ * acc_const_noise, steer_const_noise, variant, seed, num_prime, num_obs the
+ * handle's configuration; num_path the tick context's; keys[0] = uint32(k +
+ * keys[e]), the tick's idx_mpc; draws, init_eps NULL; alpha, sigma from cfg.
+ * The validators' Philox streams are their own, so the rows are independent
+ * of the solve's draws under the same key.  Frozen episodes are validated like
+ * the others (their frozen state and its plan).
+ *
+ * mpcmmd_world_validation_log synchronises and reads back the first `ticks`
+ * rows: counts [ticks][E][3] = count, count_lane, count_rows of
+ * mpcmmd_validate_carla; count_pos [ticks][E][3] per channel (obs, lane_lb,
+ * lane_ub); stats [ticks][E][4][3] = var, cvar, mean, max per channel; mmd
+ * [ticks][E][3][num_sigma] (may be NULL when num_sigma == 0); est
+ * [ticks][E][2] = the cost_lane and cost_obs the solve itself estimated
+ * (mpcmmd_result).  mpcmmd_world_validation_inputs synchronises and reads back
+ * the packed inputs of the last validated tick (debugging and tests): acc,
+ * steer [E][num_prime], st0 [E][8], path [E][6][num_path], x_obs, y_obs
+ * [E][num_obs][100], keys [E]; a NULL array is skipped.
+ *
+ * Before any HIP call: MPCMMD_E_INVALID for a NULL w, num_rollouts outside
+ * 1..2^20 or num_rollouts * num_prime >= 2^31, alpha outside [0, 1],
+ * num_sigma outside 0..8, a sigma that is not finite and > 0, a handle with
+ * num_obs > 32 (the validator's limit), a NULL required log array, a tick
+ * range outside [0, max_ticks]; MPCMMD_E_STATE for a log or inputs readback
+ * while the stage is off.  MPCMMD_E_UNSUPPORTED if the validator's workgroup
+ * needs more LDS than the device has. */
+typedef struct mpcmmd_world_validation {
+  int32_t num_rollouts; /* R: fresh noise rows per (tick, episode) */
+  float alpha;          /* quantile level of VaR / CVaR */
+  int32_t num_sigma;    /* S, 0..8 */
+  float sigma[8];       /* MMD bandwidths, the same for every episode and tick */
+} mpcmmd_world_validation;
+int mpcmmd_world_validate(mpcmmd_world* w, const mpcmmd_world_validation* cfg);
+int mpcmmd_world_validation_log(mpcmmd_world* w, int32_t ticks, int32_t* counts, int32_t* count_pos, float* stats,
+                                float* mmd, float* est);
+int mpcmmd_world_validation_inputs(mpcmmd_world* w, float* acc, float* steer, float* st0, float* path, float* x_obs,
+                                   float* y_obs, uint32_t* keys);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,17 @@ with ``--noise beta``) and, with
 -clear, the lane-departure share and the mean progress, each as mean +- sample
 standard deviation over the episodes.
 
+With ``--validate R [--alpha A] [--risk-sigma s ...]`` every tick's plan is also
+rolled out under R fresh noise rows (on the GPU inside
+the chained loop, or from the host with ``--host-step``; the files are equal
+again).  The npz then also holds ``val_counts`` (count, count_lane, count_rows),
+``val_count_pos``, ``val_var``, ``val_cvar``, ``val_mean``, ``val_max`` [T, E, 3]
+(channels obs, lane_lb, lane_ub), ``val_mmd`` [T, E, 3, S] and ``val_est``
+[T, E, 2] (the cost_lane and cost_obs the solve itself estimated), and a second
+line per cost gives, over the live (tick, episode) pairs, the plans' mean
+Monte-Carlo collision probability count_rows / R and the mean validated CVaR of
+the obstacle cost beside the mean of the solver's own obstacle cost.
+
 The episode runner is a parameter of ``closed_loop`` (``run=``), so the
 accounting is testable without a GPU.
 """
@@ -43,6 +54,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 COSTS = ("mmd", "cvar", "det")
 V_DES = 10.0
 LOG_KEYS = ("log_d", "log_f", "log_i", "done_tick", "collided", "goal")
+VAL_KEYS = ("val_counts", "val_count_pos", "val_var", "val_cvar", "val_mean", "val_max", "val_mmd", "val_est")
 
 
 def _replay():
@@ -102,11 +114,30 @@ def summarise(res):
                 progress=_mean_std(log_d[last, np.arange(E), 2] - log_d[0, :, 2] if T else np.zeros(E)))
 
 
+def summarise_validation(res, rollouts):
+    """The three figures of one cost's validated plans, each (mean, sample sd)
+    over the episodes of the episode's mean over its live ticks (``summarise``'s
+    convention: rows after ``done_tick`` are left out): the Monte-Carlo
+    collision probability count_rows / R, the validated CVaR of the obstacle
+    cost, and the obstacle cost the solver estimated."""
+    T, E = res["val_counts"].shape[:2]
+    done = np.asarray(res["done_tick"])
+    last = np.where(done >= 0, done, T - 1)
+    live = np.arange(T)[:, None] <= last[None, :]
+    n = np.maximum(live.sum(axis=0), 1)
+    per_episode = lambda a: np.where(live, np.asarray(a, np.float64), 0.0).sum(axis=0) / n
+    return dict(p_collision=_mean_std(per_episode(res["val_counts"][:, :, 2] / float(rollouts))),
+                cvar_obs=_mean_std(per_episode(res["val_cvar"][:, :, 0])),
+                est_obs=_mean_std(per_episode(res["val_est"][:, :, 1])))
+
+
 def closed_loop(prob, costs, route, goal_index, vehicles, starts, ticks, out_dir=None, run=None, log=print, **kw):
     """Runs ``run(prob, cost, route, goal_index, vehicles, starts, ticks, **kw)``
     (default: ``prob.run_episodes``) per cost, writes the files and prints the
     lines of the module docstring.  Returns {cost: (the result, its summary)}."""
     run = run or _run
+    val = kw.get("validate")
+    keys = LOG_KEYS + (VAL_KEYS if val is not None else ())
     results = {}
     for cost in costs:
         if cost not in COSTS:
@@ -114,13 +145,20 @@ def closed_loop(prob, costs, route, goal_index, vehicles, starts, ticks, out_dir
         res = run(prob, cost, route, goal_index, vehicles, starts, ticks, **kw)
         if out_dir is not None:
             os.makedirs(out_dir, exist_ok=True)
-            np.savez(os.path.join(out_dir, f"closed_loop_{cost}.npz"), **{k: res[k] for k in LOG_KEYS})
+            np.savez(os.path.join(out_dir, f"closed_loop_{cost}.npz"), **{k: res[k] for k in keys})
         s = summarise(res)
         E = np.asarray(res["done_tick"]).size
         log(f"{cost}: {E} episodes x {int(ticks)} ticks, collision share = {s['collision'][0]:.4f} +- "
             f"{s['collision'][1]:.4f}, mean min -clear = {s['min_neg_clear'][0]:.4f} +- {s['min_neg_clear'][1]:.4f}, "
             f"lane departure share = {s['lane_departure'][0]:.4f} +- {s['lane_departure'][1]:.4f}, "
             f"mean progress = {s['progress'][0]:.2f} +- {s['progress'][1]:.2f} m")
+        if val is not None:
+            sv = summarise_validation(res, val["rollouts"])
+            s.update(sv)
+            log(f"{cost}: plans under {int(val['rollouts'])} fresh noise rows, mean collision probability = "
+                f"{sv['p_collision'][0]:.4f} +- {sv['p_collision'][1]:.4f}, mean validated CVaR(obs) = "
+                f"{sv['cvar_obs'][0]:.4f} +- {sv['cvar_obs'][1]:.4f}, mean solver cost_obs = "
+                f"{sv['est_obs'][0]:.4f} +- {sv['est_obs'][1]:.4f}")
         results[cost] = (res, s)
     return results
 
@@ -146,6 +184,10 @@ def main(argv=None):
     ap.add_argument("--num-batch", type=int, default=100)
     ap.add_argument("--maxiter-cem", type=int, default=20)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--validate", type=int, default=None, metavar="R",
+                    help="also roll every tick's plan out under R fresh noise rows (Monte-Carlo risk of the plans)")
+    ap.add_argument("--alpha", type=float, default=0.98, help="quantile level of the validated VaR / CVaR")
+    ap.add_argument("--risk-sigma", type=float, nargs="*", default=[], metavar="s", help="MMD bandwidths (at most 8)")
     a = ap.parse_args(argv)
     if not a.synthetic:
         ap.error("only --synthetic worlds are built in")
@@ -156,9 +198,10 @@ def main(argv=None):
     prob = cem.CEM(a.num_reduced, 1, a.num_obs, a.noise_level, a.num_prime, a.noise, a.town, a.acc_const_noise,
                    a.steer_const_noise, num_batch=a.num_batch, maxiter_cem=a.maxiter_cem, seed=a.seed,
                    max_configs=a.episodes)
+    kw = {} if a.validate is None else dict(validate=dict(rollouts=a.validate, alpha=a.alpha, sigma=a.risk_sigma))
     closed_loop(prob, a.costs, route, goal_index, vehicles, synthetic_starts(route, a.episodes, a.start_spread),
                 a.ticks, a.out, num_path=a.num_path, v_des=V_DES, seed=a.seed, chained=not a.host_step,
-                device_step=False)
+                device_step=False, **kw)
     prob.close()
 
 

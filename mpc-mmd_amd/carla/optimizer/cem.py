@@ -183,7 +183,7 @@ class CEM:
 
     def run_episodes(self, cost, route, vehicles, starts, ticks, *, goal_index=None, num_path=600, mean=None, cov=None,
                      v_des=10.0, dt=0.05, threshold=0.1, u=None, key_base=0, key_stride=100000, seed=0,
-                     device_step=True, chained=False):
+                     device_step=True, chained=False, validate=None):
         """E closed-loop episodes of ``ticks`` ticks on the surrogate world
         (DESIGN.md section 19): each tick all E episodes are ONE batched solve
         through the tick route (E <= max_configs), then one world step turns
@@ -205,11 +205,30 @@ class CEM:
         5 |s_c|) of that tick's controls -- unless u [ticks, E, 4] is given.  Returns log_d [T, E, 3], log_f [T, E, 13], log_i [T, E, 4]
         (``_native.WORLD_LOG_*`` name the columns), done_tick, collided, goal
         [E] and, per tick, cx, cy [T, E, 11], steering [T, E, 4], mean_param
-        [T, E, 8]."""
+        [T, E, 8].
+
+        ``validate`` = dict(rollouts=R, alpha=0.98, sigma=()) adds the
+        Monte-Carlo risk of every tick's plan:
+        ``validate_carla_risk`` of the tick, the plan the solve returned and R
+        fresh noise rows under keys = idx_mpc, as val_counts (count, count_lane,
+        count_rows), val_count_pos, val_var, val_cvar, val_mean, val_max
+        [T, E, 3], val_mmd [T, E, 3, S] and val_est [T, E, 2] (the cost_lane and
+        cost_obs the solve itself estimated).  On the chained route the stage
+        runs inside the loop on the device (mpcmmd_world_validate); on the two
+        host-linked routes each tick's obs and path are read back and the
+        validator is called from the host -- the same bits, the slow way."""
         N = native()
         kinds = {"mmd": "mmd_opt", "cvar": "cvar", "det": "det"}
         if cost not in kinds:
             raise ValueError("cost must be 'mmd', 'cvar' or 'det'")
+        val = None
+        if validate is not None:
+            extra = set(validate) - {"rollouts", "alpha", "sigma"}
+            if extra or "rollouts" not in validate:
+                raise ValueError("validate: dict(rollouts=R, alpha=..., sigma=...)")
+            sg = validate.get("sigma", ())
+            val = dict(rollouts=int(validate["rollouts"]), alpha=float(validate.get("alpha", 0.98)),
+                       sigma=np.asarray(() if sg is None else sg, np.float32).reshape(-1))
         starts = np.asarray(starts, np.float64).reshape(-1, 4)
         E, T = starts.shape[0], int(ticks)
         if E > self.max_configs:
@@ -226,6 +245,8 @@ class CEM:
         if chained:
             world = N.World(tk, model, T)
             try:
+                if val is not None:
+                    world.validate(**val)
                 world.reset(starts[:, :2], np.stack([starts[:, 2], starts[:, 3], np.zeros(E)], 1),
                             np.tile(vehicles[None], (E, 1, 1)), np.tile(mean.reshape(1, 8), (E, 1)), cov, u, keys)
                 k0 = 0
@@ -235,6 +256,8 @@ class CEM:
                 if k0 != T:
                     raise ValueError("chained: the tick counts must add up to ticks")
                 out = world.log(T)
+                if val is not None:
+                    out.update(world.validation_log(T))
             finally:
                 world.close()
             done = np.where(out["done_tick"] >= 0, out["done_tick"], T - 1)
@@ -253,6 +276,11 @@ class CEM:
                    log_i=np.empty((T, E, 4), np.int32), cx=np.empty((T, E, 11), np.float32),
                    cy=np.empty((T, E, 11), np.float32), steering=np.empty((T, E, 4), np.float32),
                    mean_param=np.empty((T, E, 8), np.float32))
+        if val is not None:
+            H, O, S = self.num_prime, self.num_obs, val["sigma"].size
+            out.update(val_counts=np.empty((T, E, 3), np.int32), val_count_pos=np.empty((T, E, 3), np.int32),
+                       val_mmd=np.empty((T, E, 3, S), np.float32), val_est=np.empty((T, E, 2), np.float32))
+            out.update({"val_" + key: np.empty((T, E, 3), np.float32) for key in ("var", "cvar", "mean", "max")})
         for k in range(T):
             idx = [k + int(key) for key in keys]
             rs = tk.solve_batch(kinds[cost], idx, nxt["init_state"], nxt["x_wp"], nxt["y_wp"], nxt["obstacles"],
@@ -262,6 +290,23 @@ class CEM:
             out["steering"][k] = [np.asarray(r["steering"])[:4] for r in rs]
             means = np.array([r["mean_param"] for r in rs], np.float32)
             out["mean_param"][k] = means
+            if val is not None:   # the tick's plan against fresh noise rows, from what the solve left on the device
+                obs = self._h.read("obs", shape=(E, 2, O, H))
+                tracks = np.zeros((2, E, O, 100), np.float32)
+                tracks[:, :, :, :H] = obs.transpose(1, 0, 2, 3)
+                path = self._h.read("path").reshape(-1, 6, N.MAX_PATH)[:E, :, :num_path]
+                c = self._cfg   # the handle's own (fp32) noise scalars
+                r = N.validate_carla_risk(nxt["init_state"], [x["v_best"] for x in rs], [x["steering"] for x in rs],
+                                          tracks[0], tracks[1], path, idx, H, self.noise, float(c.noise_level),
+                                          float(c.acc_const_noise), float(c.steer_const_noise),
+                                          num_rollouts=val["rollouts"], variant=self.variant, seed=c.seed,
+                                          device=c.device, alpha=val["alpha"], sigma=val["sigma"] if S else None,
+                                          counts=True)
+                out["val_counts"][k] = np.stack([r["count"], r["count_lane"], r["count_rows"]], 1)
+                out["val_count_pos"][k], out["val_mmd"][k] = r["count_pos"], r["mmd"]
+                for key in ("var", "cvar", "mean", "max"):
+                    out["val_" + key][k] = r[key]
+                out["val_est"][k] = [[x["cost_lane"], x["cost_obs"]] for x in rs]
             nxt = N.world_step(model, k, out["cx"][k], out["cy"][k], out["steering"][k], None if u is None else u[k],
                                means, st["pos"], st["ego"], st["vehicles"], st["done_tick"], device=dev, keys=keys)
             st = {key: nxt[key] for key in st}

@@ -6,8 +6,14 @@
 // tick context's begin, the CEM iterations and k_world_step on the handle's
 // stream: the kernel reads the handle's result buffers and writes the tick
 // context's input image, st0 and iteration 0's population, so nothing crosses
-// the host between two solves.
+// the host between two solves.  With a validation stage configured
+// (mpcmmd_world_validate) each tick also enqueues, between
+// its CEM iterations and its world step, the Monte-Carlo risk of the plan it
+// just made: k_world_validate_prep packs the validators' inputs from the device
+// buffers the solve used, then mpcmmd_validate_carla_risk's own launches write
+// the tick's row of the validation log.
 #include <array>
+#include <cmath>
 #include <cstring>
 
 #include "handle.hpp"
@@ -16,6 +22,7 @@
 #include "world.hpp"
 #include "world_draw.hpp"
 #include "world_host.hpp"
+#include "world_validate.hpp"
 
 using namespace mpcmmd;
 
@@ -37,6 +44,19 @@ struct mpcmmd_world {
   float* plan = nullptr;    // [Tmax][Emax][34]
   double* chol = nullptr;   // [8][8]
   std::array<double, 64> chol_host{};
+  // the validation stage (off: val_on false, none of the buffers exists)
+  bool val_on = false;
+  size_t val_first = 0;        // its allocations are bufs[val_first ..]
+  int val_S = 0, val_lds = 0;  // bandwidths; the device's LDS per workgroup
+  size_t val_nacc = 0;         // words of cnt_oh | cnt_lane
+  ValidateCarlaParams vv{};    // the packed inputs, the accumulators and the costs
+  ValidateRiskParams vq{};     // the statistics' scratch (the results point into the log per tick)
+  WorldValidateParams vp{};    // the packed inputs once more, as k_world_validate_prep writes them
+  int32_t *vl_count = nullptr, *vl_lane = nullptr, *vl_rows = nullptr;  // [Tmax][Emax]
+  int32_t* vl_pos = nullptr;                                            // [Tmax][Emax][3]
+  float *vl_var = nullptr, *vl_cvar = nullptr, *vl_mean = nullptr, *vl_max = nullptr;  // [Tmax][Emax][3]
+  float* vl_mmd = nullptr;                                              // [Tmax][Emax][3][S]
+  float* vl_est = nullptr;                                              // [Tmax][Emax][2]
 };
 
 namespace {
@@ -75,6 +95,51 @@ void enqueue_step(mpcmmd_world* w, int tick, bool reset) {
   q.chol = w->chol;
   launch_world_step(q, w->E, h->stream);
   HIPC(hipGetLastError());
+}
+
+// the validation stage of tick `tick`, behind its CEM iterations and before its world step (the
+// step overwrites the input image and st0): the packed inputs, the zeroed accumulators, then
+// mpcmmd_validate_carla_risk's launches with K = E and the results pointed at the tick's log row
+void enqueue_validation(mpcmmd_world* w, int tick) {
+  mpcmmd_handle* h = w->h;
+  const TickLayout l = tick_layout_of(w->t);
+  const int T = h->T, E = w->E;
+  const size_t row = size_t(tick) * w->Emax;
+  WorldValidateParams p = w->vp;
+  p.tick = tick;
+  p.res = h->p.results + size_t(T - 1) * kResultStride, p.s_res = T * kResultStride;
+  p.res_steer = h->p.res_steer + size_t(T - 1) * kNum, p.s_steer = T * kNum;
+  p.in = tick_inputs_device(w->t), p.s_in = l.stride;
+  p.path_in = h->p.path, p.obs = h->p.obs;
+  p.key = w->keys_dev;
+  p.est = w->vl_est + row * 2;
+  launch_world_validate_prep(p, E, h->stream);
+  HIPC(hipGetLastError());
+  ValidateCarlaParams v = w->vv;
+  v.K = E;
+  v.count_rows = w->vl_rows + row, v.count = w->vl_count + row, v.count_lane = w->vl_lane + row;
+  HIPC(hipMemsetAsync(v.cnt_oh, 0, w->val_nacc * 4, h->stream));
+  HIPC(hipMemsetAsync(v.count_rows, 0, size_t(E) * 4, h->stream));
+  if (!launch_validate_carla(v, size_t(w->val_lds), h->stream)) throw std::logic_error("world validation: LDS check");
+  HIPC(hipGetLastError());
+  ValidateRiskParams q = w->vq;
+  q.K = E;
+  q.count_pos = w->vl_pos + row * 3;
+  q.var = w->vl_var + row * 3, q.cvar = w->vl_cvar + row * 3;
+  q.mean = w->vl_mean + row * 3, q.vmax = w->vl_max + row * 3;
+  q.mmd = w->val_S ? w->vl_mmd + row * 3 * w->val_S : nullptr;
+  launch_vrisk_stats(q, h->stream);
+  HIPC(hipGetLastError());
+  launch_vrisk_mmd(q, h->stream);
+  HIPC(hipGetLastError());
+}
+
+// frees the validation stage's buffers (the last allocations of the context)
+void drop_validation(mpcmmd_world* w) {
+  if (!w->val_on) return;
+  for (size_t i = w->val_first; i < w->bufs.size(); ++i) (void)hipFree(w->bufs[i]);
+  w->bufs.resize(w->val_first);
+  w->val_on = false;
 }
 
 }  // namespace
@@ -185,6 +250,7 @@ int mpcmmd_world_run(mpcmmd_world* w, int32_t cost_kind, int32_t tick_begin, int
     if (int rc = tick_begin_chained(w->t, E, cost_kind, idx.data(), covs.data(), v_des, threshold)) return rc;
     if (int rc = mpcmmd_iterate(w->h, 0, w->h->T)) return rc;
     if (int rc = guarded([&] {
+          if (w->val_on) enqueue_validation(w, k);
           enqueue_step(w, k, false);
           return MPCMMD_OK;
         }))
@@ -208,6 +274,141 @@ int mpcmmd_world_log(mpcmmd_world* w, int32_t ticks, double* log_d, float* log_f
     };
     back(log_d, w->logd, 3 * 8), back(log_f, w->logf, 13 * 4), back(log_i, w->logi, 4 * 4), back(plan, w->plan, 34 * 4);
     HIPC(hipMemcpy(done_tick, w->q.done, E * 4, hipMemcpyDeviceToHost));
+    return MPCMMD_OK;
+  });
+}
+
+int mpcmmd_world_validate(mpcmmd_world* w, const mpcmmd_world_validation* cfg) {
+  if (!w) return fail(MPCMMD_E_INVALID, "null argument");
+  mpcmmd_handle* h = w->h;
+  const int O = h->O, H = h->H, P = tick_num_path(w->t);
+  ValidateRiskParams q{};
+  if (cfg) {
+    const int R = cfg->num_rollouts, S = cfg->num_sigma;
+    if (R < 1 || R > (1 << 20) || int64_t(R) * H >= (int64_t(1) << 31))
+      return fail(MPCMMD_E_INVALID, "world validation: num_rollouts out of 1..2^20 (and R H < 2^31)");
+    if (!(cfg->alpha >= 0.0f && cfg->alpha <= 1.0f))
+      return fail(MPCMMD_E_INVALID, "world validation: alpha out of [0, 1]");
+    if (S < 0 || S > kRiskMaxSigma) return fail(MPCMMD_E_INVALID, "world validation: num_sigma out of [0, 8]");
+    for (int i = 0; i < S; ++i)
+      if (!(std::isfinite(cfg->sigma[i]) && cfg->sigma[i] > 0.0f))
+        return fail(MPCMMD_E_INVALID, "world validation: every sigma must be finite and > 0");
+    if (!validate_carla_shape_ok(O, H, P))
+      return fail(MPCMMD_E_INVALID, "world validation: the validator takes num_obs <= 32 and num_prime >= 2");
+    q.R = R, q.S = S;
+    if (mpcmmd_quantile_position(R, cfg->alpha, &q.lo, &q.hi, &q.w_lo, &q.w_hi) != MPCMMD_OK)
+      return fail(MPCMMD_E_INVALID, "world validation: quantile position");
+  }
+  const int rc = guarded([&] {
+    check_device(h);
+    HIPC(hipStreamSynchronize(h->stream));  // nothing in flight reads the buffers about to go
+    drop_validation(w);
+    w->reset_done = false;  // the stage changes with the episodes: the next run needs a reset
+    if (!cfg) return MPCMMD_OK;
+    int lds_max = 0;
+    HIPC(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device));
+    const size_t need = validate_carla_lds(O, H, P, true);
+    if (need > size_t(lds_max))
+      return fail(MPCMMD_E_UNSUPPORTED, "world validation: the shape's workgroup needs " + std::to_string(need) +
+                                            " B of LDS, the device has " + std::to_string(lds_max));
+    w->val_first = w->bufs.size();
+    w->val_on = true;  // from here on drop_validation frees what exists
+    const size_t Em = size_t(w->Emax), Tm = size_t(w->Tmax), R = size_t(q.R), S = size_t(q.S);
+    const size_t n3 = 3 * Em, tiles = (R + kRiskTile - 1) / kRiskTile;
+    w->val_S = q.S, w->val_lds = lds_max;
+    const ProblemConsts& pc = h->pc;
+    const mpcmmd_config& c = h->cfg;
+    ValidateCarlaParams& v = w->vv;
+    v = ValidateCarlaParams{};
+    v.O = O, v.H = H, v.R = q.R, v.P = P, v.noise = c.noise, v.seed = c.seed;  // as carla_plan_params (validate_api.hip)
+    v.sigma_acc = v.sigma_steer = c.noise_level;
+    v.K_steer = float(pc.K_steer * double(c.noise_level));
+    v.acc_const = c.acc_const_noise, v.steer_const = c.steer_const_noise;
+    v.y_lb = float(pc.y_lb), v.y_ub = float(pc.y_ub), v.wheel_base = float(pc.wheel_base);
+    v.obs_a2 = float(pc.a_obs * pc.a_obs), v.obs_b2 = float(pc.b_obs * pc.b_obs);
+    v.init_mu_x = float(pc.init_mu_x), v.init_mu_y = float(pc.init_mu_y);
+    v.init_sigma_x = float(pc.init_sigma_x), v.init_sigma_y = float(pc.init_sigma_y);
+    WorldValidateParams& p = w->vp;
+    p = WorldValidateParams{};
+    p.H = H, p.O = O, p.P = P;
+    p.pd = world_alloc<double>(w, size_t(kNum) * kNvar, pc.Pd.data());
+    v.acc = p.acc = world_alloc<float>(w, Em * H), v.steer = p.steer = world_alloc<float>(w, Em * H);
+    v.st0 = p.st0 = world_alloc<float>(w, Em * 8), v.path = p.path = world_alloc<float>(w, Em * 6 * P);
+    v.x_obs = p.x_obs = world_alloc<float>(w, Em * O * kNum), v.y_obs = p.y_obs = world_alloc<float>(w, Em * O * kNum);
+    v.keys = p.keys = world_alloc<uint32_t>(w, Em);
+    const size_t n_oh = Em * O * H;
+    w->val_nacc = n_oh + Em * 2 * H;
+    v.cnt_oh = world_alloc<int32_t>(w, w->val_nacc), v.cnt_lane = v.cnt_oh + n_oh;
+    q.costs = v.costs = world_alloc<float>(w, n3 * R);  // every element is stored by its row's workgroup
+    q.np = world_alloc<int32_t>(w, n3);
+    if (S > 0) {
+      std::vector<float> sg(Em * S);
+      for (size_t i = 0; i < sg.size(); ++i) sg[i] = cfg->sigma[i % S];
+      q.sigma = world_alloc<float>(w, sg.size(), sg.data());
+      q.u = world_alloc<float>(w, n3 * R);
+      q.part = world_alloc<double>(w, n3 * tiles * S);
+    }
+    w->vq = q;
+    const size_t rows = Tm * Em;
+    w->vl_count = world_alloc<int32_t>(w, rows), w->vl_lane = world_alloc<int32_t>(w, rows);
+    w->vl_rows = world_alloc<int32_t>(w, rows), w->vl_pos = world_alloc<int32_t>(w, rows * 3);
+    w->vl_var = world_alloc<float>(w, rows * 3), w->vl_cvar = world_alloc<float>(w, rows * 3);
+    w->vl_mean = world_alloc<float>(w, rows * 3), w->vl_max = world_alloc<float>(w, rows * 3);
+    w->vl_mmd = world_alloc<float>(w, rows * 3 * S), w->vl_est = world_alloc<float>(w, rows * 2);
+    return MPCMMD_OK;
+  });
+  if (rc != MPCMMD_OK) {  // a failed allocation leaves no half-made stage
+    drop_validation(w);
+    (void)hipGetLastError();
+  }
+  return rc;
+}
+
+int mpcmmd_world_validation_log(mpcmmd_world* w, int32_t ticks, int32_t* counts, int32_t* count_pos, float* stats,
+                                float* mmd, float* est) {
+  if (!w || !counts || !count_pos || !stats || !est) return fail(MPCMMD_E_INVALID, "null argument");
+  if (w->val_on && w->val_S > 0 && !mmd) return fail(MPCMMD_E_INVALID, "null argument");
+  if (ticks < 0 || ticks > w->Tmax) return fail(MPCMMD_E_INVALID, "world: tick range");
+  if (!w->val_on) return fail(MPCMMD_E_STATE, "mpcmmd_world_validation_log without a validation stage");
+  return guarded([&] {
+    check_device(w->h);
+    HIPC(hipStreamSynchronize(w->h->stream));
+    if (ticks == 0 || w->E == 0) return MPCMMD_OK;
+    const size_t E = size_t(w->E), Em = size_t(w->Emax), n = size_t(ticks) * E, S = size_t(w->val_S);
+    // rows of Emax -> [ticks][n_episodes]: one strided copy per array
+    auto back = [&](void* dst, const void* src, size_t row_bytes) {
+      HIPC(hipMemcpy2D(dst, E * row_bytes, src, Em * row_bytes, E * row_bytes, size_t(ticks), hipMemcpyDeviceToHost));
+    };
+    std::vector<int32_t> c3(n * 3);
+    back(c3.data(), w->vl_count, 4), back(c3.data() + n, w->vl_lane, 4), back(c3.data() + 2 * n, w->vl_rows, 4);
+    for (size_t i = 0; i < n; ++i)
+      for (size_t k = 0; k < 3; ++k) counts[i * 3 + k] = c3[k * n + i];
+    std::vector<float> s4(n * 12);
+    back(s4.data(), w->vl_var, 12), back(s4.data() + n * 3, w->vl_cvar, 12);
+    back(s4.data() + n * 6, w->vl_mean, 12), back(s4.data() + n * 9, w->vl_max, 12);
+    for (size_t i = 0; i < n; ++i)
+      for (size_t k = 0; k < 4; ++k) std::memcpy(stats + (i * 4 + k) * 3, &s4[(k * n + i) * 3], 12);
+    back(count_pos, w->vl_pos, 12), back(est, w->vl_est, 8);
+    if (S > 0) back(mmd, w->vl_mmd, 12 * S);
+    return MPCMMD_OK;
+  });
+}
+
+int mpcmmd_world_validation_inputs(mpcmmd_world* w, float* acc, float* steer, float* st0, float* path, float* x_obs,
+                                   float* y_obs, uint32_t* keys) {
+  if (!w) return fail(MPCMMD_E_INVALID, "null argument");
+  if (!w->val_on) return fail(MPCMMD_E_STATE, "mpcmmd_world_validation_inputs without a validation stage");
+  return guarded([&] {
+    check_device(w->h);
+    HIPC(hipStreamSynchronize(w->h->stream));
+    const size_t E = size_t(w->E), H = size_t(w->vp.H), O = size_t(w->vp.O), P = size_t(w->vp.P);
+    auto back = [&](void* dst, const void* src, size_t bytes) {
+      if (dst && bytes) HIPC(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    };
+    back(acc, w->vp.acc, E * H * 4), back(steer, w->vp.steer, E * H * 4), back(st0, w->vp.st0, E * 8 * 4);
+    back(path, w->vp.path, E * 6 * P * 4);
+    back(x_obs, w->vp.x_obs, E * O * kNum * 4), back(y_obs, w->vp.y_obs, E * O * kNum * 4);
+    back(keys, w->vp.keys, E * 4);
     return MPCMMD_OK;
   });
 }

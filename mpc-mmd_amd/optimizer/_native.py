@@ -33,7 +33,8 @@ SYMBOLS = (
     "mpcmmd_carla_begin_batch", "mpcmmd_carla_solve_batch", "mpcmmd_tick_create", "mpcmmd_tick_destroy",
     "mpcmmd_carla_tick_begin_batch", "mpcmmd_carla_tick_solve_batch", "mpcmmd_carla_tick_host",
     "mpcmmd_world_step_host", "mpcmmd_world_step_device", "mpcmmd_world_create", "mpcmmd_world_destroy",
-    "mpcmmd_world_reset", "mpcmmd_world_run", "mpcmmd_world_log",
+    "mpcmmd_world_reset", "mpcmmd_world_run", "mpcmmd_world_log", "mpcmmd_world_validate",
+    "mpcmmd_world_validation_log", "mpcmmd_world_validation_inputs",
 )
 
 
@@ -142,6 +143,11 @@ class WorldStepIO(C.Structure):
                  ("key", C.POINTER(C.c_uint32))])
 
 
+class WorldValidation(C.Structure):
+    _fields_ = [("num_rollouts", C.c_int32), ("alpha", C.c_float), ("num_sigma", C.c_int32),
+                ("sigma", C.c_float * 8)]
+
+
 WORLD_LOG_D = ("x", "y", "arc")
 WORLD_LOG_F = ("v", "psi", "psidot", "a_c", "s_c", "a", "s", "u0", "u1", "u2", "u3", "clear", "d")
 WORLD_LOG_I = ("idx", "lane_out", "collided", "goal")
@@ -235,6 +241,10 @@ def lib():
         L.mpcmmd_world_reset.argtypes = [vp, C.c_int32, dp, fp, fp, fp, fp, fp, ip]
         L.mpcmmd_world_run.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp, fp, C.c_float]
         L.mpcmmd_world_log.argtypes = [vp, C.c_int32, dp, fp, ip, fp, ip]
+    if hasattr(L, "mpcmmd_world_validate"):   # an older library lacks the stage: World.validate raises
+        L.mpcmmd_world_validate.argtypes = [vp, C.POINTER(WorldValidation)]
+        L.mpcmmd_world_validation_log.argtypes = [vp, C.c_int32, ip, ip, fp, fp, fp]
+        L.mpcmmd_world_validation_inputs.argtypes = [vp, fp, fp, fp, fp, fp, fp, C.POINTER(C.c_uint32)]
     L.mpcmmd_path_smoothing.argtypes = [C.c_int32, fp, fp, C.c_float, fp, fp]
     L.mpcmmd_path_parameters.argtypes = [C.c_int32, fp, fp, fp, fp, fp, fp, fp, fp, fp]
     L.mpcmmd_global_to_frenet.argtypes = [C.POINTER(Path), C.c_int32, fp, fp, fp, fp, fp, fp, fp]
@@ -701,6 +711,55 @@ class World:
                                        li.ctypes.data_as(ip), _fptr(pl), dn.ctypes.data_as(ip)))
         return dict(log_d=ld, log_f=lf, log_i=li, cx=pl[..., :11].copy(), cy=pl[..., 11:22].copy(),
                     steering=pl[..., 22:26].copy(), mean_param=pl[..., 26:].copy(), done_tick=dn)
+
+    def validate(self, rollouts, alpha=0.98, sigma=()):
+        """mpcmmd_world_validate: from the next ``reset`` on, every tick of ``run`` also computes the
+        Monte-Carlo risk of the plan it made (``validate_carla_risk`` of that tick with ``rollouts``
+        fresh noise rows, quantile level ``alpha`` and the MMD bandwidths ``sigma``, at most 8) into
+        the validation log.  ``rollouts`` None turns the stage off."""
+        if not hasattr(self._L, "mpcmmd_world_validate"):
+            raise NativeError(f"{LIB_PATH} has no mpcmmd_world_validate (built before the entry point existed): "
+                              "rebuild it")
+        self._val_S = 0
+        if rollouts is None:
+            check(self._L.mpcmmd_world_validate(self._w, None))
+            return
+        sg = np.asarray(() if sigma is None else sigma, np.float32).reshape(-1)
+        cfg = WorldValidation(int(rollouts), float(alpha), int(sg.size))
+        for i, v in enumerate(sg[:8]):   # more than 8: num_sigma says so and the library refuses
+            cfg.sigma[i] = float(v)
+        check(self._L.mpcmmd_world_validate(self._w, C.byref(cfg)))
+        self._val_S = int(sg.size)
+
+    def validation_log(self, ticks):
+        """The first ``ticks`` rows of the validation log: val_counts [T, E, 3] (count, count_lane,
+        count_rows of ``validate_carla``), val_count_pos [T, E, 3], val_var, val_cvar, val_mean,
+        val_max [T, E, 3] (channels RISK_CHANNELS), val_mmd [T, E, 3, S] and val_est [T, E, 2]
+        (the cost_lane and cost_obs the solve itself estimated)."""
+        T, E, S = int(ticks), self.E, getattr(self, "_val_S", 0)
+        n = max(T, 0)
+        cn, cp = np.zeros((n, E, 3), np.int32), np.zeros((n, E, 3), np.int32)
+        st, mm = np.zeros((n, E, 4, 3), np.float32), np.zeros((n, E, 3, S), np.float32)
+        es = np.zeros((n, E, 2), np.float32)
+        ip = C.POINTER(C.c_int32)
+        check(self._L.mpcmmd_world_validation_log(self._w, T, cn.ctypes.data_as(ip), cp.ctypes.data_as(ip), _fptr(st),
+                                                  _fptr(mm) if S else None, _fptr(es)))
+        return dict(val_counts=cn, val_count_pos=cp, val_var=st[:, :, 0].copy(), val_cvar=st[:, :, 1].copy(),
+                    val_mean=st[:, :, 2].copy(), val_max=st[:, :, 3].copy(), val_mmd=mm, val_est=es)
+
+    def validation_inputs(self):
+        """The packed inputs of the last validated tick, as the validators read them: acc, steer [E, H],
+        st0 [E, 8], path [E, 6, num_path], x_obs, y_obs [E, O, 100], keys [E] (uint32)."""
+        E, h = self.E, self.tick.handle
+        H, O, P = h.cfg.num_prime, h.cfg.num_obs, self.tick.num_path
+        out = dict(acc=np.zeros((E, H), np.float32), steer=np.zeros((E, H), np.float32),
+                   st0=np.zeros((E, 8), np.float32), path=np.zeros((E, 6, P), np.float32),
+                   x_obs=np.zeros((E, O, 100), np.float32), y_obs=np.zeros((E, O, 100), np.float32),
+                   keys=np.zeros(E, np.uint32))
+        check(self._L.mpcmmd_world_validation_inputs(
+            self._w, *[_fptr(out[k]) for k in ("acc", "steer", "st0", "path", "x_obs", "y_obs")],
+            out["keys"].ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
 
 
 class Tick:
