@@ -414,7 +414,8 @@ int mpcmmd_run_stage(mpcmmd_handle* h, int32_t stage, int32_t t);
  * fp64 values of `name` ("P","Pdot","Pddot" [100][11] (fp32-rounded),
  * "P_prime" [H][11], "guess_kinv_x" [14][14], "guess_kinv_y" [15][15],
  * "proj_kinv_x", "proj_kinv_y", "fit" [11][H], "det_kinv_x", "det_kinv_y"
- * (the CARLA det projection's, for cfg->num_obs obstacles)).  Returns element count, or
+ * (the CARLA det projection's, for cfg->num_obs obstacles), "mpc_scalars" [3] = the
+ * variant's y_lb, y_ub, K_steer (mpcmmd_mpc_model)).  Returns element count, or
  * < 0 on error / when count is too small. */
 int mpcmmd_host_constant(const mpcmmd_config* cfg, const char* name, double* dst, size_t count);
 
@@ -902,6 +903,144 @@ int mpcmmd_world_validation_log(mpcmmd_world* w, int32_t ticks, int32_t* counts,
                                 float* mmd, float* est);
 int mpcmmd_world_validation_inputs(mpcmmd_world* w, float* acc, float* steer, float* st0, float* path, float* x_obs,
                                    float* y_obs, uint32_t* keys);
+
+/* ---- Receding-horizon episodes of the synthetic variants -----------------------
+ * The closed loop of a MPCMMD_VARIANT_STATIC / _DYNAMIC handle (DESIGN.md
+ * section 21): solve, apply the plan's first control under the noise model,
+ * re-solve from where the ego ended up, warm-started from the previous mean.
+ * The world is the optimizer's own rollout model with one realised draw (a
+ * model of this library's: the reference has no synthetic loop):
+ *   controller   compute_controls at step 0: a_c = (v_1 - v_0) / 0.15, s_c =
+ *                atan(2.5 curv), curv = (ydd_0 xd_0 - yd_0 xdd_0) / (s2 sqrt(s2))
+ *   perturbation the optimizer's noisy_from on one draw u[3]
+ *   ego          bicycle_step_cr_t's expression, wheel base 2.5, the model's dt,
+ *                no speed clamp; position in fp64
+ *   vehicles     num_obs rows (x, y, vx, vy), constant velocity, all seen by
+ *                the optimizer; tracks x + vx tt on np.linspace(0, 15, 100)
+ *   flags        clear = max_o (1 - (dx/a)^2 - (dy/b)^2) (-inf without
+ *                vehicles), collided = !(clear <= 0), lane_out = y < y_lb | y >
+ *                y_ub, goal = x >= goal_x; a collided or goal episode is
+ *                frozen: done_tick is set, the state stops, the slot keeps
+ *                being solved on the frozen state (with zero acceleration)
+ * fp32 in the order DESIGN.md states, transcendentals in fp64 rounded once;
+ * every NaN a subtraction may form is stored as 0x7FC00000.
+ *
+ * The variates u[3] are given, or drawn where the controls are known (u NULL):
+ * Philox streams keyed (episode key, seed) at stream ids 45..49 (csrc/rng.hpp),
+ * element = tick.  u0, u1, u2 = normals 0, 1, 2 of block `tick` of stream 45.
+ * beta: u0 ~ Beta(2|a_c|, 5|a_c|) (streams 46, 47), u1 ~ Beta(2|s_c|, 5|s_c|)
+ * (48, 49) by the validators' fp64 sampler with its |control| = 0 limit rule,
+ * rounded once -- the optimizer's beta_pair parameters.  The log row holds the
+ * variates used.
+ *
+ * mpcmmd_mpc_step_host steps one episode on the host (no GPU needed).
+ * mpcmmd_mpc_step_device steps n_episodes (1..65535) independent episodes with
+ * one launch of k_mpc_step (one workgroup per episode, k_mpc.hip) on device
+ * `device`, every array with a leading episode axis; each word it writes is the
+ * host step's (tests/test_gpu_mpc_step.py).  It uploads and reads back every
+ * array: the kernel's reference harness, not a fast path.  ABI version
+ * unchanged: detect the entry points by their symbols.
+ *
+ * Before any HIP call: MPCMMD_E_INVALID for a NULL argument or array, num_obs
+ * outside 0..64, num_batch < 1, a noise other than 0 / 1, dt, a_obs or b_obs
+ * not > 0, n_episodes out of range. */
+typedef struct mpcmmd_mpc_model {
+  int32_t num_obs;   /* vehicles, 0..64 (the context: the handle's num_obs) */
+  int32_t num_batch; /* rows of the first population */
+  int32_t noise;     /* 0 gaussian, 1 beta (u[0], u[1] are then Beta variates) */
+  float dt;          /* tick length (0.15: the rollout step) */
+  float sigma_acc, sigma_steer, acc_const, steer_const; /* the noise model's scalars */
+  float K_steer;     /* float32(K_steer * sigma_steer), as the optimizer holds it (beta noise) */
+  float a_obs, b_obs; /* half axes of the keep-out ellipse (4.25, 2.75) */
+  float y_lb, y_ub;  /* lane bounds of y */
+  float goal_x;      /* the episode ends at x >= goal_x */
+  const double* pdot2;  /* [2][11]: rows 0, 1 of Pdot (mpcmmd_host_constant) */
+  const double* pddot1; /* [11]: row 0 of Pddot */
+  const double* chol;   /* [8][8] lower Cholesky factor of the run's covariance, row-major */
+  const float* pop0;    /* [num_batch][8] standard normals of the first population */
+  uint32_t seed;        /* key word 1 of the drawn variates' Philox streams (the context: the handle's) */
+} mpcmmd_mpc_model;
+
+#define MPCMMD_MPC_LOG_D 2  /* x, y after the step */
+#define MPCMMD_MPC_LOG_F 12 /* vx, vy, psi, a_c, s_c, a, s, u[3], clear, curv */
+#define MPCMMD_MPC_LOG_I 4  /* lane_out, collided, goal, frozen (the step found the episode done) */
+
+typedef struct mpcmmd_mpc_step_io { /* leading axis n_episodes for the device step */
+  /* the plan and the variates of this tick */
+  const float* cx;   /* [11] */
+  const float* cy;   /* [11] */
+  const float* u;    /* [3] the variates, or NULL: drawn from (key, seed, tick) once a_c and s_c are known */
+  const float* mean; /* [8] the CEM mean as the solve left it */
+  /* the episode's state, updated in place unless it is frozen */
+  double* pos;        /* [2] x, y */
+  float* vel;         /* [3] vx, vy, psi */
+  float* vehicles;    /* [num_obs][4] x, y, vx, vy */
+  int32_t* done_tick; /* [1] -1 while the episode runs; the tick that set collided or goal */
+  /* the next tick */
+  float* init_state; /* [6] float(x), float(y), vx, vy, ax, ay */
+  float* x_obs;      /* [num_obs][100] */
+  float* y_obs;
+  float* pop;        /* [num_batch][8] */
+  float* st0;        /* [8] the rollouts' initial state of that init_state (the handle's st0 buffer) */
+  /* the log row */
+  double* log_d;  /* [MPCMMD_MPC_LOG_D] */
+  float* log_f;   /* [MPCMMD_MPC_LOG_F] */
+  int32_t* log_i; /* [MPCMMD_MPC_LOG_I] */
+  const uint32_t* key; /* [1] the episode's key; needed when u is NULL */
+} mpcmmd_mpc_step_io;
+
+int mpcmmd_mpc_step_host(const mpcmmd_mpc_model* m, int32_t tick, const mpcmmd_mpc_step_io* io);
+/* The standard normals [cfg->num_batch][8] a handle of cfg draws for its first population (fixed
+ * key, cfg->seed): the pop0 of a model that steps that handle's loop on the host.  Host only. */
+int mpcmmd_mpc_first_normals(const mpcmmd_config* cfg, float* out);
+int mpcmmd_mpc_step_device(const mpcmmd_mpc_model* m, int32_t device, int32_t n_episodes, int32_t tick,
+                           const mpcmmd_mpc_step_io* io);
+
+/* The chained route: E <= max_configs episodes on a static / dynamic handle
+ * with nothing crossing the host between two solves.  The context owns its
+ * device memory (the episodes' state, the variates, the log, the KKT columns);
+ * num_batch, chol, pop0 and seed of the model are not read: the population is
+ * the handle's, from its own pop0 normals and the Cholesky factor of the
+ * covariance given at reset, the seed the handle's.  Destroy it before its
+ * handle.
+ *
+ * mpcmmd_mpc_reset (synchronous) uploads the start states (pos [E][2], vel
+ * [E][3], vehicles [E][num_obs][4]), the means [E][8] (into the handle's
+ * mean), the covariance [64] (factored on the host as initial_population
+ * factors it), the keys [E] and the variates u [max_ticks][E][3] -- or u NULL:
+ * k_mpc_step draws them -- and runs k_mpc_step once in reset mode (every
+ * episode as if frozen, no controller, no log row), which writes tick 0's
+ * st0, solve_c, obs and first population into the handle's buffers.
+ *
+ * mpcmmd_mpc_run enqueues, per tick of [tick_begin, tick_begin + count): the
+ * chained begin (only idx_mpc, v_des [E] and cov are staged; the lam / s_lane
+ * memsets), the T CEM iterations and k_mpc_step, which reads the plan from the
+ * handle's results of the last iteration and writes the next solve's buffers;
+ * mean stays where k_select left it: the warm start.  Episode e solves tick k
+ * with idx_mpc = k + keys[e].  No device-to-host copy and no synchronisation
+ * beyond the staging-event wait every begin makes.  Ticks run in order; a run
+ * may be split.
+ *
+ * mpcmmd_mpc_log synchronises and reads back the first `ticks` rows: log_d
+ * [ticks][E][2], log_f [ticks][E][12], log_i [ticks][E][4], plan
+ * [ticks][E][30] (cx, cy and mean of the solve the step consumed) and
+ * done_tick [E].  Every row equals the host-stepped loop's (mpcmmd_solve_batch
+ * + mpcmmd_mpc_step_host) bit for bit (tests/test_gpu_mpc_loop.py).
+ *
+ * Before any HIP call: MPCMMD_E_INVALID for a NULL argument, a CARLA handle, a
+ * model out of range or whose num_obs is not the handle's, n_episodes outside
+ * 1..max_configs, a covariance that is not positive definite, a tick range
+ * outside [0, max_ticks]; MPCMMD_E_STATE for a run before a reset;
+ * MPCMMD_E_UNSUPPORTED for mmd_opt on a handle without it. */
+typedef struct mpcmmd_mpc mpcmmd_mpc;
+int mpcmmd_mpc_create(mpcmmd_handle* h, const mpcmmd_mpc_model* m, int32_t max_ticks, mpcmmd_mpc** out);
+void mpcmmd_mpc_destroy(mpcmmd_mpc* c);
+int mpcmmd_mpc_reset(mpcmmd_mpc* c, int32_t n_episodes, const double* pos, const float* vel, const float* vehicles,
+                     const float* mean, const float* cov, const float* u, const int32_t* keys);
+int mpcmmd_mpc_run(mpcmmd_mpc* c, int32_t cost_kind, int32_t tick_begin, int32_t count, const float* cov,
+                   const float* v_des);
+int mpcmmd_mpc_log(mpcmmd_mpc* c, int32_t ticks, double* log_d, float* log_f, int32_t* log_i, float* plan,
+                   int32_t* done_tick);
 
 #ifdef __cplusplus
 }

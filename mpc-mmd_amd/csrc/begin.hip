@@ -65,9 +65,14 @@ void gen_beta_tables(mpcmmd_handle* h) {
 int mpcmmd::begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc,
                        const float* init_state, const float* mean, const float* cov, const float* x_obs,
                        const float* y_obs, const float* v_des, const mpcmmd_draws* draws, const mpcmmd_path* path,
-                       const TickRoute* tick) {
-  if (!h || !idx_mpc || !init_state || !mean || !cov || (!tick && (!x_obs || !y_obs)) || !v_des)
+                       const TickRoute* tick, bool resident) {
+  if (resident) {  // the synthetic closed loop (mpc_api.hip): only idx_mpc, cov and v_des come from the host
+    if (!h || !idx_mpc || !cov || !v_des) return fail(MPCMMD_E_INVALID, "null argument");
+    if (h->carla || path || tick || draws)
+      return fail(MPCMMD_E_INVALID, "the resident begin is the static / dynamic variants' own");
+  } else if (!h || !idx_mpc || !init_state || !mean || !cov || (!tick && (!x_obs || !y_obs)) || !v_des) {
     return fail(MPCMMD_E_INVALID, "null argument");
+  }
   if (h->carla != (path != nullptr || tick != nullptr))
     return fail(MPCMMD_E_INVALID, h->carla ? "CARLA handle: use mpcmmd_carla_begin / mpcmmd_carla_solve (a path is needed)"
                                            : "mpcmmd_carla_begin needs a handle of a CARLA variant");
@@ -138,7 +143,8 @@ int mpcmmd::begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const
     std::vector<double> sc(size_t(G) * 4 * kNvar);
     std::vector<float> st0(size_t(G) * 8), ob(size_t(G) * 2 * O * H), pop(size_t(G) * B * 8);
     const bool det = cost_kind == MPCMMD_COST_DET;  // the det projection's own KKT
-    const bool chained = tick && tick->chained;     // the world route: st0, pop and mean are on the device
+    // the world route: st0, pop and mean are on the device; the resident route: solve_c and obs too
+    const bool chained = (tick && tick->chained) || resident;
     const double* pkx = det ? h->det_kx.data() : h->pc.proj_kinv_x.data();
     const double* pky = det ? h->det_ky.data() : h->pc.proj_kinv_y.data();
     CarlaBatch cb;  // CARLA: the noisy initial rows, path and det track images of every configuration
@@ -168,7 +174,7 @@ int mpcmmd::begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const
       }
       cb = carla_batch(h->pc, G, R, h->R0, O, det, init_state, views.data(), eps.data(), x_obs, y_obs);
     }
-    for (int g = 0; g < G; ++g) {
+    for (int g = 0; g < G && !resident; ++g) {
       const float* is = init_state + size_t(g) * 6;
       // boundary vectors (cem_helper.py:152-167) and the per-solve KKT columns
       double bx[3] = {is[0], is[2], is[4]};
@@ -186,7 +192,7 @@ int mpcmmd::begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const
       if (!chained)
         initial_population(mean + size_t(g) * 8, cov + size_t(g) * 64, z0.data(), B, pop.data() + size_t(g) * B * 8);
     }
-    if (!tick) upload_staged(h, p.solve_c, sc.data(), sc.size() * 8);
+    if (!tick && !resident) upload_staged(h, p.solve_c, sc.data(), sc.size() * 8);
     if (h->carla) {
       // one staged copy per buffer whatever G is (the staging area holds each staged buffer once)
       // (the tick route: k_tick_path and k_tick_setup write the three buffers)
@@ -206,7 +212,7 @@ int mpcmmd::begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const
       }
     }
     if (!chained) upload_staged(h, p.st0, st0.data(), st0.size() * 4);
-    if (!tick) upload_staged(h, p.obs, ob.data(), ob.size() * 4);
+    if (!tick && !resident) upload_staged(h, p.obs, ob.data(), ob.size() * 4);
     if (!chained) {
       upload_staged(h, p.pop, pop.data(), pop.size() * 4);  // iteration 0's half: [0][G B][8]
       upload_staged(h, p.mean, mean, cfg_bytes(h, p.mean, G));

@@ -200,9 +200,14 @@ struct TickRoute {
 
 // mpcmmd_begin for n_cfg configurations (begin.hip).  path: n_cfg paths (the
 // CARLA host route); tick: the CARLA tick route, which takes no path and no
-// obstacle tracks (x_obs, y_obs null) and no external draws.
+// obstacle tracks (x_obs, y_obs null) and no external draws.  resident: the
+// synthetic closed loop's route (mpc_api.hip) for static / dynamic handles, on
+// which st0, solve_c, obs, the first population and the mean are on the device
+// already (k_mpc_step wrote them; init_state, mean, x_obs, y_obs are not read):
+// only idx_mpc, v_des and cov are staged.
 int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc, const float* init_state,
                const float* mean, const float* cov, const float* x_obs, const float* y_obs, const float* v_des,
-               const mpcmmd_draws* draws, const mpcmmd_path* path = nullptr, const TickRoute* tick = nullptr);
+               const mpcmmd_draws* draws, const mpcmmd_path* path = nullptr, const TickRoute* tick = nullptr,
+               bool resident = false);
 
 }  // namespace mpcmmd

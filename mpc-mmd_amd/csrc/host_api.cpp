@@ -124,6 +124,9 @@ int mpcmmd_host_constant(const mpcmmd_config* cfg, const char* name, double* dst
       det_projection_kinv(c, cfg->num_obs, dk[0], dk[1]);
       v = &dk[n == "det_kinv_y" ? 1 : 0];
     }
+    // the variant's scalars the synthetic closed loop's model takes (mpcmmd_mpc_model): y_lb, y_ub, K_steer
+    const std::vector<double> mpc_scalars = {c.y_lb, c.y_ub, c.K_steer};
+    if (n == "mpc_scalars") v = &mpc_scalars;
     if (!v) return fail(MPCMMD_E_INVALID, "unknown constant " + n);
     if (dst) {
       if (count < v->size()) return fail(MPCMMD_E_INVALID, "dst too small");

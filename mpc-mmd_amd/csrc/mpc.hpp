@@ -1,0 +1,47 @@
+// The synthetic closed loop on the device: what k_mpc.hip (the kernel) and
+// mpc_api.hip (the entry points) share.  Internal to the library.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "mpc_step.hpp"
+
+namespace mpcmmd {
+
+constexpr int kMpcThreads = 256;
+
+// k_mpc_step's arguments: the model's arrays, then the per-episode arrays of
+// mpcmmd_mpc_step_io with a leading episode axis, all device pointers.  The
+// plan's episode stride (in floats) is spelled out: the harness gives dense
+// arrays, the chained route (mpc_api.hip) the handle's result buffer.  The
+// tracks go to x_obs / y_obs [E][O][100] (the harness) or, first H points
+// only, to obs [E][2][O][H] (the handle's buffer); solve_c is written where
+// kcol is given.
+struct MpcStepParams {
+  MpcScalars w;
+  int tick;
+  int reset;                       // 1: every episode as if frozen, no controller, no log row, done untouched
+  int s_plan;                      // stride of cx / cy
+  int H;                           // points of a track in obs
+  const uint32_t* key;             // [E] episode keys of the drawn variates (u null), with seed
+  uint32_t seed;
+  const double *pdot2, *pddot1, *chol;  // [2][11], [11], [8][8]
+  const double* kcol;              // [4][11][4] KKT coefficient columns (solve_columns), or null
+  const float* pop0;               // [B][8]
+  const float *cx, *cy, *u, *mean;  // [E][11] (stride s_plan), [E][3] or null (drawn), [E][8]
+  double* pos;                     // [E][2]
+  float* vel;                      // [E][3]
+  float* veh;                      // [E][O][4]
+  int32_t* done;                   // [E]
+  float *init, *st0, *pop;         // [E][6], [E][8], [E][B][8]
+  float *x_obs, *y_obs;            // [E][O][100], or null
+  float* obs;                      // [E][2][O][H], or null
+  double* solve_c;                 // [E][4][11] (with kcol)
+  double* logd;                    // [E][2]
+  float* logf;                     // [E][12]
+  int32_t* logi;                   // [E][4]
+  float* plan;                     // [E][30] cx, cy, mean: the chained route's log of the plan, or null
+};
+
+void launch_mpc_step(const MpcStepParams& q, int episodes, hipStream_t s);
+
+}  // namespace mpcmmd

@@ -50,6 +50,13 @@ enum Stream : uint32_t {
   kStreamWorldGammaAccB = 42,
   kStreamWorldGammaSteerA = 43,
   kStreamWorldGammaSteerB = 44,
+  // the synthetic closed loop's perturbation (mpc_draw.hpp), key (episode key, seed), element = tick: block
+  // `tick` of the normals (u0, u1, u2; Beta noise takes u2 only) and the Beta gammas of u0 (acc) and u1 (steer)
+  kStreamMpcNormal = 45,
+  kStreamMpcGammaAccA = 46,
+  kStreamMpcGammaAccB = 47,
+  kStreamMpcGammaSteerA = 48,
+  kStreamMpcGammaSteerB = 49,
 };
 constexpr uint32_t kFixedKey0 = 0xFFFFFFFFu;
 constexpr int kGammaMaxAttempts = 32;

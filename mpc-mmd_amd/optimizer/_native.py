@@ -35,6 +35,8 @@ SYMBOLS = (
     "mpcmmd_world_step_host", "mpcmmd_world_step_device", "mpcmmd_world_create", "mpcmmd_world_destroy",
     "mpcmmd_world_reset", "mpcmmd_world_run", "mpcmmd_world_log", "mpcmmd_world_validate",
     "mpcmmd_world_validation_log", "mpcmmd_world_validation_inputs",
+    "mpcmmd_mpc_step_host", "mpcmmd_mpc_step_device", "mpcmmd_mpc_create", "mpcmmd_mpc_destroy",
+    "mpcmmd_mpc_reset", "mpcmmd_mpc_run", "mpcmmd_mpc_log", "mpcmmd_mpc_first_normals",
 )
 
 
@@ -148,6 +150,27 @@ class WorldValidation(C.Structure):
                 ("sigma", C.c_float * 8)]
 
 
+class MpcModelStruct(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("num_obs", "num_batch", "noise")] +
+                [(k, C.c_float) for k in ("dt", "sigma_acc", "sigma_steer", "acc_const", "steer_const", "K_steer",
+                                          "a_obs", "b_obs", "y_lb", "y_ub", "goal_x")] +
+                [(k, C.POINTER(C.c_double)) for k in ("pdot2", "pddot1", "chol")] +
+                [("pop0", C.POINTER(C.c_float)), ("seed", C.c_uint32)])
+
+
+class MpcStepIO(C.Structure):
+    _fields_ = ([(k, C.POINTER(C.c_float)) for k in ("cx", "cy", "u", "mean")] +
+                [("pos", C.POINTER(C.c_double)), ("vel", C.POINTER(C.c_float)), ("vehicles", C.POINTER(C.c_float)),
+                 ("done_tick", C.POINTER(C.c_int32))] +
+                [(k, C.POINTER(C.c_float)) for k in ("init_state", "x_obs", "y_obs", "pop", "st0")] +
+                [("log_d", C.POINTER(C.c_double)), ("log_f", C.POINTER(C.c_float)), ("log_i", C.POINTER(C.c_int32)),
+                 ("key", C.POINTER(C.c_uint32))])
+
+
+MPC_LOG_D = ("x", "y")
+MPC_LOG_F = ("vx", "vy", "psi", "a_c", "s_c", "a", "s", "u0", "u1", "u2", "clear", "curv")
+MPC_LOG_I = ("lane_out", "collided", "goal", "frozen")
+
 WORLD_LOG_D = ("x", "y", "arc")
 WORLD_LOG_F = ("v", "psi", "psidot", "a_c", "s_c", "a", "s", "u0", "u1", "u2", "u3", "clear", "d")
 WORLD_LOG_I = ("idx", "lane_out", "collided", "goal")
@@ -245,6 +268,18 @@ def lib():
         L.mpcmmd_world_validate.argtypes = [vp, C.POINTER(WorldValidation)]
         L.mpcmmd_world_validation_log.argtypes = [vp, C.c_int32, ip, ip, fp, fp, fp]
         L.mpcmmd_world_validation_inputs.argtypes = [vp, fp, fp, fp, fp, fp, fp, C.POINTER(C.c_uint32)]
+    if hasattr(L, "mpcmmd_mpc_step_host"):   # an older library lacks the synthetic loop: mpc_step raises
+        dp = C.POINTER(C.c_double)
+        L.mpcmmd_mpc_step_host.argtypes = [C.POINTER(MpcModelStruct), C.c_int32, C.POINTER(MpcStepIO)]
+        L.mpcmmd_mpc_step_device.argtypes = [C.POINTER(MpcModelStruct), C.c_int32, C.c_int32, C.c_int32,
+                                             C.POINTER(MpcStepIO)]
+        L.mpcmmd_mpc_create.argtypes = [vp, C.POINTER(MpcModelStruct), C.c_int32, C.POINTER(vp)]
+        L.mpcmmd_mpc_destroy.argtypes = [vp]
+        L.mpcmmd_mpc_destroy.restype = None
+        L.mpcmmd_mpc_reset.argtypes = [vp, C.c_int32, dp, fp, fp, fp, fp, fp, ip]
+        L.mpcmmd_mpc_run.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp, fp]
+        L.mpcmmd_mpc_log.argtypes = [vp, C.c_int32, dp, fp, ip, fp, ip]
+        L.mpcmmd_mpc_first_normals.argtypes = [C.POINTER(Config), fp]
     L.mpcmmd_path_smoothing.argtypes = [C.c_int32, fp, fp, C.c_float, fp, fp]
     L.mpcmmd_path_parameters.argtypes = [C.c_int32, fp, fp, fp, fp, fp, fp, fp, fp, fp]
     L.mpcmmd_global_to_frenet.argtypes = [C.POINTER(Path), C.c_int32, fp, fp, fp, fp, fp, fp, fp]
@@ -760,6 +795,167 @@ class World:
             self._w, *[_fptr(out[k]) for k in ("acc", "steer", "st0", "path", "x_obs", "y_obs")],
             out["keys"].ctypes.data_as(C.POINTER(C.c_uint32))))
         return out
+
+
+class MpcModel:
+    """mpcmmd_mpc_model: the constants of the synthetic closed loop (DESIGN.md
+    section 21).  ``cfg`` gives the noise kind and scalars, num_obs, num_batch,
+    the seed and, through ``host_constant``, the rows of Pdot / Pddot and the
+    variant's y_lb, y_ub, K_steer; keywords override.  cov the run's [8, 8]
+    covariance (factored here as ``initial_population`` factors it), pop0
+    [B, 8] standard normals (the host-linked routes: ``Handle.pop0``)."""
+
+    def __init__(self, cfg, cov, pop0, goal_x, dt=0.15, a_obs=4.25, b_obs=2.75, **over):
+        v = dict(zip(("y_lb", "y_ub", "K_steer"), host_constant(cfg, "mpc_scalars")))
+        self.cfg = cfg
+        self.num_obs, self.num_batch = int(over.pop("num_obs", cfg.num_obs)), int(cfg.num_batch)
+        noise = over.pop("noise", cfg.noise)
+        noise = NOISE[noise] if isinstance(noise, str) else int(noise)
+        f = np.float32
+        lvl = f(cfg.noise_level)
+        p = dict(dt=f(dt), sigma_acc=lvl, sigma_steer=lvl, acc_const=f(cfg.acc_const_noise),
+                 steer_const=f(cfg.steer_const_noise), K_steer=f(v["K_steer"] * float(lvl)), a_obs=f(a_obs),
+                 b_obs=f(b_obs), y_lb=f(v["y_lb"]), y_ub=f(v["y_ub"]), goal_x=f(goal_x))
+        seed = int(over.pop("seed", cfg.seed)) & 0xFFFFFFFF
+        for k, val in over.items():
+            if k not in p:
+                raise TypeError(f"MpcModel: unknown keyword {k}")
+            p[k] = f(val)
+        self.scalars = p
+        self.noise, self.seed = noise, seed
+        pd = host_constant(cfg, "Pdot").reshape(-1, 11)
+        pdd = host_constant(cfg, "Pddot").reshape(-1, 11)
+        self.arrays = dict(pdot2=np.ascontiguousarray(pd[:2]), pddot1=np.ascontiguousarray(pdd[0]),
+                           chol=np.ascontiguousarray(np.linalg.cholesky(
+                               np.asarray(cov, np.float32).astype(np.float64).reshape(8, 8))))
+        self.pop0 = np.ascontiguousarray(np.asarray(pop0, np.float32).reshape(-1, 8))
+        if self.pop0.shape[0] != self.num_batch:
+            raise ValueError("MpcModel: pop0 must be [num_batch, 8]")
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        self.c = MpcModelStruct(self.num_obs, self.num_batch, noise,
+                                *(float(p[k]) for k in ("dt", "sigma_acc", "sigma_steer", "acc_const", "steer_const",
+                                                        "K_steer", "a_obs", "b_obs", "y_lb", "y_ub", "goal_x")),
+                                *(dp(self.arrays[k]) for k in ("pdot2", "pddot1", "chol")), _fptr(self.pop0), seed)
+
+
+def pop0_normals(cfg):
+    """mpcmmd_mpc_first_normals: the standard normals [B, 8] a handle of ``cfg`` draws for its first
+    population (the pop0 of a model that steps that handle's loop on the host)."""
+    out = np.empty((int(cfg.num_batch), 8), np.float32)
+    check(lib().mpcmmd_mpc_first_normals(C.byref(cfg), _fptr(out)))
+    return out
+
+
+def mpc_step(model, tick, cx, cy, u, mean, pos, vel, vehicles, done_tick, device=None, keys=None):
+    """One step of E episodes of the synthetic closed loop: mpcmmd_mpc_step_host
+    per episode (device None), or one k_mpc_step launch on GPU ``device``
+    (mpcmmd_mpc_step_device).  cx, cy [E, 11], u [E, 3] -- or None: drawn by the
+    library from (keys [E], the model's seed, tick) once the controls are known
+    -- mean [E, 8]; the state pos [E, 2] float64, vel [E, 3] = vx, vy, psi,
+    vehicles [E, num_obs, 4], done_tick [E] is not modified.  Returns a dict:
+    the new state under the same names, the next tick's init_state [E, 6], st0
+    [E, 8], x_obs, y_obs [E, O, 100], pop [E, B, 8] and the log row log_d
+    [E, 2], log_f [E, 12], log_i [E, 4] (MPC_LOG_D / _F / _I name the columns)."""
+    L = lib()
+    if not hasattr(L, "mpcmmd_mpc_step_host"):
+        raise NativeError(f"{LIB_PATH} has no mpcmmd_mpc_step_host (built before the entry point existed): rebuild it")
+    E = np.asarray(pos).reshape(-1, 2).shape[0]
+    m = model
+    f = lambda a, *sh: np.array(np.asarray(a, np.float32).reshape(E, *sh), np.float32, order="C")
+    if u is None and keys is None:
+        raise ValueError("mpc_step: give the variates u or the episodes' keys")
+    O = m.num_obs
+    a = dict(cx=f(cx, 11), cy=f(cy, 11), u=np.zeros((0, 3), np.float32) if u is None else f(u, 3),
+             key=np.zeros(0, np.uint32) if keys is None else
+             np.array(np.asarray(keys, np.int64).reshape(E) & 0xFFFFFFFF, np.uint32),
+             mean=f(mean, 8), pos=np.array(np.asarray(pos, np.float64).reshape(E, 2), order="C"), vel=f(vel, 3),
+             vehicles=f(vehicles, O, 4), done_tick=np.array(np.asarray(done_tick).reshape(E), np.int32, order="C"),
+             init_state=np.empty((E, 6), np.float32), st0=np.empty((E, 8), np.float32),
+             x_obs=np.empty((E, O, 100), np.float32), y_obs=np.empty((E, O, 100), np.float32),
+             pop=np.empty((E, m.num_batch, 8), np.float32), log_d=np.empty((E, 2), np.float64),
+             log_f=np.empty((E, 12), np.float32), log_i=np.empty((E, 4), np.int32))
+    names = [k for k, _ in MpcStepIO._fields_]
+    types = dict(MpcStepIO._fields_)
+
+    def io_of(e):
+        ptr = []
+        for k in names:
+            row = a[k][e:]   # the device call takes episode 0's address with every episode behind it
+            ptr.append(C.cast(row.ctypes.data, types[k]) if row.size else None)
+        return MpcStepIO(*ptr)
+
+    if device is None:
+        for e in range(E):
+            check(L.mpcmmd_mpc_step_host(C.byref(m.c), int(tick), C.byref(io_of(e))))
+    else:
+        check(L.mpcmmd_mpc_step_device(C.byref(m.c), int(device), E, int(tick), C.byref(io_of(0))))
+    for k in ("cx", "cy", "u", "mean", "key"):
+        del a[k]
+    return a
+
+
+class Mpc:
+    """Owns one mpcmmd_mpc: the chained closed loop of a static / dynamic
+    ``handle`` on ``model`` for up to ``max_ticks`` ticks.  ``reset`` takes the
+    episodes' start states, ``run(cost, tick_begin, count)`` enqueues begin, CEM
+    and k_mpc_step per tick with nothing crossing the host, ``log(ticks)``
+    performs the one readback.  Close it before its handle."""
+
+    def __init__(self, handle, model, max_ticks):
+        self._L = lib()
+        if not hasattr(self._L, "mpcmmd_mpc_create"):
+            raise NativeError(f"{LIB_PATH} has no mpcmmd_mpc_create (built before the entry point existed): rebuild it")
+        self.handle, self.model, self.max_ticks = handle, model, int(max_ticks)
+        c = C.c_void_p()
+        check(self._L.mpcmmd_mpc_create(handle._h, C.byref(model.c), self.max_ticks, C.byref(c)))
+        self._c = c
+        self.E = 0
+        handle._ticks.append(self)   # Handle.close frees its contexts first
+
+    def close(self):
+        if getattr(self, "_c", None):
+            self._L.mpcmmd_mpc_destroy(self._c)
+            self._c = None
+            if self in self.handle._ticks:
+                self.handle._ticks.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, pos, vel, vehicles, mean, cov, u, keys):
+        """pos [E, 2] float64, vel [E, 3] = vx, vy, psi, vehicles [E, num_obs, 4], mean [E, 8], cov
+        [8, 8], keys [E] (episode e solves tick k with idx_mpc = k + keys[e]), u [max_ticks, E, 3] or
+        None: the kernel draws each tick's variates from (keys[e], the handle's seed, tick)."""
+        pos = np.ascontiguousarray(np.asarray(pos, np.float64).reshape(-1, 2))
+        E = self.E = pos.shape[0]
+        f = lambda a, *sh: np.ascontiguousarray(np.asarray(a, np.float32).reshape(*sh))
+        veh = f(vehicles, E, self.model.num_obs, 4)
+        kk = np.ascontiguousarray(np.asarray(keys, np.int64).reshape(E).astype(np.int32))
+        check(self._L.mpcmmd_mpc_reset(self._c, E, pos.ctypes.data_as(C.POINTER(C.c_double)), _fptr(f(vel, E, 3)),
+                                       _fptr(veh) if veh.size else None, _fptr(f(mean, E, 8)), _fptr(f(cov, 64)),
+                                       None if u is None else _fptr(f(u, self.max_ticks, E, 3)),
+                                       kk.ctypes.data_as(C.POINTER(C.c_int32))))
+        self.handle._G = E
+
+    def run(self, cost, tick_begin, count, cov, v_des):
+        f = lambda a, *sh: np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32), sh))
+        check(self._L.mpcmmd_mpc_run(self._c, COST[cost], int(tick_begin), int(count),
+                                     _fptr(np.ascontiguousarray(np.asarray(cov, np.float32).reshape(64))),
+                                     _fptr(f(np.asarray(v_des, np.float32).reshape(-1), self.E))))
+
+    def log(self, ticks):
+        """The first ``ticks`` rows: dict of log_d, log_f, log_i, cx, cy, mean, done_tick."""
+        T, E = int(ticks), self.E
+        ld, lf = np.empty((T, E, 2), np.float64), np.empty((T, E, 12), np.float32)
+        li, pl, dn = np.empty((T, E, 4), np.int32), np.empty((T, E, 30), np.float32), np.empty(E, np.int32)
+        ip = C.POINTER(C.c_int32)
+        check(self._L.mpcmmd_mpc_log(self._c, T, ld.ctypes.data_as(C.POINTER(C.c_double)), _fptr(lf),
+                                     li.ctypes.data_as(ip), _fptr(pl), dn.ctypes.data_as(ip)))
+        return dict(log_d=ld, log_f=lf, log_i=li, cx=pl[..., :11].copy(), cy=pl[..., 11:22].copy(),
+                    mean=pl[..., 22:].copy(), done_tick=dn)
 
 
 class Tick:

@@ -13,8 +13,10 @@ the MI355X through libmpcmmd.so (no JAX).  Constructor and methods keep the
 reference's names, argument meaning and return tuples; extra keyword-only
 options: ``num_batch`` (reference hard-codes 100, cem.py:137), ``variant``
 ("static" / "dynamic": the two constants that differ in
-synthetic_dynamic_obs), ``maxiter_cem``, ``device``, ``seed``; per call
-``draws`` (explicit standard normals, see include/mpcmmd.h) and ``trace``.
+synthetic_dynamic_obs), ``maxiter_cem``, ``device``, ``seed``, ``max_configs`` (configurations the
+handle holds: the episodes of ``run_episodes``); per call ``draws`` (explicit
+standard normals, see include/mpcmmd.h) and ``trace``.  ``run_episodes`` is
+this package's own: the receding-horizon loop of DESIGN.md section 21.
 """
 from __future__ import annotations
 
@@ -33,7 +35,7 @@ def _default_device():
 class CEM:
     def __init__(self, num_reduced, num_obs, noise_level, num_prime, noise, acc_const_noise,
                  steer_const_noise, *, num_batch=100, variant="static", maxiter_cem=20, device=None,
-                 seed=0):
+                 seed=0, max_configs=1):
         if noise not in _native.NOISE:
             raise ValueError("noise must be 'gaussian' or 'beta'")
         self.noise = noise
@@ -81,7 +83,7 @@ class CEM:
         self.Pddot_jax = self.Pddot.astype(np.float32)
         self.nvar = 11
         self.cem_helper = Helper(self)
-        self._h = _native.Handle(self._cfg)
+        self._h = _native.Handle(self._cfg, max_configs=int(max_configs))
 
     # ------------------------------------------------------------------
     def _solve(self, cost, idx_mpc, init_state, mean_param_init, cov_param_init, x_obs_traj, y_obs_traj,
@@ -117,6 +119,82 @@ class CEM:
         """cem.py:590-714 -> (cx_best, cy_best, saa_lane, saa_obs)."""
         return self._solve("saa", idx_mpc, init_state, mean_param_init, cov_param_init, x_obs_traj,
                            y_obs_traj, v_des, **kw)
+
+    # ------------------------------------------------------------------
+    def run_episodes(self, cost, vehicles, starts, ticks, *, chained=True, device_step=None, u=None, key_base=0,
+                     keys=None, goal_x=200.0, mean=None, cov=None, v_des=15.0, dt=0.15):
+        """E closed-loop episodes of ``ticks`` ticks in lockstep: solve, apply
+        the plan's first control under the noise model, re-solve from the new state, warm-started
+        from the previous mean.  vehicles [E, num_obs, 4] = x, y, vx, vy; starts [E, 4] = x, y, vx, vy
+        of the ego (a fifth column gives the heading, else atan2(vy, vx)); E <= ``max_configs``.
+        u [ticks, E, 3] gives the perturbation variates, None has the step draw them from (keys[e],
+        seed, tick); episode e solves tick k with idx_mpc = k + keys[e], keys = key_base + 100003 e
+        unless given.
+
+        chained=True runs everything on the GPU with one readback (``_native.Mpc``); a tuple of counts
+        splits that run (``run(0, c0)``, ``run(c0, c1)``, ...); False links the ticks through the host:
+        ``solve_batch``, the mean read back through ``Handle.read("mean")``, and ``mpc_step`` on the
+        host (device_step None) or by the kernel on GPU ``device_step``.  All routes return the same
+        bits: a dict of log_d [ticks, E, 2], log_f [ticks, E, 12], log_i [ticks, E, 4]
+        (``_native.MPC_LOG_*`` name the columns), every tick's cx, cy [ticks, E, 11] and mean
+        [ticks, E, 8], and done_tick [E]."""
+        h, cfg = self._h, self._cfg
+        ticks = int(ticks)
+        starts = np.asarray(starts, np.float64)
+        starts = starts.reshape(-1, starts.shape[-1])
+        E = starts.shape[0]
+        if E < 1 or E > h.max_configs:
+            raise ValueError(f"{E} episodes: the handle holds 1..{h.max_configs} (CEM(..., max_configs=))")
+        f32 = np.float32
+        veh = np.ascontiguousarray(np.asarray(vehicles, f32).reshape(E, self.num_obs, 4))
+        pos = np.ascontiguousarray(starts[:, :2])
+        vxy = starts[:, 2:4].astype(f32)
+        psi = starts[:, 4].astype(f32) if starts.shape[1] > 4 else np.arctan2(vxy[:, 1].astype(np.float64),
+                                                                               vxy[:, 0].astype(np.float64)).astype(f32)
+        vel = np.ascontiguousarray(np.concatenate([vxy, psi[:, None]], 1))
+        mean = np.array([15.0] * 4 + [0.0] * 4, f32) if mean is None else np.asarray(mean, f32)
+        mean = np.ascontiguousarray(np.broadcast_to(mean.reshape(-1, 8), (E, 8)))
+        cov = np.diag([20.0] * 4 + [100.0] * 4).astype(f32) if cov is None else np.asarray(cov, f32).reshape(8, 8)
+        keys = (int(key_base) + 100003 * np.arange(E)) if keys is None else np.asarray(keys, np.int64).reshape(E)
+        if u is not None:
+            u = np.ascontiguousarray(np.asarray(u, f32).reshape(ticks, E, 3))
+        model = _native.MpcModel(cfg, cov, _native.pop0_normals(cfg), goal_x=goal_x, dt=dt, a_obs=self.a_obs,
+                                 b_obs=self.b_obs)
+        if chained is not False:
+            counts = (ticks,) if chained is True else tuple(int(c) for c in chained)
+            if sum(counts) != ticks:
+                raise ValueError("run_episodes: the chained counts must add up to ticks")
+            ctx = _native.Mpc(h, model, max(ticks, 1))
+            try:
+                ctx.reset(pos, vel, veh, mean, cov, u, keys)
+                k = 0
+                for c in counts:
+                    ctx.run(cost, k, c, cov, v_des)
+                    k += c
+                return ctx.log(ticks)
+            finally:
+                ctx.close()
+        out = dict(log_d=np.empty((ticks, E, 2)), log_f=np.empty((ticks, E, 12), f32),
+                   log_i=np.empty((ticks, E, 4), np.int32), cx=np.empty((ticks, E, 11), f32),
+                   cy=np.empty((ticks, E, 11), f32), mean=np.empty((ticks, E, 8), f32))
+        done = np.full(E, -1, np.int32)
+        zero = np.zeros((E, 11), f32)
+        # tick 0's inputs: the step of a frozen episode writes the inputs of the state it is given
+        st = _native.mpc_step(model, -1, zero, zero, np.zeros((E, 3), f32), mean, pos, vel, veh, np.zeros(E, np.int32),
+                              device=device_step)
+        for k in range(ticks):
+            res = h.solve_batch(cost, [int(np.int32(np.uint32((k + int(q)) & 0xFFFFFFFF))) for q in keys],
+                                st["init_state"], mean, cov, st["x_obs"], st["y_obs"], v_des)
+            mean = h.read("mean", shape=(E, 8)).copy()
+            cx, cy = np.stack([r["cx"] for r in res]), np.stack([r["cy"] for r in res])
+            st = _native.mpc_step(model, k, cx, cy, None if u is None else u[k], mean, pos, vel, veh, done,
+                                  device=device_step, keys=keys)
+            pos, vel, veh, done = st["pos"], st["vel"], st["vehicles"], st["done_tick"]
+            out["cx"][k], out["cy"][k], out["mean"][k] = cx, cy, mean
+            for name in ("log_d", "log_f", "log_i"):
+                out[name][k] = st[name]
+        out["done_tick"] = done
+        return out
 
     @property
     def handle(self):

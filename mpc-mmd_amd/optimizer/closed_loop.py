@@ -1,0 +1,150 @@
+"""Closed-loop MPC episodes of the synthetic variants.
+
+``optimizer.sweep`` solves every configuration once from a standing start and
+``optimizer.validation`` scores that open-loop plan.  Here the plan moves an
+ego: each tick the plan's first control is perturbed by the noise model and
+applied, the ego and the vehicles move, and the next tick is solved from where
+the ego ended up, warm-started from the previous mean (``CEM.run_episodes``).
+The world is the optimizer's own rollout model with one realised draw.  E
+independent episodes run in lockstep on one batch handle; by default the whole
+loop is enqueued on the GPU (mpcmmd_mpc_run: per tick the chained begin, the
+CEM iterations and k_mpc_step, nothing crossing the host, one readback of the
+log at the end).  With ``--host-step`` each tick is one batched solve
+(mpcmmd_solve_batch) and one host step (mpcmmd_mpc_step_host); the files are
+equal.
+
+    cd mpc-mmd_amd
+    python -m optimizer.closed_loop --variant static --episodes 8 --ticks 100 \\
+        --costs mmd_opt mmd_random cvar saa --out stats
+
+Episode e is configuration e of the sweep's scenario generator
+(``sweep.obstacles``): its obstacle positions and, for the dynamic variant, the
+generator's initial velocities, which the world keeps constant (the dynamic
+generator's lane-tracking QP is not re-planned).  The ego starts as the sweep
+starts it.  Episodes also differ by their key (the solver's streams and the
+perturbation's variates, which the library draws after each tick's solve:
+normals, or Beta(2 |control|, 5 |control|) with ``--noise beta``).  Per cost
+``closed_loop_<cost>.npz`` holds ``log_d`` [T, E, 2] (x, y), ``log_f`` [T, E, 12]
+(vx, vy, psi, a_c, s_c, a, s, u[3], clear, curv), ``log_i`` [T, E, 4] (lane_out,
+collided, goal, frozen), every tick's ``cx``, ``cy`` [T, E, 11] and ``mean``
+[T, E, 8], and ``done_tick`` [E]; one line per cost gives the collision share,
+the mean minimum -clear, the lane-departure share and the mean progress in x,
+each as mean +- sample standard deviation over the episodes.
+
+The episode runner is a parameter of ``closed_loop`` (``run=``), so the
+accounting is testable without a GPU.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+
+import numpy as np
+
+COSTS = ("mmd_opt", "mmd_random", "cvar", "saa")
+KEYS = ("log_d", "log_f", "log_i", "cx", "cy", "mean", "done_tick")
+CLEAR, LANE_OUT, COLLIDED = 10, 0, 1   # columns of log_f / log_i (_native.MPC_LOG_F / _I)
+
+
+def scenario(variant, episodes, num_obs):
+    """vehicles [E, num_obs, 4] = x, y, vx, vy and keys [E]: configuration e of the sweep's generator."""
+    from .sweep import obstacles
+    veh = np.zeros((episodes, num_obs, 4), np.float32)
+    keys = np.zeros(episodes, np.int64)
+    for e in range(episodes):
+        ob = obstacles(variant, e, num_obs)
+        veh[e] = np.stack([np.asarray(ob[k], np.float64).reshape(num_obs) for k in ("x", "y", "vx", "vy")], 1)
+        keys[e] = int(ob["idx_mpc"])
+    return veh, keys
+
+
+def starts_of(variant, episodes):
+    """[E, 4] = x, y, vx, vy: the sweep's standing start (sweep.main)."""
+    y0 = 1.75 if variant == "static" else -1.75
+    return np.tile(np.array([0.0, y0, 5.0, 0.0]), (episodes, 1))
+
+
+def _run(prob, cost, vehicles, starts, ticks, **kw):
+    return prob.run_episodes(cost, vehicles, starts, ticks, **kw)
+
+
+def _mean_std(v):
+    v = np.asarray(v, np.float64)
+    return float(v.mean()) if v.size else 0.0, float(v.std(ddof=1)) if v.size > 1 else 0.0
+
+
+def summarise(res):
+    """The four figures of one cost's episodes, each (mean, sample sd) over the
+    episodes.  Rows after an episode's ``done_tick`` repeat its frozen state and
+    are left out."""
+    log_f, log_i, log_d = res["log_f"], res["log_i"], res["log_d"]
+    T, E = log_i.shape[:2]
+    done = np.asarray(res["done_tick"])
+    last = np.where(done >= 0, done, T - 1)
+    live = np.arange(T)[:, None] <= last[None, :]
+    neg_clear = np.where(live, -log_f[:, :, CLEAR].astype(np.float64), np.inf)
+    return dict(collision=_mean_std((log_i[:, :, COLLIDED].astype(bool) & live).any(axis=0).astype(float)),
+                min_neg_clear=_mean_std(neg_clear.min(axis=0) if T else np.zeros(E)),
+                lane_departure=_mean_std((log_i[:, :, LANE_OUT].astype(bool) & live).any(axis=0).astype(float)),
+                progress=_mean_std(log_d[last, np.arange(E), 0] - log_d[0, :, 0] if T else np.zeros(E)))
+
+
+def closed_loop(prob, costs, vehicles, starts, ticks, out_dir=None, run=None, log=print, **kw):
+    """Runs ``run(prob, cost, vehicles, starts, ticks, **kw)`` (default:
+    ``prob.run_episodes``) per cost, writes the files and prints the lines of
+    the module docstring.  Returns {cost: (the result, its summary)}."""
+    run = run or _run
+    results = {}
+    for cost in costs:
+        if cost not in COSTS:
+            raise ValueError(f"cost must be one of {sorted(COSTS)}")
+        res = run(prob, cost, vehicles, starts, ticks, **kw)
+        if out_dir is not None:
+            os.makedirs(out_dir, exist_ok=True)
+            np.savez(os.path.join(out_dir, f"closed_loop_{cost}.npz"), **{k: res[k] for k in KEYS})
+        s = summarise(res)
+        E = np.asarray(res["done_tick"]).size
+        log(f"{cost}: {E} episodes x {int(ticks)} ticks, collision share = {s['collision'][0]:.4f} +- "
+            f"{s['collision'][1]:.4f}, mean min -clear = {s['min_neg_clear'][0]:.4f} +- {s['min_neg_clear'][1]:.4f}, "
+            f"lane departure share = {s['lane_departure'][0]:.4f} +- {s['lane_departure'][1]:.4f}, "
+            f"mean progress = {s['progress'][0]:.2f} +- {s['progress'][1]:.2f} m")
+        results[cost] = (res, s)
+    return results
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="closed-loop MPC episodes of the synthetic variants")
+    ap.add_argument("--variant", default="static", choices=["static", "dynamic"])
+    ap.add_argument("--episodes", type=int, default=8)
+    ap.add_argument("--ticks", type=int, default=100)
+    ap.add_argument("--costs", nargs="+", default=list(COSTS), choices=sorted(COSTS))
+    ap.add_argument("--host-step", action="store_true",
+                    help="solve tick by tick and step the world on the host (mpcmmd_mpc_step_host)")
+    ap.add_argument("--out", default="stats_closed_loop")
+    ap.add_argument("--num-reduced", type=int, default=10)
+    ap.add_argument("--num-obs", type=int, default=3)
+    ap.add_argument("--num-prime", type=int, default=30)
+    ap.add_argument("--noise", default="gaussian", choices=["gaussian", "beta"])
+    ap.add_argument("--noise-level", type=float, default=0.1)
+    ap.add_argument("--acc-const-noise", type=float, default=0.0)
+    ap.add_argument("--steer-const-noise", type=float, default=0.0)
+    ap.add_argument("--num-batch", type=int, default=100)
+    ap.add_argument("--maxiter-cem", type=int, default=20)
+    ap.add_argument("--v-des", type=float, default=15.0)
+    ap.add_argument("--goal-x", type=float, default=200.0)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args(argv)
+    from .cem import CEM
+    prob = CEM(a.num_reduced, a.num_obs, a.noise_level, a.num_prime, a.noise, a.acc_const_noise, a.steer_const_noise,
+               num_batch=a.num_batch, variant=a.variant, maxiter_cem=a.maxiter_cem, seed=a.seed,
+               max_configs=a.episodes)
+    vehicles, keys = scenario(a.variant, a.episodes, a.num_obs)
+    try:
+        closed_loop(prob, a.costs, vehicles, starts_of(a.variant, a.episodes), a.ticks, a.out, keys=keys,
+                    v_des=a.v_des, goal_x=a.goal_x, chained=not a.host_step, device_step=None)
+    finally:
+        prob.handle.close()
+
+
+if __name__ == "__main__":
+    main()
