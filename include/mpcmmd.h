@@ -1042,6 +1042,83 @@ int mpcmmd_mpc_run(mpcmmd_mpc* c, int32_t cost_kind, int32_t tick_begin, int32_t
 int mpcmmd_mpc_log(mpcmmd_mpc* c, int32_t ticks, double* log_d, float* log_f, int32_t* log_i, float* plan,
                    int32_t* done_tick);
 
+/* The validation stage of the synthetic chained route:
+ * the Monte-Carlo risk of every tick's plan, computed inside the loop from the
+ * device buffers the solve just used.  (No ABI version change: callers detect
+ * these entry points by their symbols.)
+ *
+ * mpcmmd_mpc_validate configures the stage (cfg NULL: turns it off) and
+ * allocates everything it needs into the context -- the costs [E][3][R], the
+ * MMD scratch, the packed inputs, the fp32 Pdot / Pddot images, the logs
+ * [max_ticks][E]..., one side stream and two events -- so a run allocates
+ * nothing.  It synchronises the handle's stream (and the side stream of a stage
+ * it replaces), and it takes effect at the next mpcmmd_mpc_reset: a run before
+ * that reset is MPCMMD_E_STATE.
+ *
+ * With the stage on, mpcmmd_mpc_run enqueues per tick, in this order: the
+ * resident begin, the T CEM iterations, the stage, k_mpc_step.  The stage is
+ * k_mpc_validate_prep, which packs the validators' inputs on the device (always
+ * on the handle's stream and before the step: the step overwrites the state and
+ * the tracks, the next solve the results), and then the launches of
+ * mpcmmd_validate and mpcmmd_validate_risk unchanged (k_validate, k_vrisk_roll,
+ * the statistics, the MMD) with their results pointed at the tick's log row.
+ * overlap = 0 puts those launches behind the prep on the handle's stream.
+ * overlap = 1 records an event behind the prep, has the context's side stream
+ * wait for it and run the launches there, while the handle's stream goes
+ * straight on to k_mpc_step and the next tick; the next tick's prep first waits
+ * for the side stream's completion event of the previous tick (the packed
+ * inputs, the costs and the scratch are single buffers).  Plain streams and
+ * events: nothing is captured into a graph.  mpcmmd_mpc_validation_log,
+ * mpcmmd_mpc_validation_inputs, mpcmmd_mpc_log, mpcmmd_mpc_reset,
+ * mpcmmd_mpc_destroy and turning the stage off synchronise both streams.  No
+ * device-to-host copy, no host synchronisation and no allocation is added to the
+ * loop, and the solve and the loop's log are what they are without the stage.
+ *
+ * The log row of (tick k, episode e) is, bit for bit, what mpcmmd_validate and
+ * mpcmmd_validate_risk return for num_cfg = 1 with: cx, cy the solve's fp32 cx,
+ * cy widened to fp64; init_state the fp32 (float(x), float(y), vx, vy, ax, ay)
+ * the host-stepped loop hands mpcmmd_solve_batch for that tick, widened (the
+ * validators read words 0..3: the stage packs 0 into words 4, 5); x_obs, y_obs
+ * the tick's tracks (columns >= num_prime zero: the validators read h <
+ * num_prime only); noise, variant, seed, num_prime, num_obs the handle's
+ * configuration; noise_level, acc_const_noise, steer_const_noise the handle's
+ * fp32 fields widened; keys[0] = uint32(k + keys[e]), the tick's idx_mpc; draws
+ * NULL; alpha, sigma from cfg.  The validators' Philox stream ids (24..30,
+ * csrc/rng.hpp) are their own -- the solve draws from streams 0..7 and 16..18,
+ * the step's variates from 45..49 -- so the rows are independent of the
+ * solve's draws and of the step's variates under the same key.  Frozen episodes
+ * are validated like the others (their frozen state and its plan).
+ *
+ * mpcmmd_mpc_validation_log synchronises and reads back the first `ticks` rows:
+ * counts [ticks][E][2] = count, count_lane of mpcmmd_validate; count_pos
+ * [ticks][E][3] per channel (obs, lane_lb, lane_ub); stats [ticks][E][4][3] =
+ * var, cvar, mean, max per channel; mmd [ticks][E][3][num_sigma] (may be NULL
+ * when num_sigma == 0); est [ticks][E][2] = the cost_lane and cost_obs the solve
+ * itself estimated (mpcmmd_result).  mpcmmd_mpc_validation_inputs synchronises
+ * and reads back the packed inputs of the last validated tick (debugging and
+ * tests): cx, cy [E][11], init_state [E][6], x_obs, y_obs [E][num_obs][100],
+ * keys [E]; a NULL array is skipped.
+ *
+ * Before any HIP call: MPCMMD_E_INVALID for a NULL c, num_rollouts outside
+ * 1..2^20, alpha outside [0, 1], num_sigma outside 0..8, a sigma that is not
+ * finite and > 0, an overlap other than 0 or 1, a handle whose num_obs is
+ * outside the validators' 1..32 (the loop itself allows 0..64), a NULL required
+ * log array, a tick range outside [0, max_ticks]; MPCMMD_E_STATE for a log or
+ * inputs readback while the stage is off, and for a run between
+ * mpcmmd_mpc_validate and the next reset. */
+typedef struct mpcmmd_mpc_validation {
+  int32_t num_rollouts; /* R: fresh noise rows per (tick, episode) */
+  float alpha;          /* quantile level of VaR / CVaR */
+  int32_t num_sigma;    /* S, 0..8 */
+  float sigma[8];       /* MMD bandwidths, the same for every episode and tick */
+  int32_t overlap;      /* 0: the stage in-line on the handle's stream; 1: its heavy part on the context's side stream */
+} mpcmmd_mpc_validation;
+int mpcmmd_mpc_validate(mpcmmd_mpc* c, const mpcmmd_mpc_validation* cfg);
+int mpcmmd_mpc_validation_log(mpcmmd_mpc* c, int32_t ticks, int32_t* counts, int32_t* count_pos, float* stats,
+                              float* mmd, float* est);
+int mpcmmd_mpc_validation_inputs(mpcmmd_mpc* c, double* cx, double* cy, double* init_state, float* x_obs,
+                                 float* y_obs, uint32_t* keys);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,13 +6,21 @@
 // (begin.hip), the CEM iterations and k_mpc_step on the handle's stream: the
 // kernel reads the handle's result buffer and writes st0, solve_c, obs and
 // iteration 0's population, so nothing crosses the host between two solves.
+// With a validation stage configured (mpcmmd_mpc_validate)
+// each tick also enqueues, between its CEM iterations and its step, the
+// Monte-Carlo risk of the plan it just made: k_mpc_validate_prep packs the
+// validators' inputs from the device buffers the solve used, then
+// mpcmmd_validate's and mpcmmd_validate_risk's own launches write the tick's row
+// of the validation log, on the handle's stream or on the context's side stream.
 #include <array>
+#include <cmath>
 #include <cstring>
 
 #include "handle.hpp"
 #include "mpc.hpp"
 #include "mpc_draw.hpp"
 #include "mpc_host.hpp"
+#include "mpc_validate.hpp"
 #include "rng.hpp"
 #include "solve_host.hpp"
 
@@ -34,6 +42,21 @@ struct mpcmmd_mpc {
   float* plan = nullptr;    // [Tmax][Emax][30]
   double* chol = nullptr;   // [8][8]
   std::array<double, 64> chol_host{};
+  // the validation stage (off: val_on false, none of the buffers, streams or events exists)
+  bool val_on = false;
+  size_t val_first = 0;       // its allocations are bufs[val_first ..]
+  int val_S = 0;              // bandwidths
+  bool val_overlap = false;   // the validators' launches go to the side stream
+  ValidateRiskParams vq{};    // the packed plan inputs (vq.roll), the costs and the statistics' scratch
+  MpcValidateParams vp{};     // the packed inputs once more, as k_mpc_validate_prep writes them
+  int32_t *vl_count = nullptr, *vl_lane = nullptr;  // [Tmax][Emax]
+  int32_t* vl_pos = nullptr;                        // [Tmax][Emax][3]
+  float *vl_var = nullptr, *vl_cvar = nullptr, *vl_mean = nullptr, *vl_max = nullptr;  // [Tmax][Emax][3]
+  float* vl_mmd = nullptr;                          // [Tmax][Emax][3][S]
+  float* vl_est = nullptr;                          // [Tmax][Emax][2]
+  hipStream_t side = nullptr;                       // the validators' stream of an overlapped stage
+  hipEvent_t ev_prep = nullptr, ev_done = nullptr;  // the prep is done; the side stream's tick is done
+  bool side_pending = false;                        // ev_done was recorded since the last synchronisation
 };
 
 namespace {
@@ -84,6 +107,75 @@ void enqueue_step(mpcmmd_mpc* c, int tick, bool reset) {
   q.chol = c->chol;
   launch_mpc_step(q, c->E, h->stream);
   HIPC(hipGetLastError());
+}
+
+// the validation stage of tick `tick`, behind its CEM iterations and before its step (the step
+// overwrites pos, vel and obs, the next solve the results): the packed inputs on the handle's
+// stream, then mpcmmd_validate's and mpcmmd_validate_risk's launches with K = E and the results
+// pointed at the tick's log row -- behind the prep, or on the side stream between two events
+void enqueue_validation(mpcmmd_mpc* c, int tick) {
+  mpcmmd_handle* h = c->h;
+  const int T = h->T, E = c->E;
+  const size_t row = size_t(tick) * c->Emax;
+  if (c->side_pending) {  // the previous tick's validators still own the packed inputs, the costs and the scratch
+    HIPC(hipStreamWaitEvent(h->stream, c->ev_done, 0));
+    c->side_pending = false;
+  }
+  MpcValidateParams p = c->vp;
+  p.tick = tick;
+  p.res = h->p.results + size_t(T - 1) * kResultStride, p.s_res = T * kResultStride;
+  p.pos = c->q.pos, p.vel = c->q.vel;
+  p.obs = h->p.obs;
+  p.key = c->keys_dev;
+  p.est = c->vl_est + row * 2;
+  launch_mpc_validate_prep(p, E, h->stream);
+  HIPC(hipGetLastError());
+  hipStream_t s = h->stream;
+  if (c->val_overlap) {
+    HIPC(hipEventRecord(c->ev_prep, h->stream));
+    HIPC(hipStreamWaitEvent(c->side, c->ev_prep, 0));
+    s = c->side;
+  }
+  ValidateRiskParams q = c->vq;
+  q.K = q.roll.K = E;
+  ValidateParams v = q.roll;
+  v.count = c->vl_count + row, v.count_lane = c->vl_lane + row;
+  launch_validate(v, s);
+  HIPC(hipGetLastError());
+  q.count_pos = c->vl_pos + row * 3;
+  q.var = c->vl_var + row * 3, q.cvar = c->vl_cvar + row * 3;
+  q.mean = c->vl_mean + row * 3, q.vmax = c->vl_max + row * 3;
+  q.mmd = c->val_S ? c->vl_mmd + row * 3 * c->val_S : nullptr;
+  launch_vrisk_roll(q, s);
+  HIPC(hipGetLastError());
+  launch_vrisk_stats(q, s);
+  HIPC(hipGetLastError());
+  launch_vrisk_mmd(q, s);
+  HIPC(hipGetLastError());
+  if (c->val_overlap) {
+    HIPC(hipEventRecord(c->ev_done, c->side));
+    c->side_pending = true;
+  }
+}
+
+// the handle's stream and the side stream idle
+void sync_streams(mpcmmd_mpc* c) {
+  HIPC(hipStreamSynchronize(c->h->stream));
+  if (c->side) HIPC(hipStreamSynchronize(c->side));
+  c->side_pending = false;
+}
+
+// frees the validation stage's buffers (the last allocations of the context), its stream and events
+void drop_validation(mpcmmd_mpc* c) {
+  if (!c->val_on) return;
+  for (size_t i = c->val_first; i < c->bufs.size(); ++i) (void)hipFree(c->bufs[i]);
+  c->bufs.resize(c->val_first);
+  if (c->ev_prep) (void)hipEventDestroy(c->ev_prep);
+  if (c->ev_done) (void)hipEventDestroy(c->ev_done);
+  if (c->side) (void)hipStreamDestroy(c->side);
+  c->ev_prep = c->ev_done = nullptr, c->side = nullptr;
+  c->side_pending = false;
+  c->val_on = false;
 }
 
 }  // namespace
@@ -211,6 +303,8 @@ void mpcmmd_mpc_destroy(mpcmmd_mpc* c) {
   if (!c) return;
   (void)hipSetDevice(c->h->device);
   if (c->h->stream) (void)hipStreamSynchronize(c->h->stream);  // the steps in flight
+  if (c->side) (void)hipStreamSynchronize(c->side);            // and the validators
+  drop_validation(c);
   for (void* d : c->bufs) (void)hipFree(d);
   delete c;
 }
@@ -227,7 +321,7 @@ int mpcmmd_mpc_reset(mpcmmd_mpc* c, int32_t n_episodes, const double* pos, const
   return guarded([&] {
     mpcmmd_handle* h = c->h;
     check_device(h);
-    HIPC(hipStreamSynchronize(h->stream));  // a reset starts over: nothing of the last run is in flight
+    sync_streams(c);  // a reset starts over: nothing of the last run is in flight
     const size_t E = size_t(n_episodes), O = size_t(c->q.w.O);
     c->E = n_episodes, c->drawn = u == nullptr;
     c->keys.assign(keys, keys + E);
@@ -264,6 +358,7 @@ int mpcmmd_mpc_run(mpcmmd_mpc* c, int32_t cost_kind, int32_t tick_begin, int32_t
       return rc;
     if (int rc = mpcmmd_iterate(c->h, 0, c->h->T)) return rc;
     if (int rc = guarded([&] {
+          if (c->val_on) enqueue_validation(c, k);
           enqueue_step(c, k, false);
           return MPCMMD_OK;
         }))
@@ -278,7 +373,7 @@ int mpcmmd_mpc_log(mpcmmd_mpc* c, int32_t ticks, double* log_d, float* log_f, in
   if (ticks < 0 || ticks > c->Tmax) return fail(MPCMMD_E_INVALID, "mpc: tick range");
   return guarded([&] {
     check_device(c->h);
-    HIPC(hipStreamSynchronize(c->h->stream));
+    sync_streams(c);
     const size_t E = size_t(c->E), Em = size_t(c->Emax);
     // rows of Emax -> [ticks][n_episodes]: one strided copy per array
     auto back = [&](void* dst, const void* src, size_t row_bytes) {
@@ -287,6 +382,132 @@ int mpcmmd_mpc_log(mpcmmd_mpc* c, int32_t ticks, double* log_d, float* log_f, in
     };
     back(log_d, c->logd, 2 * 8), back(log_f, c->logf, 12 * 4), back(log_i, c->logi, 4 * 4), back(plan, c->plan, 30 * 4);
     if (E > 0) HIPC(hipMemcpy(done_tick, c->q.done, E * 4, hipMemcpyDeviceToHost));
+    return MPCMMD_OK;
+  });
+}
+
+int mpcmmd_mpc_validate(mpcmmd_mpc* c, const mpcmmd_mpc_validation* cfg) {
+  if (!c) return fail(MPCMMD_E_INVALID, "null argument");
+  mpcmmd_handle* h = c->h;
+  const int O = h->O, H = h->H;
+  ValidateRiskParams q{};
+  if (cfg) {
+    const int R = cfg->num_rollouts, S = cfg->num_sigma;
+    if (R < 1 || R > (1 << 20)) return fail(MPCMMD_E_INVALID, "mpc validation: num_rollouts out of 1..2^20");
+    if (!(cfg->alpha >= 0.0f && cfg->alpha <= 1.0f))
+      return fail(MPCMMD_E_INVALID, "mpc validation: alpha out of [0, 1]");
+    if (S < 0 || S > kRiskMaxSigma) return fail(MPCMMD_E_INVALID, "mpc validation: num_sigma out of [0, 8]");
+    for (int i = 0; i < S; ++i)
+      if (!(std::isfinite(cfg->sigma[i]) && cfg->sigma[i] > 0.0f))
+        return fail(MPCMMD_E_INVALID, "mpc validation: every sigma must be finite and > 0");
+    if (cfg->overlap != 0 && cfg->overlap != 1) return fail(MPCMMD_E_INVALID, "mpc validation: overlap must be 0 or 1");
+    if (!validate_shape_ok(O, H))
+      return fail(MPCMMD_E_INVALID, "mpc validation: the validators take 1 <= num_obs <= 32 and 2 <= num_prime <= 100");
+    q.R = q.roll.R = R, q.S = S;
+    if (mpcmmd_quantile_position(R, cfg->alpha, &q.lo, &q.hi, &q.w_lo, &q.w_hi) != MPCMMD_OK)
+      return fail(MPCMMD_E_INVALID, "mpc validation: quantile position");
+  }
+  const int rc = guarded([&] {
+    check_device(h);
+    sync_streams(c);  // nothing in flight reads the buffers about to go
+    drop_validation(c);
+    c->reset_done = false;  // the stage changes with the episodes: the next run needs a reset
+    if (!cfg) return MPCMMD_OK;
+    c->val_first = c->bufs.size();
+    c->val_on = true;  // from here on drop_validation frees what exists
+    c->val_S = q.S, c->val_overlap = cfg->overlap == 1;
+    HIPC(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
+    HIPC(hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming));
+    HIPC(hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming));
+    const size_t Em = size_t(c->Emax), Tm = size_t(c->Tmax), R = size_t(q.R), S = size_t(q.S);
+    const size_t n3 = 3 * Em, tiles = (R + kRiskTile - 1) / kRiskTile;
+    const ProblemConsts& pc = h->pc;
+    const mpcmmd_config& hc = h->cfg;
+    ValidateParams& v = q.roll;  // as plan_params (validate_api.hip)
+    v.O = O, v.H = H, v.noise = hc.noise;
+    v.noise_level = hc.noise_level, v.acc_const = hc.acc_const_noise, v.steer_const = hc.steer_const_noise;
+    v.K_steer = pc.K_steer, v.y_lb = pc.y_lb, v.y_ub = pc.y_ub, v.seed = hc.seed;
+    const std::vector<float> basis = pack_basis(pc);  // P, Pdot, Pddot
+    v.Pdot = mpc_alloc<float>(c, size_t(kNum) * kNvar, basis.data() + kNum * kNvar);
+    v.Pddot = mpc_alloc<float>(c, size_t(kNum) * kNvar, basis.data() + 2 * kNum * kNvar);
+    MpcValidateParams& p = c->vp;
+    p = MpcValidateParams{};
+    p.H = H, p.O = O;
+    v.cx = p.cx = mpc_alloc<double>(c, Em * kNvar), v.cy = p.cy = mpc_alloc<double>(c, Em * kNvar);
+    v.init_state = p.init = mpc_alloc<double>(c, Em * 6);
+    v.x_obs = p.x_obs = mpc_alloc<float>(c, Em * O * kMpcTrack);
+    v.y_obs = p.y_obs = mpc_alloc<float>(c, Em * O * kMpcTrack);
+    v.keys = p.keys = mpc_alloc<uint32_t>(c, Em);
+    v.draws = nullptr;
+    q.costs = mpc_alloc<float>(c, n3 * R);  // every element is stored by its rollout's thread
+    q.np = mpc_alloc<int32_t>(c, n3);
+    if (S > 0) {
+      std::vector<float> sg(Em * S);
+      for (size_t i = 0; i < sg.size(); ++i) sg[i] = cfg->sigma[i % S];
+      q.sigma = mpc_alloc<float>(c, sg.size(), sg.data());
+      q.u = mpc_alloc<float>(c, n3 * R);
+      q.part = mpc_alloc<double>(c, n3 * tiles * S);
+    }
+    c->vq = q;
+    const size_t rows = Tm * Em;
+    c->vl_count = mpc_alloc<int32_t>(c, rows), c->vl_lane = mpc_alloc<int32_t>(c, rows);
+    c->vl_pos = mpc_alloc<int32_t>(c, rows * 3);
+    c->vl_var = mpc_alloc<float>(c, rows * 3), c->vl_cvar = mpc_alloc<float>(c, rows * 3);
+    c->vl_mean = mpc_alloc<float>(c, rows * 3), c->vl_max = mpc_alloc<float>(c, rows * 3);
+    c->vl_mmd = mpc_alloc<float>(c, rows * 3 * S), c->vl_est = mpc_alloc<float>(c, rows * 2);
+    return MPCMMD_OK;
+  });
+  if (rc != MPCMMD_OK) {  // a failed allocation leaves no half-made stage
+    drop_validation(c);
+    (void)hipGetLastError();
+  }
+  return rc;
+}
+
+int mpcmmd_mpc_validation_log(mpcmmd_mpc* c, int32_t ticks, int32_t* counts, int32_t* count_pos, float* stats,
+                              float* mmd, float* est) {
+  if (!c || !counts || !count_pos || !stats || !est) return fail(MPCMMD_E_INVALID, "null argument");
+  if (c->val_on && c->val_S > 0 && !mmd) return fail(MPCMMD_E_INVALID, "null argument");
+  if (ticks < 0 || ticks > c->Tmax) return fail(MPCMMD_E_INVALID, "mpc: tick range");
+  if (!c->val_on) return fail(MPCMMD_E_STATE, "mpcmmd_mpc_validation_log without a validation stage");
+  return guarded([&] {
+    check_device(c->h);
+    sync_streams(c);
+    if (ticks == 0 || c->E == 0) return MPCMMD_OK;
+    const size_t E = size_t(c->E), Em = size_t(c->Emax), n = size_t(ticks) * E, S = size_t(c->val_S);
+    // rows of Emax -> [ticks][n_episodes]: one strided copy per array
+    auto back = [&](void* dst, const void* src, size_t row_bytes) {
+      HIPC(hipMemcpy2D(dst, E * row_bytes, src, Em * row_bytes, E * row_bytes, size_t(ticks), hipMemcpyDeviceToHost));
+    };
+    std::vector<int32_t> c2(n * 2);
+    back(c2.data(), c->vl_count, 4), back(c2.data() + n, c->vl_lane, 4);
+    for (size_t i = 0; i < n; ++i)
+      for (size_t k = 0; k < 2; ++k) counts[i * 2 + k] = c2[k * n + i];
+    std::vector<float> s4(n * 12);
+    back(s4.data(), c->vl_var, 12), back(s4.data() + n * 3, c->vl_cvar, 12);
+    back(s4.data() + n * 6, c->vl_mean, 12), back(s4.data() + n * 9, c->vl_max, 12);
+    for (size_t i = 0; i < n; ++i)
+      for (size_t k = 0; k < 4; ++k) std::memcpy(stats + (i * 4 + k) * 3, &s4[(k * n + i) * 3], 12);
+    back(count_pos, c->vl_pos, 12), back(est, c->vl_est, 8);
+    if (S > 0) back(mmd, c->vl_mmd, 12 * S);
+    return MPCMMD_OK;
+  });
+}
+
+int mpcmmd_mpc_validation_inputs(mpcmmd_mpc* c, double* cx, double* cy, double* init_state, float* x_obs,
+                                 float* y_obs, uint32_t* keys) {
+  if (!c) return fail(MPCMMD_E_INVALID, "null argument");
+  if (!c->val_on) return fail(MPCMMD_E_STATE, "mpcmmd_mpc_validation_inputs without a validation stage");
+  return guarded([&] {
+    check_device(c->h);
+    sync_streams(c);
+    const size_t E = size_t(c->E), O = size_t(c->vp.O);
+    auto back = [&](void* dst, const void* src, size_t bytes) {
+      if (dst && bytes) HIPC(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    };
+    back(cx, c->vp.cx, E * kNvar * 8), back(cy, c->vp.cy, E * kNvar * 8), back(init_state, c->vp.init, E * 6 * 8);
+    back(x_obs, c->vp.x_obs, E * O * kMpcTrack * 4), back(y_obs, c->vp.y_obs, E * O * kMpcTrack * 4);
+    back(keys, c->vp.keys, E * 4);
     return MPCMMD_OK;
   });
 }

@@ -37,6 +37,7 @@ SYMBOLS = (
     "mpcmmd_world_validation_log", "mpcmmd_world_validation_inputs",
     "mpcmmd_mpc_step_host", "mpcmmd_mpc_step_device", "mpcmmd_mpc_create", "mpcmmd_mpc_destroy",
     "mpcmmd_mpc_reset", "mpcmmd_mpc_run", "mpcmmd_mpc_log", "mpcmmd_mpc_first_normals",
+    "mpcmmd_mpc_validate", "mpcmmd_mpc_validation_log", "mpcmmd_mpc_validation_inputs",
 )
 
 
@@ -148,6 +149,11 @@ class WorldStepIO(C.Structure):
 class WorldValidation(C.Structure):
     _fields_ = [("num_rollouts", C.c_int32), ("alpha", C.c_float), ("num_sigma", C.c_int32),
                 ("sigma", C.c_float * 8)]
+
+
+class MpcValidation(C.Structure):
+    _fields_ = [("num_rollouts", C.c_int32), ("alpha", C.c_float), ("num_sigma", C.c_int32),
+                ("sigma", C.c_float * 8), ("overlap", C.c_int32)]
 
 
 class MpcModelStruct(C.Structure):
@@ -280,6 +286,11 @@ def lib():
         L.mpcmmd_mpc_run.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp, fp]
         L.mpcmmd_mpc_log.argtypes = [vp, C.c_int32, dp, fp, ip, fp, ip]
         L.mpcmmd_mpc_first_normals.argtypes = [C.POINTER(Config), fp]
+    if hasattr(L, "mpcmmd_mpc_validate"):   # an older library lacks the stage: Mpc.validate raises
+        dp = C.POINTER(C.c_double)
+        L.mpcmmd_mpc_validate.argtypes = [vp, C.POINTER(MpcValidation)]
+        L.mpcmmd_mpc_validation_log.argtypes = [vp, C.c_int32, ip, ip, fp, fp, fp]
+        L.mpcmmd_mpc_validation_inputs.argtypes = [vp, dp, dp, dp, fp, fp, C.POINTER(C.c_uint32)]
     L.mpcmmd_path_smoothing.argtypes = [C.c_int32, fp, fp, C.c_float, fp, fp]
     L.mpcmmd_path_parameters.argtypes = [C.c_int32, fp, fp, fp, fp, fp, fp, fp, fp, fp]
     L.mpcmmd_global_to_frenet.argtypes = [C.POINTER(Path), C.c_int32, fp, fp, fp, fp, fp, fp, fp]
@@ -956,6 +967,56 @@ class Mpc:
                                      li.ctypes.data_as(ip), _fptr(pl), dn.ctypes.data_as(ip)))
         return dict(log_d=ld, log_f=lf, log_i=li, cx=pl[..., :11].copy(), cy=pl[..., 11:22].copy(),
                     mean=pl[..., 22:].copy(), done_tick=dn)
+
+    def validate(self, rollouts, alpha=0.98, sigma=(), overlap=True):
+        """mpcmmd_mpc_validate: from the next ``reset`` on, every tick of ``run`` also computes the
+        Monte-Carlo risk of the plan it made (``validate`` and ``validate_risk`` of that tick with
+        ``rollouts`` fresh noise rows, quantile level ``alpha`` and the MMD bandwidths ``sigma``, at
+        most 8) into the validation log; ``overlap`` puts the validators' launches on the context's
+        side stream, off the loop's critical path (False: in-line on the handle's stream; same bits).
+        ``rollouts`` None turns the stage off."""
+        if not hasattr(self._L, "mpcmmd_mpc_validate"):
+            raise NativeError(f"{LIB_PATH} has no mpcmmd_mpc_validate (built before the entry point existed): "
+                              "rebuild it")
+        self._val_S = 0
+        if rollouts is None:
+            check(self._L.mpcmmd_mpc_validate(self._c, None))
+            return
+        sg = np.asarray(() if sigma is None else sigma, np.float32).reshape(-1)
+        cfg = MpcValidation(int(rollouts), float(alpha), int(sg.size))
+        for i, v in enumerate(sg[:8]):   # more than 8: num_sigma says so and the library refuses
+            cfg.sigma[i] = float(v)
+        cfg.overlap = int(overlap)
+        check(self._L.mpcmmd_mpc_validate(self._c, C.byref(cfg)))
+        self._val_S = int(sg.size)
+
+    def validation_log(self, ticks):
+        """The first ``ticks`` rows of the validation log: val_counts [T, E, 2] (count, count_lane of
+        ``validate``), val_count_pos [T, E, 3], val_stats [T, E, 4, 3] (var, cvar, mean, max by
+        channels RISK_CHANNELS), val_mmd [T, E, 3, S] and val_est [T, E, 2] (the cost_lane and
+        cost_obs the solve itself estimated)."""
+        T, E, S = int(ticks), self.E, getattr(self, "_val_S", 0)
+        n = max(T, 0)
+        cn, cp = np.zeros((n, E, 2), np.int32), np.zeros((n, E, 3), np.int32)
+        st, mm = np.zeros((n, E, 4, 3), np.float32), np.zeros((n, E, 3, S), np.float32)
+        es = np.zeros((n, E, 2), np.float32)
+        ip = C.POINTER(C.c_int32)
+        check(self._L.mpcmmd_mpc_validation_log(self._c, T, cn.ctypes.data_as(ip), cp.ctypes.data_as(ip), _fptr(st),
+                                                _fptr(mm) if S else None, _fptr(es)))
+        return dict(val_counts=cn, val_count_pos=cp, val_stats=st, val_mmd=mm, val_est=es)
+
+    def validation_inputs(self):
+        """The packed inputs of the last validated tick, as the validators read them: cx, cy [E, 11],
+        init_state [E, 6] (float64), x_obs, y_obs [E, O, 100], keys [E] (uint32)."""
+        E, O = self.E, self.model.num_obs
+        out = dict(cx=np.zeros((E, 11)), cy=np.zeros((E, 11)), init_state=np.zeros((E, 6)),
+                   x_obs=np.zeros((E, O, 100), np.float32), y_obs=np.zeros((E, O, 100), np.float32),
+                   keys=np.zeros(E, np.uint32))
+        dp = C.POINTER(C.c_double)
+        check(self._L.mpcmmd_mpc_validation_inputs(
+            self._c, *[out[k].ctypes.data_as(dp) for k in ("cx", "cy", "init_state")], _fptr(out["x_obs"]),
+            _fptr(out["y_obs"]), out["keys"].ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
 
 
 class Tick:

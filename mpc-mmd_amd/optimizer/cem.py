@@ -122,7 +122,7 @@ class CEM:
 
     # ------------------------------------------------------------------
     def run_episodes(self, cost, vehicles, starts, ticks, *, chained=True, device_step=None, u=None, key_base=0,
-                     keys=None, goal_x=200.0, mean=None, cov=None, v_des=15.0, dt=0.15):
+                     keys=None, goal_x=200.0, mean=None, cov=None, v_des=15.0, dt=0.15, validate=None):
         """E closed-loop episodes of ``ticks`` ticks in lockstep: solve, apply
         the plan's first control under the noise model, re-solve from the new state, warm-started
         from the previous mean.  vehicles [E, num_obs, 4] = x, y, vx, vy; starts [E, 4] = x, y, vx, vy
@@ -137,8 +137,25 @@ class CEM:
         host (device_step None) or by the kernel on GPU ``device_step``.  All routes return the same
         bits: a dict of log_d [ticks, E, 2], log_f [ticks, E, 12], log_i [ticks, E, 4]
         (``_native.MPC_LOG_*`` name the columns), every tick's cx, cy [ticks, E, 11] and mean
-        [ticks, E, 8], and done_tick [E]."""
+        [ticks, E, 8], and done_tick [E].
+
+        validate = dict(rollouts=R, alpha=0.98, sigma=(), overlap=True) also computes, per tick and
+        episode, the Monte-Carlo risk of the plan that tick made: R fresh noisy
+        rollouts of the plan from the tick's state against the tick's tracks.  The chained routes run
+        it inside the loop on the GPU (``Mpc.validate``; ``overlap`` puts it on a side stream); the
+        host-linked routes call ``_native.validate`` and ``_native.validate_risk`` after each tick's
+        solve for the E episodes as one batch: the stage's reference and its fallback, same bits.  The
+        dict gains val_counts [ticks, E, 2] (count, count_lane), val_count_pos [ticks, E, 3], val_stats
+        [ticks, E, 4, 3] (var, cvar, mean, max by obs, lane_lb, lane_ub), val_mmd [ticks, E, 3, S] and
+        val_est [ticks, E, 2] (the cost_lane, cost_obs the solve itself estimated)."""
         h, cfg = self._h, self._cfg
+        val = None
+        if validate is not None:
+            val = dict(alpha=0.98, sigma=(), overlap=True)
+            val.update(validate)
+            if set(val) != {"rollouts", "alpha", "sigma", "overlap"}:
+                raise TypeError("run_episodes: validate takes rollouts, alpha, sigma, overlap")
+            val["sigma"] = np.asarray(() if val["sigma"] is None else val["sigma"], np.float32).reshape(-1)
         ticks = int(ticks)
         starts = np.asarray(starts, np.float64)
         starts = starts.reshape(-1, starts.shape[-1])
@@ -166,17 +183,32 @@ class CEM:
                 raise ValueError("run_episodes: the chained counts must add up to ticks")
             ctx = _native.Mpc(h, model, max(ticks, 1))
             try:
+                if val is not None:   # before the reset: the stage takes effect there
+                    ctx.validate(val["rollouts"], val["alpha"], val["sigma"], val["overlap"])
                 ctx.reset(pos, vel, veh, mean, cov, u, keys)
                 k = 0
                 for c in counts:
                     ctx.run(cost, k, c, cov, v_des)
                     k += c
-                return ctx.log(ticks)
+                out = ctx.log(ticks)
+                if val is not None:
+                    out.update(ctx.validation_log(ticks))
+                return out
             finally:
                 ctx.close()
         out = dict(log_d=np.empty((ticks, E, 2)), log_f=np.empty((ticks, E, 12), f32),
                    log_i=np.empty((ticks, E, 4), np.int32), cx=np.empty((ticks, E, 11), f32),
                    cy=np.empty((ticks, E, 11), f32), mean=np.empty((ticks, E, 8), f32))
+        if val is not None:
+            S = val["sigma"].size
+            out.update(val_counts=np.empty((ticks, E, 2), np.int32), val_count_pos=np.empty((ticks, E, 3), np.int32),
+                       val_stats=np.empty((ticks, E, 4, 3), f32), val_mmd=np.empty((ticks, E, 3, S), f32),
+                       val_est=np.empty((ticks, E, 2), f32))
+            # the handle's configuration as the stage reads it: the fp32 fields widened
+            plan = dict(num_prime=self.num_prime, noise=self.noise, noise_level=float(cfg.noise_level),
+                        acc_const_noise=float(cfg.acc_const_noise), steer_const_noise=float(cfg.steer_const_noise),
+                        num_rollouts=int(val["rollouts"]), variant=self.variant, seed=int(cfg.seed),
+                        device=int(cfg.device))
         done = np.full(E, -1, np.int32)
         zero = np.zeros((E, 11), f32)
         # tick 0's inputs: the step of a frozen episode writes the inputs of the state it is given
@@ -187,6 +219,15 @@ class CEM:
                                 st["init_state"], mean, cov, st["x_obs"], st["y_obs"], v_des)
             mean = h.read("mean", shape=(E, 8)).copy()
             cx, cy = np.stack([r["cx"] for r in res]), np.stack([r["cy"] for r in res])
+            if val is not None:   # the plan against the state and the tracks it was solved for
+                ins = (cx, cy, st["init_state"], st["x_obs"], st["y_obs"], [(k + int(q)) & 0xFFFFFFFF for q in keys])
+                cnt, lane = _native.validate(*ins, **plan)
+                rk = _native.validate_risk(*ins, alpha=float(val["alpha"]), sigma=val["sigma"] if S else None, **plan)
+                out["val_counts"][k] = np.stack([cnt, lane], 1)
+                out["val_count_pos"][k] = rk["count_pos"]
+                out["val_stats"][k] = np.stack([rk[n] for n in ("var", "cvar", "mean", "max")], 1)
+                out["val_mmd"][k] = rk["mmd"]
+                out["val_est"][k] = [(r["cost_lane"], r["cost_obs"]) for r in res]
             st = _native.mpc_step(model, k, cx, cy, None if u is None else u[k], mean, pos, vel, veh, done,
                                   device=device_step, keys=keys)
             pos, vel, veh, done = st["pos"], st["vel"], st["vehicles"], st["done_tick"]

@@ -31,6 +31,20 @@ collided, goal, frozen), every tick's ``cx``, ``cy`` [T, E, 11] and ``mean``
 the mean minimum -clear, the lane-departure share and the mean progress in x,
 each as mean +- sample standard deviation over the episodes.
 
+With ``--validate R [--alpha A] [--risk-sigma s ...] [--no-overlap]`` every
+tick's plan is also rolled out under R fresh noise rows from the tick's state
+against the tick's tracks: inside the chained loop on the
+GPU, on a side stream unless ``--no-overlap`` puts it in-line, or, with
+``--host-step``, by mpcmmd_validate and mpcmmd_validate_risk after each tick's
+solve -- the same bits again.  The npz then also holds ``val_counts`` [T, E, 2]
+(count, count_lane), ``val_count_pos`` [T, E, 3], ``val_stats`` [T, E, 4, 3]
+(var, cvar, mean, max by obs, lane_lb, lane_ub), ``val_mmd`` [T, E, 3, S] and
+``val_est`` [T, E, 2] (the cost_lane, cost_obs the solve estimated), and a second
+line per cost gives, over the live (tick, episode) pairs, the mean Monte-Carlo
+collision probability count_pos[obs] / R, the mean count / R (the reference's
+coll_* metric) and the mean validated CVaR of the obstacle cost beside the mean
+of the solver's own cost_obs.
+
 The episode runner is a parameter of ``closed_loop`` (``run=``), so the
 accounting is testable without a GPU.
 """
@@ -43,6 +57,7 @@ import numpy as np
 
 COSTS = ("mmd_opt", "mmd_random", "cvar", "saa")
 KEYS = ("log_d", "log_f", "log_i", "cx", "cy", "mean", "done_tick")
+VAL_KEYS = ("val_counts", "val_count_pos", "val_stats", "val_mmd", "val_est")
 CLEAR, LANE_OUT, COLLIDED = 10, 0, 1   # columns of log_f / log_i (_native.MPC_LOG_F / _I)
 
 
@@ -89,11 +104,31 @@ def summarise(res):
                 progress=_mean_std(log_d[last, np.arange(E), 0] - log_d[0, :, 0] if T else np.zeros(E)))
 
 
+def summarise_validation(res, rollouts):
+    """The four figures of one cost's validated plans, each (mean, sample sd)
+    over the episodes of the episode's mean over its live ticks (``summarise``'s
+    convention: rows after ``done_tick`` are left out): the Monte-Carlo collision
+    probability count_pos[obs] / R, the reference's count / R, the validated
+    CVaR of the obstacle cost, and the obstacle cost the solver estimated."""
+    T, E = res["val_counts"].shape[:2]
+    done = np.asarray(res["done_tick"])
+    last = np.where(done >= 0, done, T - 1)
+    live = np.arange(T)[:, None] <= last[None, :]
+    n = np.maximum(live.sum(axis=0), 1)
+    per_episode = lambda a: np.where(live, np.asarray(a, np.float64), 0.0).sum(axis=0) / n
+    return dict(p_collision=_mean_std(per_episode(res["val_count_pos"][:, :, 0] / float(rollouts))),
+                count_share=_mean_std(per_episode(res["val_counts"][:, :, 0] / float(rollouts))),
+                cvar_obs=_mean_std(per_episode(res["val_stats"][:, :, 1, 0])),
+                est_obs=_mean_std(per_episode(res["val_est"][:, :, 1])))
+
+
 def closed_loop(prob, costs, vehicles, starts, ticks, out_dir=None, run=None, log=print, **kw):
     """Runs ``run(prob, cost, vehicles, starts, ticks, **kw)`` (default:
     ``prob.run_episodes``) per cost, writes the files and prints the lines of
     the module docstring.  Returns {cost: (the result, its summary)}."""
     run = run or _run
+    val = kw.get("validate")
+    keys = KEYS + (VAL_KEYS if val is not None else ())
     results = {}
     for cost in costs:
         if cost not in COSTS:
@@ -101,18 +136,26 @@ def closed_loop(prob, costs, vehicles, starts, ticks, out_dir=None, run=None, lo
         res = run(prob, cost, vehicles, starts, ticks, **kw)
         if out_dir is not None:
             os.makedirs(out_dir, exist_ok=True)
-            np.savez(os.path.join(out_dir, f"closed_loop_{cost}.npz"), **{k: res[k] for k in KEYS})
+            np.savez(os.path.join(out_dir, f"closed_loop_{cost}.npz"), **{k: res[k] for k in keys})
         s = summarise(res)
         E = np.asarray(res["done_tick"]).size
         log(f"{cost}: {E} episodes x {int(ticks)} ticks, collision share = {s['collision'][0]:.4f} +- "
             f"{s['collision'][1]:.4f}, mean min -clear = {s['min_neg_clear'][0]:.4f} +- {s['min_neg_clear'][1]:.4f}, "
             f"lane departure share = {s['lane_departure'][0]:.4f} +- {s['lane_departure'][1]:.4f}, "
             f"mean progress = {s['progress'][0]:.2f} +- {s['progress'][1]:.2f} m")
+        if val is not None:
+            sv = summarise_validation(res, val["rollouts"])
+            s.update(sv)
+            log(f"{cost}: plans under {int(val['rollouts'])} fresh noise rows, mean collision probability = "
+                f"{sv['p_collision'][0]:.4f} +- {sv['p_collision'][1]:.4f}, mean count / R = "
+                f"{sv['count_share'][0]:.4f} +- {sv['count_share'][1]:.4f}, mean validated CVaR(obs) = "
+                f"{sv['cvar_obs'][0]:.4f} +- {sv['cvar_obs'][1]:.4f}, mean solver cost_obs = "
+                f"{sv['est_obs'][0]:.4f} +- {sv['est_obs'][1]:.4f}")
         results[cost] = (res, s)
     return results
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="closed-loop MPC episodes of the synthetic variants")
     ap.add_argument("--variant", default="static", choices=["static", "dynamic"])
     ap.add_argument("--episodes", type=int, default=8)
@@ -120,6 +163,12 @@ def main(argv=None):
     ap.add_argument("--costs", nargs="+", default=list(COSTS), choices=sorted(COSTS))
     ap.add_argument("--host-step", action="store_true",
                     help="solve tick by tick and step the world on the host (mpcmmd_mpc_step_host)")
+    ap.add_argument("--validate", type=int, default=None, metavar="R",
+                    help="also roll every tick's plan out under R fresh noise rows (the val_* arrays, a second line)")
+    ap.add_argument("--alpha", type=float, default=0.98, help="quantile level of the validated VaR / CVaR")
+    ap.add_argument("--risk-sigma", type=float, nargs="*", default=[], metavar="s", help="MMD bandwidths (at most 8)")
+    ap.add_argument("--no-overlap", action="store_true",
+                    help="the validation stage in-line on the loop's stream (default: on a side stream; same bits)")
     ap.add_argument("--out", default="stats_closed_loop")
     ap.add_argument("--num-reduced", type=int, default=10)
     ap.add_argument("--num-obs", type=int, default=3)
@@ -133,7 +182,18 @@ def main(argv=None):
     ap.add_argument("--v-des", type=float, default=15.0)
     ap.add_argument("--goal-x", type=float, default=200.0)
     ap.add_argument("--seed", type=int, default=0)
-    a = ap.parse_args(argv)
+    return ap.parse_args(argv)
+
+
+def validation_of(a):
+    """The ``validate=`` keyword of the parsed options ({} without --validate)."""
+    if a.validate is None:
+        return {}
+    return dict(validate=dict(rollouts=a.validate, alpha=a.alpha, sigma=a.risk_sigma, overlap=not a.no_overlap))
+
+
+def main(argv=None):
+    a = parse_args(argv)
     from .cem import CEM
     prob = CEM(a.num_reduced, a.num_obs, a.noise_level, a.num_prime, a.noise, a.acc_const_noise, a.steer_const_noise,
                num_batch=a.num_batch, variant=a.variant, maxiter_cem=a.maxiter_cem, seed=a.seed,
@@ -141,7 +201,7 @@ def main(argv=None):
     vehicles, keys = scenario(a.variant, a.episodes, a.num_obs)
     try:
         closed_loop(prob, a.costs, vehicles, starts_of(a.variant, a.episodes), a.ticks, a.out, keys=keys,
-                    v_des=a.v_des, goal_x=a.goal_x, chained=not a.host_step, device_step=None)
+                    v_des=a.v_des, goal_x=a.goal_x, chained=not a.host_step, device_step=None, **validation_of(a))
     finally:
         prob.handle.close()
 
