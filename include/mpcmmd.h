@@ -1119,6 +1119,80 @@ int mpcmmd_mpc_validation_log(mpcmmd_mpc* c, int32_t ticks, int32_t* counts, int
 int mpcmmd_mpc_validation_inputs(mpcmmd_mpc* c, double* cx, double* cy, double* init_state, float* x_obs,
                                  float* y_obs, uint32_t* keys);
 
+/* ---- Planned vehicles of the synthetic closed loop ------
+ * With this policy a vehicle is no longer moved at constant velocity: it follows
+ * the dynamic driver's lane-tracking QP (obs_data.compute_obs_guess, what
+ * mpcmmd_obs_dynamic_traj solves once) and re-plans it every tick from its own
+ * state.  A planned vehicle has the fp32 state S = (x, y, vx, vy, ax, ay) -- the
+ * row (x, y, vx, vy) of `vehicles` and the row (ax, ay) of veh_acc -- and a
+ * target (v_des, y_des), constant over the episode.  Three pure functions, each
+ * element a sequential fp64 sum started at 0.0, rounded once to fp32 and stored
+ * through the quiet-NaN rule (0x7FC00000), no contraction, no transcendental:
+ *   plan(S, target)   rx[j] = (-2 v_des) colsum_x[j] (j < 11), rx[11..13] = x,
+ *                     vx, ax; ry[j] = (-2 y_des) colsum_y[j], ry[11..14] = y, vy,
+ *                     ay, 0; cxf[j] = float(sum_i kinv_x[j][i] rx[i]), cyf[j] =
+ *                     float(sum_i kinv_y[j][i] ry[i]).  With ax = ay = 0 this is
+ *                     mpcmmd_obs_dynamic_traj's solve bit for bit.
+ *   track(c, k)       float(sum_j P[k][j] double(c[j])), k < 100
+ *   advance(cxf, cyf) S' = (adv[0].cxf, adv[0].cyf, adv[1].cxf, adv[1].cyf,
+ *                     adv[2].cxf, adv[2].cyf)
+ * Where the step moves a vehicle by v dt, a live episode with the policy on does
+ * S <- advance(plan(S, target)); a frozen or reset episode keeps S.  The clear
+ * terms use the new positions, and the tracks the step writes are
+ * track(plan(S, target), k) of the new S, in the same buffers and layouts.
+ * Nothing else of the step changes.  A NaN in a state or a target reaches that
+ * vehicle's tracks and state as the quiet NaN, and collided = !(clear <= 0)
+ * applies; nothing is rejected for being NaN.
+ *
+ * mpcmmd_mpc_vehicle_constant returns the model's constants for the tick length
+ * dt, 0 < dt < 15 (host only): "kinv_x" [14][14], "kinv_y" [15][15], "colsum_x",
+ * "colsum_y" [11], "P" [100][11] (fp32-rounded), "adv" [3][11] = the rows P,
+ * Pdot, Pddot of the same basis at the single time double(dt) on [0, 15], each
+ * element rounded to fp32 and widened.  Return value as mpcmmd_host_constant's:
+ * the element count, or MPCMMD_E_INVALID (dt out of range, an unknown name, dst
+ * too small).
+ *
+ * mpcmmd_mpc_step_host_planned / _device_planned are mpcmmd_mpc_step_host /
+ * _device with the policy on (the model's dt must be < 15); the device step gives
+ * every array of pl a leading episode axis and runs the planned instantiation of
+ * k_mpc_step, whose every word equals the host step's
+ * (tests/test_gpu_mpc_vehicles.py).  A NULL pl, or a NULL veh_acc or veh_target
+ * with num_obs > 0, is MPCMMD_E_INVALID before any HIP call.  ABI version
+ * unchanged: detect the entry points by their symbols. */
+int mpcmmd_mpc_vehicle_constant(float dt, const char* name, double* dst, size_t count);
+
+typedef struct mpcmmd_mpc_planned { /* leading axis n_episodes for the device step */
+  float* veh_acc;          /* [num_obs][2] ax, ay: updated in place unless the episode is frozen */
+  const float* veh_target; /* [num_obs][2] v_des, y_des */
+  float* veh_log;          /* [num_obs][6] S after the step, or NULL */
+} mpcmmd_mpc_planned;
+
+int mpcmmd_mpc_step_host_planned(const mpcmmd_mpc_model* m, int32_t tick, const mpcmmd_mpc_step_io* io,
+                                 const mpcmmd_mpc_planned* pl);
+int mpcmmd_mpc_step_device_planned(const mpcmmd_mpc_model* m, int32_t device, int32_t n_episodes, int32_t tick,
+                                   const mpcmmd_mpc_step_io* io, const mpcmmd_mpc_planned* pl);
+
+/* The policy on the chained route.  mpcmmd_mpc_plan_vehicles allocates into the
+ * context what the policy needs -- the constants, the accelerations and targets
+ * [max_configs][num_obs][2], the vehicle log [max_ticks][max_configs][num_obs][6]
+ * -- and stages veh_target [n_episodes][num_obs][2] and veh_acc (NULL: zeros).
+ * veh_target NULL turns the policy off and frees all of it.  Like
+ * mpcmmd_mpc_validate it synchronises the context's streams and takes effect at
+ * the next mpcmmd_mpc_reset: a run before that reset is MPCMMD_E_STATE, and a
+ * reset with another n_episodes than the staged one is MPCMMD_E_INVALID.  Every
+ * reset starts the accelerations from the staged ones again.  With the policy on
+ * the reset's reset-mode step and every tick's step are the planned kernel; no
+ * readback, no synchronisation and no allocation is added to the loop, and the
+ * validation stage (which packs whatever tracks the step wrote) needs no change.
+ * MPCMMD_E_INVALID for a NULL c, n_episodes outside 1..max_configs or a model
+ * whose dt is not < 15.
+ *
+ * mpcmmd_mpc_vehicle_log synchronises like mpcmmd_mpc_log and reads back the
+ * first `ticks` rows veh [ticks][E][num_obs][6]: every vehicle's S after that
+ * tick's step.  MPCMMD_E_STATE with the policy off. */
+int mpcmmd_mpc_plan_vehicles(mpcmmd_mpc* c, int32_t n_episodes, const float* veh_target, const float* veh_acc);
+int mpcmmd_mpc_vehicle_log(mpcmmd_mpc* c, int32_t ticks, float* veh);
+
 #ifdef __cplusplus
 }
 #endif

@@ -312,6 +312,16 @@ DynObsConsts build_dyn_obs_consts() {
   return c;
 }
 
+std::vector<double> build_vehicle_advance(float dt) {
+  if (!(dt > 0.0f && dt < 15.0f)) throw std::runtime_error("vehicle advance: 0 < dt < 15");
+  std::vector<double> P, Pd, Pdd;
+  bernstein10({double(dt)}, 0.0, 15.0, P, Pd, Pdd);
+  std::vector<double> adv;
+  for (const auto* v : {&P, &Pd, &Pdd})
+    for (double x : *v) adv.push_back(round32(x));
+  return adv;
+}
+
 void dyn_obs_traj(const DynObsConsts& c, int num_obs, const float* x0, const float* y0, const float* vx0,
                   const float* vy0, const float* v_des, float y_des, float* x_traj, float* y_traj) {
   // rhs = [-lincost; b_eq] with -lincost = A^T b = -k_p * target * colsum(A)

@@ -58,6 +58,11 @@ struct DynObsConsts {
 };
 DynObsConsts build_dyn_obs_consts();
 
+// The rows P, Pdot, Pddot [3][11] of the same basis at the single time double(dt)
+// on [0, 15], each element rounded to fp32 and widened as P is: what advances a
+// planned vehicle by one tick (mpc_vehicle.hpp).  0 < dt < 15.
+std::vector<double> build_vehicle_advance(float dt);
+
 // x_traj/y_traj [num_obs][100] fp32 for obstacles starting at (x0, y0) with
 // speeds (vx0, vy0), zero acceleration, tracking speed v_des[i] and lane
 // y_des (dynamic main_mpc.py:116-126 uses y_des = -1.75).

@@ -13,6 +13,9 @@
 //      threads 128..157: the plan's log; all threads: the first population
 // Static LDS only (about 1.1 KB).  Latency-bound by construction (a handful of
 // dependent fp64 chains); launched once per tick.
+// k_mpc_step_planned is the same step with the vehicles following their
+// re-planned QP: the body below is written once and
+// instantiated twice.
 #include "mpc.hpp"
 #include "mpc_draw.hpp"
 
@@ -26,7 +29,17 @@ struct DevMath {
   static DEVI void sincos64(double a, double& s, double& c) { ::sincos(a, &s, &c); }
 };
 
-__global__ __launch_bounds__(kMpcThreads) void k_mpc_step(const MpcStepParams q) {
+// kPlanned: the vehicles follow their re-planned QP (mpc_vehicle.hpp) --
+//   a  before phase 1's barrier, from the last thread down (thread 0 has the controller): the
+//      O x 22 coefficients of plan(S_k) into s_coef, and the basis rows into s_P
+//   b  phase 2, a lane per vehicle: S_k+1 = advance, written back and logged; the clear term
+//   c  all threads: the coefficients of plan(S_k+1)
+//   d  phase 3's tracks: two 11-term sums per (vehicle, point); consecutive threads share a
+//      vehicle (its coefficients broadcast) and read rows of s_P 88 B apart (no bank shared)
+// The instantiation without the policy references none of the policy's LDS and is the kernel
+// it was: about 1.1 KB of static LDS; with the policy about 17 KB.
+template <bool kPlanned>
+DEVI void mpc_step_body(const MpcStepParams& q, const MpcVehParams* pv) {
   const MpcScalars& w = q.w;
   const int ep = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   __shared__ MpcEgo s_ego;
@@ -35,10 +48,27 @@ __global__ __launch_bounds__(kMpcThreads) void k_mpc_step(const MpcStepParams q)
   __shared__ float s_init[6];
   __shared__ float s_veh[kMpcMaxObs][4];
   __shared__ float s_clear;
+  __shared__ double s_P[kMpcTrack * 11];
+  __shared__ float s_coef[kMpcMaxObs][kVehCoef];
+  __shared__ float s_S[kMpcMaxObs][6];
+  __shared__ float s_tgt[kMpcMaxObs][2];
 
   const bool frozen = q.reset || q.done[ep] >= 0;
   const float* cx = q.cx + size_t(ep) * q.s_plan;
   const float* cy = q.cy + size_t(ep) * q.s_plan;
+
+  if constexpr (kPlanned) {  // a
+    const int rows = q.x_obs ? kMpcTrack : q.H;
+    for (int i = tid; i < rows * 11; i += kMpcThreads) s_P[i] = pv->k.P[i];
+    if (!frozen)
+      for (int i = kMpcThreads - 1 - tid; i < w.O * kVehCoef; i += kMpcThreads) {
+        const int o = i / kVehCoef, j = i - o * kVehCoef;
+        const float* veh = q.veh + (size_t(ep) * w.O + o) * 4;
+        const float* acc = pv->acc + (size_t(ep) * w.O + o) * 2;
+        const float S[6] = {veh[0], veh[1], veh[2], veh[3], acc[0], acc[1]};
+        s_coef[o][j] = mpc_veh_coef(pv->k, S, pv->target + (size_t(ep) * w.O + o) * 2, j);
+      }
+  }
 
   // 1
   if (tid == 0) {
@@ -72,12 +102,27 @@ __global__ __launch_bounds__(kMpcThreads) void k_mpc_step(const MpcStepParams q)
       float* veh = q.veh + (size_t(ep) * w.O + lane) * 4;
       float v[4];
       for (int k = 0; k < 4; ++k) v[k] = veh[k];
-      if (!frozen) {
-        v[0] = v[0] + v[2] * w.dt;
-        v[1] = v[1] + v[3] * w.dt;
-        veh[0] = v[0], veh[1] = v[1];
+      if constexpr (kPlanned) {  // b
+        const size_t vo = size_t(ep) * w.O + lane;
+        float* acc = pv->acc + vo * 2;
+        float S[6] = {v[0], v[1], v[2], v[3], acc[0], acc[1]};
+        if (!frozen) {
+          for (int k = 0; k < 6; ++k) S[k] = mpc_veh_advance(pv->k.adv, s_coef[lane], k);
+          for (int k = 0; k < 4; ++k) veh[k] = v[k] = S[k];
+          acc[0] = S[4], acc[1] = S[5];
+        }
+        for (int k = 0; k < 6; ++k) s_S[lane][k] = S[k];
+        for (int k = 0; k < 2; ++k) s_tgt[lane][k] = pv->target[vo * 2 + k];
+        if (pv->log)
+          for (int k = 0; k < 6; ++k) pv->log[vo * 6 + k] = S[k];
+      } else {
+        if (!frozen) {
+          v[0] = v[0] + v[2] * w.dt;
+          v[1] = v[1] + v[3] * w.dt;
+          veh[0] = v[0], veh[1] = v[1];
+        }
+        for (int k = 0; k < 4; ++k) s_veh[lane][k] = v[k];
       }
-      for (int k = 0; k < 4; ++k) s_veh[lane][k] = v[k];
       t = mpc_clear_term(w, e, v);
     }
     const bool any_nan = __ballot(t != t) != 0;
@@ -86,13 +131,26 @@ __global__ __launch_bounds__(kMpcThreads) void k_mpc_step(const MpcStepParams q)
   }
   __syncthreads();
 
+  if constexpr (kPlanned) {  // c
+    for (int i = tid; i < w.O * kVehCoef; i += kMpcThreads) {
+      const int o = i / kVehCoef, j = i - o * kVehCoef;
+      s_coef[o][j] = mpc_veh_coef(pv->k, s_S[o], s_tgt[o], j);
+    }
+    __syncthreads();
+  }
+
   // 3
   if (q.obs) {  // obstacle_transpose's layout: [2][O][H]
     float* ob = q.obs + size_t(ep) * 2 * w.O * q.H;
     for (int i = tid; i < w.O * q.H; i += kMpcThreads) {
       const int o = i / q.H, k = i - o * q.H;
-      ob[i] = mpc_track(s_veh[o][0], s_veh[o][2], k);
-      ob[size_t(w.O) * q.H + i] = mpc_track(s_veh[o][1], s_veh[o][3], k);
+      if constexpr (kPlanned) {  // d
+        ob[i] = mpc_veh_track(s_P, s_coef[o], k);
+        ob[size_t(w.O) * q.H + i] = mpc_veh_track(s_P, s_coef[o] + 11, k);
+      } else {
+        ob[i] = mpc_track(s_veh[o][0], s_veh[o][2], k);
+        ob[size_t(w.O) * q.H + i] = mpc_track(s_veh[o][1], s_veh[o][3], k);
+      }
     }
   }
   if (q.x_obs) {
@@ -100,8 +158,13 @@ __global__ __launch_bounds__(kMpcThreads) void k_mpc_step(const MpcStepParams q)
     float* yo = q.y_obs + size_t(ep) * w.O * kMpcTrack;
     for (int i = tid; i < w.O * kMpcTrack; i += kMpcThreads) {
       const int o = i / kMpcTrack, k = i - o * kMpcTrack;
-      xo[i] = mpc_track(s_veh[o][0], s_veh[o][2], k);
-      yo[i] = mpc_track(s_veh[o][1], s_veh[o][3], k);
+      if constexpr (kPlanned) {  // d
+        xo[i] = mpc_veh_track(s_P, s_coef[o], k);
+        yo[i] = mpc_veh_track(s_P, s_coef[o] + 11, k);
+      } else {
+        xo[i] = mpc_track(s_veh[o][0], s_veh[o][2], k);
+        yo[i] = mpc_track(s_veh[o][1], s_veh[o][3], k);
+      }
     }
   }
   if (q.kcol && tid < 44) q.solve_c[size_t(ep) * 44 + tid] = mpc_solve_column(q.kcol, s_init, tid);
@@ -132,10 +195,22 @@ __global__ __launch_bounds__(kMpcThreads) void k_mpc_step(const MpcStepParams q)
     q.pop[size_t(ep) * w.B * 8 + i] = world_pop(mean, q.chol, q.pop0 + size_t(i >> 3) * 8, i & 7);
 }
 
+__global__ __launch_bounds__(kMpcThreads) void k_mpc_step(const MpcStepParams q) {
+  mpc_step_body<false>(q, nullptr);
+}
+
+__global__ __launch_bounds__(kMpcThreads) void k_mpc_step_planned(const MpcStepParams q, const MpcVehParams pv) {
+  mpc_step_body<true>(q, &pv);
+}
+
 }  // namespace
 
 void launch_mpc_step(const MpcStepParams& q, int episodes, hipStream_t s) {
   hipLaunchKernelGGL(k_mpc_step, dim3(episodes), dim3(kMpcThreads), 0, s, q);
+}
+
+void launch_mpc_step_planned(const MpcStepParams& q, const MpcVehParams& pv, int episodes, hipStream_t s) {
+  hipLaunchKernelGGL(k_mpc_step_planned, dim3(episodes), dim3(kMpcThreads), 0, s, q, pv);
 }
 
 }  // namespace mpcmmd

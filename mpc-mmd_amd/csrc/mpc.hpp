@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mpc_step.hpp"
+#include "mpc_vehicle.hpp"
 
 namespace mpcmmd {
 
@@ -42,6 +43,16 @@ struct MpcStepParams {
   float* plan;                     // [E][30] cx, cy, mean: the chained route's log of the plan, or null
 };
 
+// The planned instantiation's further arguments: the
+// constants in device memory and the per-episode arrays of mpcmmd_mpc_planned.
+struct MpcVehParams {
+  MpcVehConsts k;
+  float* acc;           // [E][O][2]
+  const float* target;  // [E][O][2]
+  float* log;           // [E][O][6], or null
+};
+
 void launch_mpc_step(const MpcStepParams& q, int episodes, hipStream_t s);
+void launch_mpc_step_planned(const MpcStepParams& q, const MpcVehParams& pv, int episodes, hipStream_t s);
 
 }  // namespace mpcmmd

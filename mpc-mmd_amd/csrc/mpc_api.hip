@@ -12,6 +12,10 @@
 // validators' inputs from the device buffers the solve used, then
 // mpcmmd_validate's and mpcmmd_validate_risk's own launches write the tick's row
 // of the validation log, on the handle's stream or on the context's side stream.
+// With the vehicle policy configured (mpcmmd_mpc_plan_vehicles, DESIGN.md section
+// 23) the reset's and every tick's step is k_mpc_step_planned: the constants, the
+// accelerations, the targets and the vehicle log live in the context, and the
+// loop gains no copy, synchronisation or allocation.
 #include <array>
 #include <cmath>
 #include <cstring>
@@ -57,6 +61,13 @@ struct mpcmmd_mpc {
   hipStream_t side = nullptr;                       // the validators' stream of an overlapped stage
   hipEvent_t ev_prep = nullptr, ev_done = nullptr;  // the prep is done; the side stream's tick is done
   bool side_pending = false;                        // ev_done was recorded since the last synchronisation
+  // the planned vehicles (off: veh_on false, none of the buffers exists)
+  bool veh_on = false;
+  int veh_E = 0;                 // the episodes the staged arrays are for
+  std::vector<void*> veh_bufs;   // the policy's device allocations
+  MpcVehParams pv{};             // the constants, the live accelerations, the targets
+  float* veh_acc0 = nullptr;     // [Emax][O][2] the staged accelerations every reset starts from
+  float* veh_log = nullptr;      // [Tmax][Emax][O][6]
 };
 
 namespace {
@@ -105,7 +116,13 @@ void enqueue_step(mpcmmd_mpc* c, int tick, bool reset) {
   q.logd = c->logd + row * 2, q.logf = c->logf + row * 12, q.logi = c->logi + row * 4;
   q.plan = c->plan + row * 30;
   q.chol = c->chol;
-  launch_mpc_step(q, c->E, h->stream);
+  if (c->veh_on) {
+    MpcVehParams pv = c->pv;
+    pv.log = c->veh_log + row * size_t(q.w.O) * 6;
+    launch_mpc_step_planned(q, pv, c->E, h->stream);
+  } else {
+    launch_mpc_step(q, c->E, h->stream);
+  }
   HIPC(hipGetLastError());
 }
 
@@ -178,6 +195,40 @@ void drop_validation(mpcmmd_mpc* c) {
   c->val_on = false;
 }
 
+// frees the vehicle policy's buffers
+void drop_vehicles(mpcmmd_mpc* c) {
+  for (void* d : c->veh_bufs) (void)hipFree(d);
+  c->veh_bufs.clear();
+  c->pv = MpcVehParams{};
+  c->veh_acc0 = c->veh_log = nullptr;
+  c->veh_on = false, c->veh_E = 0;
+}
+
+template <class T>
+T* veh_alloc(mpcmmd_mpc* c, size_t count, const void* src = nullptr) {
+  void* d = nullptr;
+  HIPC(hipMalloc(&d, (count ? count : 4) * sizeof(T)));
+  c->veh_bufs.push_back(d);
+  if (src && count) HIPC(hipMemcpy(d, src, count * sizeof(T), hipMemcpyHostToDevice));
+  return static_cast<T*>(d);
+}
+
+// the constants of t in device memory, allocated by `up(src, doubles)`
+template <class F>
+MpcVehConsts upload_vehicle_consts(const MpcVehTables& t, F&& up) {
+  MpcVehConsts k;
+  k.kinv_x = up(t.qp->kinv_x.data(), t.qp->kinv_x.size());
+  k.kinv_y = up(t.qp->kinv_y.data(), t.qp->kinv_y.size());
+  k.colsum_x = up(t.qp->colsum_x.data(), t.qp->colsum_x.size());
+  k.colsum_y = up(t.qp->colsum_y.data(), t.qp->colsum_y.size());
+  k.P = up(t.qp->P.data(), t.qp->P.size());
+  k.adv = up(t.adv.data(), t.adv.size());
+  return k;
+}
+
+int step_device(const mpcmmd_mpc_model* m, int32_t device, int32_t n_episodes, int32_t tick,
+                const mpcmmd_mpc_step_io* io, const mpcmmd_mpc_planned* pl);
+
 }  // namespace
 
 extern "C" {
@@ -196,9 +247,39 @@ int mpcmmd_mpc_first_normals(const mpcmmd_config* cfg, float* out) {
   return MPCMMD_OK;
 }
 
+int mpcmmd_mpc_step_host_planned(const mpcmmd_mpc_model* m, int32_t tick, const mpcmmd_mpc_step_io* io,
+                                 const mpcmmd_mpc_planned* pl) {
+  if (int rc = check_mpc(m, io)) return rc;
+  if (int rc = check_mpc_planned(m, pl)) return rc;
+  try {
+    const MpcVehTables t = mpc_vehicle_tables(m->dt);
+    const MpcVehConsts vc = t.view();
+    mpc_step_host(*m, tick, *io, mpc_draw, pl, &vc);
+    return MPCMMD_OK;
+  } catch (const std::exception& e) {
+    return fail(MPCMMD_E_INVALID, e.what());
+  }
+}
+
 int mpcmmd_mpc_step_device(const mpcmmd_mpc_model* m, int32_t device, int32_t n_episodes, int32_t tick,
                            const mpcmmd_mpc_step_io* io) {
   if (int rc = check_mpc(m, io)) return rc;
+  return step_device(m, device, n_episodes, tick, io, nullptr);
+}
+
+int mpcmmd_mpc_step_device_planned(const mpcmmd_mpc_model* m, int32_t device, int32_t n_episodes, int32_t tick,
+                                   const mpcmmd_mpc_step_io* io, const mpcmmd_mpc_planned* pl) {
+  if (int rc = check_mpc(m, io)) return rc;
+  if (int rc = check_mpc_planned(m, pl)) return rc;
+  return step_device(m, device, n_episodes, tick, io, pl);
+}
+
+}  // extern "C"
+
+namespace {
+
+int step_device(const mpcmmd_mpc_model* m, int32_t device, int32_t n_episodes, int32_t tick,
+                const mpcmmd_mpc_step_io* io, const mpcmmd_mpc_planned* pl) {
   if (n_episodes < 1 || n_episodes > 65535) return fail(MPCMMD_E_INVALID, "mpc: 1 <= n_episodes <= 65535");
   return guarded([&] {
     int count = 0;
@@ -246,13 +327,28 @@ int mpcmmd_mpc_step_device(const mpcmmd_mpc_model* m, int32_t device, int32_t n_
     q.logd = static_cast<double*>(io_buf(io->log_d, E * MPCMMD_MPC_LOG_D * 8, false));
     q.logf = static_cast<float*>(io_buf(io->log_f, E * MPCMMD_MPC_LOG_F * 4, false));
     q.logi = static_cast<int32_t*>(io_buf(io->log_i, E * MPCMMD_MPC_LOG_I * 4, false));
-    launch_mpc_step(q, n_episodes, nullptr);
+    if (pl) {
+      const MpcVehTables t = mpc_vehicle_tables(m->dt);
+      MpcVehParams pv{};
+      pv.k = upload_vehicle_consts(
+          t, [&](const double* src, size_t n) { return static_cast<const double*>(in(src, n * 8)); });
+      pv.target = static_cast<const float*>(in(pl->veh_target, E * O * 2 * 4));
+      pv.acc = static_cast<float*>(io_buf(pl->veh_acc, E * O * 2 * 4, true));
+      pv.log = pl->veh_log ? static_cast<float*>(io_buf(pl->veh_log, E * O * 6 * 4, false)) : nullptr;
+      launch_mpc_step_planned(q, pv, n_episodes, nullptr);
+    } else {
+      launch_mpc_step(q, n_episodes, nullptr);
+    }
     HIPC(hipGetLastError());
     HIPC(hipDeviceSynchronize());
     for (const Out& o : outs) HIPC(hipMemcpy(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost));
     return MPCMMD_OK;
   });
 }
+
+}  // namespace
+
+extern "C" {
 
 int mpcmmd_mpc_create(mpcmmd_handle* h, const mpcmmd_mpc_model* m, int32_t max_ticks, mpcmmd_mpc** out) {
   if (!h || !m || !out) return fail(MPCMMD_E_INVALID, "null argument");
@@ -305,6 +401,7 @@ void mpcmmd_mpc_destroy(mpcmmd_mpc* c) {
   if (c->h->stream) (void)hipStreamSynchronize(c->h->stream);  // the steps in flight
   if (c->side) (void)hipStreamSynchronize(c->side);            // and the validators
   drop_validation(c);
+  drop_vehicles(c);
   for (void* d : c->bufs) (void)hipFree(d);
   delete c;
 }
@@ -315,6 +412,8 @@ int mpcmmd_mpc_reset(mpcmmd_mpc* c, int32_t n_episodes, const double* pos, const
     return fail(MPCMMD_E_INVALID, "null argument");
   if (n_episodes < 1 || n_episodes > c->Emax)
     return fail(MPCMMD_E_INVALID, "mpc: n_episodes must be 1..max_configs of the handle");
+  if (c->veh_on && n_episodes != c->veh_E)
+    return fail(MPCMMD_E_INVALID, "mpc: n_episodes is not the one mpcmmd_mpc_plan_vehicles staged");
   double cv[64];
   for (int i = 0; i < 64; ++i) cv[i] = double(cov[i]);
   if (!chol8(cv, c->chol_host.data())) return fail(MPCMMD_E_INVALID, "cov_param_init is not positive definite");
@@ -330,6 +429,7 @@ int mpcmmd_mpc_reset(mpcmmd_mpc* c, int32_t n_episodes, const double* pos, const
     HIPC(hipMemcpy(c->q.pos, pos, E * 2 * 8, hipMemcpyHostToDevice));
     HIPC(hipMemcpy(c->q.vel, vel, E * 3 * 4, hipMemcpyHostToDevice));
     if (O) HIPC(hipMemcpy(c->q.veh, vehicles, E * O * 4 * 4, hipMemcpyHostToDevice));
+    if (c->veh_on && O) HIPC(hipMemcpy(c->pv.acc, c->veh_acc0, E * O * 2 * 4, hipMemcpyDeviceToDevice));
     HIPC(hipMemcpy(c->q.done, running.data(), E * 4, hipMemcpyHostToDevice));
     HIPC(hipMemcpy(c->chol, c->chol_host.data(), 64 * 8, hipMemcpyHostToDevice));
     HIPC(hipMemcpy(h->p.mean, mean, E * 8 * 4, hipMemcpyHostToDevice));
@@ -508,6 +608,61 @@ int mpcmmd_mpc_validation_inputs(mpcmmd_mpc* c, double* cx, double* cy, double* 
     back(cx, c->vp.cx, E * kNvar * 8), back(cy, c->vp.cy, E * kNvar * 8), back(init_state, c->vp.init, E * 6 * 8);
     back(x_obs, c->vp.x_obs, E * O * kMpcTrack * 4), back(y_obs, c->vp.y_obs, E * O * kMpcTrack * 4);
     back(keys, c->vp.keys, E * 4);
+    return MPCMMD_OK;
+  });
+}
+
+int mpcmmd_mpc_plan_vehicles(mpcmmd_mpc* c, int32_t n_episodes, const float* veh_target, const float* veh_acc) {
+  if (!c) return fail(MPCMMD_E_INVALID, "null argument");
+  MpcVehTables t{};
+  if (veh_target) {
+    if (n_episodes < 1 || n_episodes > c->Emax)
+      return fail(MPCMMD_E_INVALID, "mpc: n_episodes must be 1..max_configs of the handle");
+    if (!(c->q.w.dt < 15.0f)) return fail(MPCMMD_E_INVALID, "mpc vehicles: 0 < dt < 15");
+    try {
+      t = mpc_vehicle_tables(c->q.w.dt);
+    } catch (const std::exception& e) {
+      return fail(MPCMMD_E_INVALID, e.what());
+    }
+  }
+  const int rc = guarded([&] {
+    check_device(c->h);
+    sync_streams(c);  // nothing in flight reads the buffers about to go
+    drop_vehicles(c);
+    c->reset_done = false;  // the policy changes with the episodes: the next run needs a reset
+    if (!veh_target) return MPCMMD_OK;
+    const size_t Em = size_t(c->Emax), Tm = size_t(c->Tmax), O = size_t(c->q.w.O), n = size_t(n_episodes) * O * 2;
+    c->pv.k = upload_vehicle_consts(t, [&](const double* src, size_t cnt) { return veh_alloc<double>(c, cnt, src); });
+    c->pv.target = veh_alloc<float>(c, Em * O * 2, nullptr);
+    c->pv.acc = veh_alloc<float>(c, Em * O * 2);
+    c->veh_acc0 = veh_alloc<float>(c, Em * O * 2);
+    c->veh_log = veh_alloc<float>(c, Tm * Em * O * 6);
+    if (n) {
+      HIPC(hipMemcpy(const_cast<float*>(c->pv.target), veh_target, n * 4, hipMemcpyHostToDevice));
+      if (veh_acc) HIPC(hipMemcpy(c->veh_acc0, veh_acc, n * 4, hipMemcpyHostToDevice));
+      else HIPC(hipMemset(c->veh_acc0, 0, n * 4));
+    }
+    c->veh_E = n_episodes;
+    c->veh_on = true;
+    return MPCMMD_OK;
+  });
+  if (rc != MPCMMD_OK) {  // a failed allocation leaves no half-made policy
+    drop_vehicles(c);
+    (void)hipGetLastError();
+  }
+  return rc;
+}
+
+int mpcmmd_mpc_vehicle_log(mpcmmd_mpc* c, int32_t ticks, float* veh) {
+  if (!c || !veh) return fail(MPCMMD_E_INVALID, "null argument");
+  if (ticks < 0 || ticks > c->Tmax) return fail(MPCMMD_E_INVALID, "mpc: tick range");
+  if (!c->veh_on) return fail(MPCMMD_E_STATE, "mpcmmd_mpc_vehicle_log without the vehicle policy");
+  return guarded([&] {
+    check_device(c->h);
+    sync_streams(c);
+    const size_t row = size_t(c->q.w.O) * 6 * 4, E = size_t(c->E), Em = size_t(c->Emax);
+    if (ticks > 0 && E > 0 && row > 0)  // rows of Emax -> [ticks][n_episodes]: one strided copy
+      HIPC(hipMemcpy2D(veh, E * row, c->veh_log, Em * row, E * row, size_t(ticks), hipMemcpyDeviceToHost));
     return MPCMMD_OK;
   });
 }

@@ -3,6 +3,8 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <stdexcept>
+#include <string>
 
 #include "host_api.hpp"
 
@@ -52,7 +54,26 @@ int check_mpc(const mpcmmd_mpc_model* m, const mpcmmd_mpc_step_io* io) {
   return MPCMMD_OK;
 }
 
-void mpc_step_host(const mpcmmd_mpc_model& m, int tick, const mpcmmd_mpc_step_io& io, MpcDraw draw) {
+MpcVehConsts MpcVehTables::view() const {
+  return MpcVehConsts{qp->kinv_x.data(), qp->kinv_y.data(), qp->colsum_x.data(), qp->colsum_y.data(),
+                      qp->P.data(),      adv.data()};
+}
+
+MpcVehTables mpc_vehicle_tables(float dt) {
+  std::vector<double> adv = build_vehicle_advance(dt);  // throws before the QP is built
+  static const DynObsConsts qp = build_dyn_obs_consts();
+  return MpcVehTables{&qp, std::move(adv)};
+}
+
+int check_mpc_planned(const mpcmmd_mpc_model* m, const mpcmmd_mpc_planned* pl) {
+  if (!m || !pl) return fail(MPCMMD_E_INVALID, "null argument");
+  if (!(m->dt > 0.0f && m->dt < 15.0f)) return fail(MPCMMD_E_INVALID, "mpc vehicles: 0 < dt < 15");
+  if (m->num_obs > 0 && (!pl->veh_acc || !pl->veh_target)) return fail(MPCMMD_E_INVALID, "mpc vehicles: null array");
+  return MPCMMD_OK;
+}
+
+void mpc_step_host(const mpcmmd_mpc_model& m, int tick, const mpcmmd_mpc_step_io& io, MpcDraw draw,
+                   const mpcmmd_mpc_planned* pl, const MpcVehConsts* vc) {
   const MpcScalars w = mpc_scalars(m);
   MpcEgo e{io.pos[0], io.pos[1], io.vel[0], io.vel[1], io.vel[2]};
   MpcControl c = mpc_controller<HostMath>(m.pdot2, m.pddot1, io.cx, io.cy);
@@ -66,6 +87,15 @@ void mpc_step_host(const mpcmmd_mpc_model& m, int tick, const mpcmmd_mpc_step_io
     e = mpc_ego_step<HostMath>(e, c.a, c.s, w.dt, &ax, &ay);
     for (int o = 0; o < w.O; ++o) {
       float* v = io.vehicles + size_t(o) * 4;
+      if (pl) {  // S <- advance(plan(S, target))
+        float* a = pl->veh_acc + size_t(o) * 2;
+        const float S[6] = {v[0], v[1], v[2], v[3], a[0], a[1]};
+        float coef[kVehCoef];
+        for (int j = 0; j < kVehCoef; ++j) coef[j] = mpc_veh_coef(*vc, S, pl->veh_target + size_t(o) * 2, j);
+        for (int k = 0; k < 4; ++k) v[k] = mpc_veh_advance(vc->adv, coef, k);
+        for (int k = 0; k < 2; ++k) a[k] = mpc_veh_advance(vc->adv, coef, 4 + k);
+        continue;
+      }
       v[0] = v[0] + v[2] * w.dt;
       v[1] = v[1] + v[3] * w.dt;
     }
@@ -92,6 +122,18 @@ void mpc_step_host(const mpcmmd_mpc_model& m, int tick, const mpcmmd_mpc_step_io
   mpc_st0(io.init_state, io.st0);
   for (int o = 0; o < w.O; ++o) {
     const float* v = io.vehicles + size_t(o) * 4;
+    if (pl) {  // the tracks of the plan of the state the step leaves
+      const float* a = pl->veh_acc + size_t(o) * 2;
+      const float S[6] = {v[0], v[1], v[2], v[3], a[0], a[1]};
+      if (pl->veh_log) std::memcpy(pl->veh_log + size_t(o) * 6, S, sizeof S);
+      float coef[kVehCoef];
+      for (int j = 0; j < kVehCoef; ++j) coef[j] = mpc_veh_coef(*vc, S, pl->veh_target + size_t(o) * 2, j);
+      for (int k = 0; k < kMpcTrack; ++k) {
+        io.x_obs[size_t(o) * kMpcTrack + k] = mpc_veh_track(vc->P, coef, k);
+        io.y_obs[size_t(o) * kMpcTrack + k] = mpc_veh_track(vc->P, coef + 11, k);
+      }
+      continue;
+    }
     for (int k = 0; k < kMpcTrack; ++k) {
       io.x_obs[size_t(o) * kMpcTrack + k] = mpc_track(v[0], v[2], k);
       io.y_obs[size_t(o) * kMpcTrack + k] = mpc_track(v[1], v[3], k);
@@ -102,3 +144,28 @@ void mpc_step_host(const mpcmmd_mpc_model& m, int tick, const mpcmmd_mpc_step_io
 }
 
 }  // namespace mpcmmd
+
+extern "C" int mpcmmd_mpc_vehicle_constant(float dt, const char* name, double* dst, size_t count) {
+  using namespace mpcmmd;
+  if (!name) return fail(MPCMMD_E_INVALID, "null argument");
+  if (!(dt > 0.0f && dt < 15.0f)) return fail(MPCMMD_E_INVALID, "mpc vehicles: 0 < dt < 15");
+  try {
+    const MpcVehTables t = mpc_vehicle_tables(dt);
+    const std::string n(name);
+    const std::vector<double>* v = n == "kinv_x"     ? &t.qp->kinv_x
+                                   : n == "kinv_y"   ? &t.qp->kinv_y
+                                   : n == "colsum_x" ? &t.qp->colsum_x
+                                   : n == "colsum_y" ? &t.qp->colsum_y
+                                   : n == "P"        ? &t.qp->P
+                                   : n == "adv"      ? &t.adv
+                                                     : nullptr;
+    if (!v) return fail(MPCMMD_E_INVALID, "unknown constant " + n);
+    if (dst) {
+      if (count < v->size()) return fail(MPCMMD_E_INVALID, "dst too small");
+      std::memcpy(dst, v->data(), v->size() * 8);
+    }
+    return int(v->size());
+  } catch (const std::exception& e) {
+    return fail(MPCMMD_E_INVALID, e.what());
+  }
+}

@@ -38,6 +38,8 @@ SYMBOLS = (
     "mpcmmd_mpc_step_host", "mpcmmd_mpc_step_device", "mpcmmd_mpc_create", "mpcmmd_mpc_destroy",
     "mpcmmd_mpc_reset", "mpcmmd_mpc_run", "mpcmmd_mpc_log", "mpcmmd_mpc_first_normals",
     "mpcmmd_mpc_validate", "mpcmmd_mpc_validation_log", "mpcmmd_mpc_validation_inputs",
+    "mpcmmd_mpc_vehicle_constant", "mpcmmd_mpc_step_host_planned", "mpcmmd_mpc_step_device_planned",
+    "mpcmmd_mpc_plan_vehicles", "mpcmmd_mpc_vehicle_log",
 )
 
 
@@ -173,6 +175,10 @@ class MpcStepIO(C.Structure):
                  ("key", C.POINTER(C.c_uint32))])
 
 
+class MpcPlanned(C.Structure):
+    _fields_ = [(k, C.POINTER(C.c_float)) for k in ("veh_acc", "veh_target", "veh_log")]
+
+
 MPC_LOG_D = ("x", "y")
 MPC_LOG_F = ("vx", "vy", "psi", "a_c", "s_c", "a", "s", "u0", "u1", "u2", "clear", "curv")
 MPC_LOG_I = ("lane_out", "collided", "goal", "frozen")
@@ -291,6 +297,14 @@ def lib():
         L.mpcmmd_mpc_validate.argtypes = [vp, C.POINTER(MpcValidation)]
         L.mpcmmd_mpc_validation_log.argtypes = [vp, C.c_int32, ip, ip, fp, fp, fp]
         L.mpcmmd_mpc_validation_inputs.argtypes = [vp, dp, dp, dp, fp, fp, C.POINTER(C.c_uint32)]
+    if hasattr(L, "mpcmmd_mpc_plan_vehicles"):   # an older library lacks the planned vehicles: the callers raise
+        L.mpcmmd_mpc_vehicle_constant.argtypes = [C.c_float, C.c_char_p, C.POINTER(C.c_double), C.c_size_t]
+        L.mpcmmd_mpc_step_host_planned.argtypes = [C.POINTER(MpcModelStruct), C.c_int32, C.POINTER(MpcStepIO),
+                                                   C.POINTER(MpcPlanned)]
+        L.mpcmmd_mpc_step_device_planned.argtypes = [C.POINTER(MpcModelStruct), C.c_int32, C.c_int32, C.c_int32,
+                                                     C.POINTER(MpcStepIO), C.POINTER(MpcPlanned)]
+        L.mpcmmd_mpc_plan_vehicles.argtypes = [vp, C.c_int32, fp, fp]
+        L.mpcmmd_mpc_vehicle_log.argtypes = [vp, C.c_int32, fp]
     L.mpcmmd_path_smoothing.argtypes = [C.c_int32, fp, fp, C.c_float, fp, fp]
     L.mpcmmd_path_parameters.argtypes = [C.c_int32, fp, fp, fp, fp, fp, fp, fp, fp, fp]
     L.mpcmmd_global_to_frenet.argtypes = [C.POINTER(Path), C.c_int32, fp, fp, fp, fp, fp, fp, fp]
@@ -857,7 +871,28 @@ def pop0_normals(cfg):
     return out
 
 
-def mpc_step(model, tick, cx, cy, u, mean, pos, vel, vehicles, done_tick, device=None, keys=None):
+VEHICLE_CONSTANTS = ("kinv_x", "kinv_y", "colsum_x", "colsum_y", "P", "adv")
+
+
+def _need_planned(L):
+    if not hasattr(L, "mpcmmd_mpc_plan_vehicles"):
+        raise NativeError(f"{LIB_PATH} has no mpcmmd_mpc_plan_vehicles (built before the planned vehicles existed): "
+                          "rebuild it")
+
+
+def mpc_vehicle_constant(dt, name):
+    """mpcmmd_mpc_vehicle_constant: one of VEHICLE_CONSTANTS for the tick length ``dt`` (0 < dt < 15), the
+    constants of the planned vehicles, as a flat float64 array.  No GPU needed."""
+    L = lib()
+    _need_planned(L)
+    n = check(L.mpcmmd_mpc_vehicle_constant(float(np.float32(dt)), name.encode(), None, 0))
+    out = np.empty(n, np.float64)
+    check(L.mpcmmd_mpc_vehicle_constant(float(np.float32(dt)), name.encode(),
+                                        out.ctypes.data_as(C.POINTER(C.c_double)), n))
+    return out
+
+
+def mpc_step(model, tick, cx, cy, u, mean, pos, vel, vehicles, done_tick, device=None, keys=None, planned=None):
     """One step of E episodes of the synthetic closed loop: mpcmmd_mpc_step_host
     per episode (device None), or one k_mpc_step launch on GPU ``device``
     (mpcmmd_mpc_step_device).  cx, cy [E, 11], u [E, 3] -- or None: drawn by the
@@ -866,7 +901,13 @@ def mpc_step(model, tick, cx, cy, u, mean, pos, vel, vehicles, done_tick, device
     vehicles [E, num_obs, 4], done_tick [E] is not modified.  Returns a dict:
     the new state under the same names, the next tick's init_state [E, 6], st0
     [E, 8], x_obs, y_obs [E, O, 100], pop [E, B, 8] and the log row log_d
-    [E, 2], log_f [E, 12], log_i [E, 4] (MPC_LOG_D / _F / _I name the columns)."""
+    [E, 2], log_f [E, 12], log_i [E, 4] (MPC_LOG_D / _F / _I name the columns).
+
+    planned = dict(acc=[E, O, 2], target=[E, O, 2]) steps the vehicles by their re-planned QP
+    (mpcmmd_mpc_step_host_planned / _device_planned): acc the accelerations
+    (ax, ay) that complete the rows of ``vehicles`` to the state S (None: zeros), target (v_des,
+    y_des) per vehicle.  The dict gains veh_acc [E, O, 2] (the new accelerations) and veh_log
+    [E, O, 6] (S after the step)."""
     L = lib()
     if not hasattr(L, "mpcmmd_mpc_step_host"):
         raise NativeError(f"{LIB_PATH} has no mpcmmd_mpc_step_host (built before the entry point existed): rebuild it")
@@ -888,14 +929,33 @@ def mpc_step(model, tick, cx, cy, u, mean, pos, vel, vehicles, done_tick, device
     names = [k for k, _ in MpcStepIO._fields_]
     types = dict(MpcStepIO._fields_)
 
+    def rows(src, k, e):
+        row = src[k][e:]   # the device call takes episode 0's address with every episode behind it
+        return C.cast(row.ctypes.data, C.POINTER(C.c_float)) if row.size else None
+
     def io_of(e):
         ptr = []
         for k in names:
-            row = a[k][e:]   # the device call takes episode 0's address with every episode behind it
+            row = a[k][e:]
             ptr.append(C.cast(row.ctypes.data, types[k]) if row.size else None)
         return MpcStepIO(*ptr)
 
-    if device is None:
+    if planned is not None:
+        _need_planned(L)
+        if set(planned) - {"acc", "target"} or "target" not in planned:
+            raise TypeError("mpc_step: planned takes target and acc")
+        acc = planned.get("acc")
+        p = dict(veh_acc=np.zeros((E, O, 2), np.float32) if acc is None else f(acc, O, 2),
+                 veh_target=f(planned["target"], O, 2), veh_log=np.empty((E, O, 6), np.float32))
+        pl_of = lambda e: MpcPlanned(*(rows(p, k, e) for k in ("veh_acc", "veh_target", "veh_log")))
+        if device is None:
+            for e in range(E):
+                check(L.mpcmmd_mpc_step_host_planned(C.byref(m.c), int(tick), C.byref(io_of(e)), C.byref(pl_of(e))))
+        else:
+            check(L.mpcmmd_mpc_step_device_planned(C.byref(m.c), int(device), E, int(tick), C.byref(io_of(0)),
+                                                   C.byref(pl_of(0))))
+        a.update(veh_acc=p["veh_acc"], veh_log=p["veh_log"])
+    elif device is None:
         for e in range(E):
             check(L.mpcmmd_mpc_step_host(C.byref(m.c), int(tick), C.byref(io_of(e))))
     else:
@@ -967,6 +1027,27 @@ class Mpc:
                                      li.ctypes.data_as(ip), _fptr(pl), dn.ctypes.data_as(ip)))
         return dict(log_d=ld, log_f=lf, log_i=li, cx=pl[..., :11].copy(), cy=pl[..., 11:22].copy(),
                     mean=pl[..., 22:].copy(), done_tick=dn)
+
+    def plan_vehicles(self, target, acc=None):
+        """mpcmmd_mpc_plan_vehicles: from the next ``reset`` on (which must be given as many episodes),
+        the vehicles follow their re-planned QP.  target [E, O, 2] = v_des,
+        y_des per vehicle, acc [E, O, 2] the start accelerations (None: zeros).  ``target`` None turns
+        the policy off."""
+        _need_planned(self._L)
+        if target is None:
+            check(self._L.mpcmmd_mpc_plan_vehicles(self._c, 0, None, None))
+            return
+        O = self.model.num_obs
+        tg = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, O, 2))
+        ac = None if acc is None else np.ascontiguousarray(np.asarray(acc, np.float32).reshape(tg.shape))
+        check(self._L.mpcmmd_mpc_plan_vehicles(self._c, tg.shape[0], _fptr(tg), None if ac is None else _fptr(ac)))
+
+    def vehicle_log(self, ticks):
+        """veh [ticks, E, O, 6]: every planned vehicle's state (x, y, vx, vy, ax, ay) after each tick's step."""
+        _need_planned(self._L)
+        out = np.zeros((max(int(ticks), 0), self.E, self.model.num_obs, 6), np.float32)
+        check(self._L.mpcmmd_mpc_vehicle_log(self._c, int(ticks), _fptr(out)))
+        return out
 
     def validate(self, rollouts, alpha=0.98, sigma=(), overlap=True):
         """mpcmmd_mpc_validate: from the next ``reset`` on, every tick of ``run`` also computes the

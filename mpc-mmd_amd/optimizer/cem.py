@@ -122,7 +122,7 @@ class CEM:
 
     # ------------------------------------------------------------------
     def run_episodes(self, cost, vehicles, starts, ticks, *, chained=True, device_step=None, u=None, key_base=0,
-                     keys=None, goal_x=200.0, mean=None, cov=None, v_des=15.0, dt=0.15, validate=None):
+                     keys=None, goal_x=200.0, mean=None, cov=None, v_des=15.0, dt=0.15, validate=None, planned=None):
         """E closed-loop episodes of ``ticks`` ticks in lockstep: solve, apply
         the plan's first control under the noise model, re-solve from the new state, warm-started
         from the previous mean.  vehicles [E, num_obs, 4] = x, y, vx, vy; starts [E, 4] = x, y, vx, vy
@@ -147,8 +147,18 @@ class CEM:
         solve for the E episodes as one batch: the stage's reference and its fallback, same bits.  The
         dict gains val_counts [ticks, E, 2] (count, count_lane), val_count_pos [ticks, E, 3], val_stats
         [ticks, E, 4, 3] (var, cvar, mean, max by obs, lane_lb, lane_ub), val_mmd [ticks, E, 3, S] and
-        val_est [ticks, E, 2] (the cost_lane, cost_obs the solve itself estimated)."""
+        val_est [ticks, E, 2] (the cost_lane, cost_obs the solve itself estimated).
+
+        planned = dict(target=[E, num_obs, 2], acc=None) has every vehicle follow the dynamic
+        driver's lane-tracking QP and re-plan it each tick from its own state
+        instead of moving at constant velocity: target = (v_des, y_des) per vehicle, acc
+        [E, num_obs, 2] the start accelerations (None: zeros).  All three routes, the same bits; the
+        dict gains veh [ticks, E, num_obs, 6]: every vehicle's (x, y, vx, vy, ax, ay) after each tick."""
         h, cfg = self._h, self._cfg
+        pl = None
+        if planned is not None:
+            if set(planned) - {"target", "acc"} or "target" not in planned:
+                raise TypeError("run_episodes: planned takes target and acc")
         val = None
         if validate is not None:
             val = dict(alpha=0.98, sigma=(), overlap=True)
@@ -177,6 +187,11 @@ class CEM:
             u = np.ascontiguousarray(np.asarray(u, f32).reshape(ticks, E, 3))
         model = _native.MpcModel(cfg, cov, _native.pop0_normals(cfg), goal_x=goal_x, dt=dt, a_obs=self.a_obs,
                                  b_obs=self.b_obs)
+        if planned is not None:
+            acc = planned.get("acc")
+            pl = dict(target=np.ascontiguousarray(np.asarray(planned["target"], f32).reshape(E, self.num_obs, 2)),
+                      acc=np.zeros((E, self.num_obs, 2), f32) if acc is None else
+                      np.ascontiguousarray(np.asarray(acc, f32).reshape(E, self.num_obs, 2)))
         if chained is not False:
             counts = (ticks,) if chained is True else tuple(int(c) for c in chained)
             if sum(counts) != ticks:
@@ -185,6 +200,8 @@ class CEM:
             try:
                 if val is not None:   # before the reset: the stage takes effect there
                     ctx.validate(val["rollouts"], val["alpha"], val["sigma"], val["overlap"])
+                if pl is not None:    # likewise
+                    ctx.plan_vehicles(pl["target"], pl["acc"])
                 ctx.reset(pos, vel, veh, mean, cov, u, keys)
                 k = 0
                 for c in counts:
@@ -193,6 +210,8 @@ class CEM:
                 out = ctx.log(ticks)
                 if val is not None:
                     out.update(ctx.validation_log(ticks))
+                if pl is not None:
+                    out["veh"] = ctx.vehicle_log(ticks)
                 return out
             finally:
                 ctx.close()
@@ -209,11 +228,13 @@ class CEM:
                         acc_const_noise=float(cfg.acc_const_noise), steer_const_noise=float(cfg.steer_const_noise),
                         num_rollouts=int(val["rollouts"]), variant=self.variant, seed=int(cfg.seed),
                         device=int(cfg.device))
+        if pl is not None:
+            out["veh"] = np.empty((ticks, E, self.num_obs, 6), f32)
         done = np.full(E, -1, np.int32)
         zero = np.zeros((E, 11), f32)
         # tick 0's inputs: the step of a frozen episode writes the inputs of the state it is given
         st = _native.mpc_step(model, -1, zero, zero, np.zeros((E, 3), f32), mean, pos, vel, veh, np.zeros(E, np.int32),
-                              device=device_step)
+                              device=device_step, planned=pl)
         for k in range(ticks):
             res = h.solve_batch(cost, [int(np.int32(np.uint32((k + int(q)) & 0xFFFFFFFF))) for q in keys],
                                 st["init_state"], mean, cov, st["x_obs"], st["y_obs"], v_des)
@@ -229,8 +250,11 @@ class CEM:
                 out["val_mmd"][k] = rk["mmd"]
                 out["val_est"][k] = [(r["cost_lane"], r["cost_obs"]) for r in res]
             st = _native.mpc_step(model, k, cx, cy, None if u is None else u[k], mean, pos, vel, veh, done,
-                                  device=device_step, keys=keys)
+                                  device=device_step, keys=keys, planned=pl)
             pos, vel, veh, done = st["pos"], st["vel"], st["vehicles"], st["done_tick"]
+            if pl is not None:
+                pl = dict(target=pl["target"], acc=st["veh_acc"])
+                out["veh"][k] = st["veh_log"]
             out["cx"][k], out["cy"][k], out["mean"][k] = cx, cy, mean
             for name in ("log_d", "log_f", "log_i"):
                 out[name][k] = st[name]

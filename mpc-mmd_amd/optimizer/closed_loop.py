@@ -19,9 +19,16 @@ equal.
 
 Episode e is configuration e of the sweep's scenario generator
 (``sweep.obstacles``): its obstacle positions and, for the dynamic variant, the
-generator's initial velocities, which the world keeps constant (the dynamic
-generator's lane-tracking QP is not re-planned).  The ego starts as the sweep
-starts it.  Episodes also differ by their key (the solver's streams and the
+generator's initial velocities.  By default (``--vehicles constant``) the world
+keeps those velocities constant; with ``--vehicles planned`` every vehicle follows
+the dynamic generator's lane-tracking QP and re-plans it each tick from its own
+state towards the driver's targets: the tracked speed
+``obs_data(1).sampling_param(43 e + 11 o + 5)[0]`` of vehicle o of episode e, the
+driver's seeds, and the lane y = -1.75 -- the cut-in of the dynamic driver, whose
+tick-0 tracks are then the sweep's own.  The npz then also holds ``veh``
+[T, E, O, 6], every vehicle's (x, y, vx, vy, ax, ay) after each tick, and one more
+line per cost gives the share of vehicles inside |y + 1.75| < 0.5 at their
+episode's last live tick.  The ego starts as the sweep starts it.  Episodes also differ by their key (the solver's streams and the
 perturbation's variates, which the library draws after each tick's solve:
 normals, or Beta(2 |control|, 5 |control|) with ``--noise beta``).  Per cost
 ``closed_loop_<cost>.npz`` holds ``log_d`` [T, E, 2] (x, y), ``log_f`` [T, E, 12]
@@ -71,6 +78,30 @@ def scenario(variant, episodes, num_obs):
         veh[e] = np.stack([np.asarray(ob[k], np.float64).reshape(num_obs) for k in ("x", "y", "vx", "vy")], 1)
         keys[e] = int(ob["idx_mpc"])
     return veh, keys
+
+
+def vehicle_targets(episodes, num_obs):
+    """[E, num_obs, 2] = v_des, y_des of the planned vehicles: the dynamic driver's seeds
+    (``dynamic_obstacles``: 43 k + 11 tt + 5) and its target lane."""
+    from .obs_data_generate_dynamic import obs_data
+    gen = obs_data(1)
+    tg = np.empty((episodes, num_obs, 2), np.float32)
+    for e in range(episodes):
+        for o in range(num_obs):
+            tg[e, o] = gen.sampling_param(43 * e + 11 * o + 5)[0], -1.75
+    return tg
+
+
+def summarise_vehicles(res, half_width=0.5, lane=-1.75):
+    """(mean, sample sd) over the episodes of the share of an episode's vehicles inside
+    |y - lane| < half_width at the episode's last live tick."""
+    veh = np.asarray(res["veh"])
+    T, E = veh.shape[:2]
+    done = np.asarray(res["done_tick"])
+    last = np.where(done >= 0, done, T - 1)
+    y = veh[last, np.arange(E), :, 1] if T and veh.shape[2] else np.zeros((E, 0))
+    inside = np.abs(y.astype(np.float64) - lane) < half_width
+    return dict(in_lane=_mean_std(inside.mean(axis=1) if inside.shape[1] else np.zeros(E)))
 
 
 def starts_of(variant, episodes):
@@ -128,7 +159,8 @@ def closed_loop(prob, costs, vehicles, starts, ticks, out_dir=None, run=None, lo
     the module docstring.  Returns {cost: (the result, its summary)}."""
     run = run or _run
     val = kw.get("validate")
-    keys = KEYS + (VAL_KEYS if val is not None else ())
+    planned = kw.get("planned") is not None
+    keys = KEYS + (VAL_KEYS if val is not None else ()) + (("veh",) if planned else ())
     results = {}
     for cost in costs:
         if cost not in COSTS:
@@ -151,6 +183,11 @@ def closed_loop(prob, costs, vehicles, starts, ticks, out_dir=None, run=None, lo
                 f"{sv['count_share'][0]:.4f} +- {sv['count_share'][1]:.4f}, mean validated CVaR(obs) = "
                 f"{sv['cvar_obs'][0]:.4f} +- {sv['cvar_obs'][1]:.4f}, mean solver cost_obs = "
                 f"{sv['est_obs'][0]:.4f} +- {sv['est_obs'][1]:.4f}")
+        if planned:
+            sp = summarise_vehicles(res)
+            s.update(sp)
+            log(f"{cost}: planned vehicles, share inside |y + 1.75| < 0.5 at the last live tick = "
+                f"{sp['in_lane'][0]:.4f} +- {sp['in_lane'][1]:.4f}")
         results[cost] = (res, s)
     return results
 
@@ -163,6 +200,9 @@ def parse_args(argv=None):
     ap.add_argument("--costs", nargs="+", default=list(COSTS), choices=sorted(COSTS))
     ap.add_argument("--host-step", action="store_true",
                     help="solve tick by tick and step the world on the host (mpcmmd_mpc_step_host)")
+    ap.add_argument("--vehicles", default="constant", choices=["constant", "planned"],
+                    help="constant velocity, or every vehicle re-plans the dynamic driver's QP each tick (the veh array, "
+                         "one more line)")
     ap.add_argument("--validate", type=int, default=None, metavar="R",
                     help="also roll every tick's plan out under R fresh noise rows (the val_* arrays, a second line)")
     ap.add_argument("--alpha", type=float, default=0.98, help="quantile level of the validated VaR / CVaR")
@@ -192,6 +232,13 @@ def validation_of(a):
     return dict(validate=dict(rollouts=a.validate, alpha=a.alpha, sigma=a.risk_sigma, overlap=not a.no_overlap))
 
 
+def planned_of(a):
+    """The ``planned=`` keyword of the parsed options ({} without --vehicles planned)."""
+    if a.vehicles != "planned":
+        return {}
+    return dict(planned=dict(target=vehicle_targets(a.episodes, a.num_obs), acc=None))
+
+
 def main(argv=None):
     a = parse_args(argv)
     from .cem import CEM
@@ -201,7 +248,8 @@ def main(argv=None):
     vehicles, keys = scenario(a.variant, a.episodes, a.num_obs)
     try:
         closed_loop(prob, a.costs, vehicles, starts_of(a.variant, a.episodes), a.ticks, a.out, keys=keys,
-                    v_des=a.v_des, goal_x=a.goal_x, chained=not a.host_step, device_step=None, **validation_of(a))
+                    v_des=a.v_des, goal_x=a.goal_x, chained=not a.host_step, device_step=None, **validation_of(a),
+                    **planned_of(a))
     finally:
         prob.handle.close()
 
