@@ -782,6 +782,49 @@ int mpcmmd_world_step_host(const mpcmmd_world_model* m, int32_t tick, const mpcm
 int mpcmmd_world_step_device(const mpcmmd_world_model* m, int32_t device, int32_t n_episodes, int32_t tick,
                              const mpcmmd_world_step_io* io);
 
+/* Routed vehicles (csrc/world_vehicle.hpp): instead of
+ * moving at constant velocity, vehicle j follows the route's splines at a
+ * constant signed lateral offset d (left positive, the sign of log_f's d) with
+ * the state s (fp64 arc length) and v (fp32 speed >= 0), and accelerates by the
+ * intelligent-driver car-following model towards its target speed v0 behind its
+ * leader: the nearest of the other vehicles and the ego (after its move: arc of
+ * its closest route point, its lateral offset, its new speed) with |d_k - d_j|
+ * < lane_tol and s_k > s_j, gap = (s_k - s_j) - length; equal gaps: the lowest
+ * vehicle index, the ego last.  Every s read is the value before the step.
+ *   a  = clip(acc_max (1 - (v/v0)^4 - (ss / max(gap, gap_min))^2), acc_min, acc_max),
+ *   ss = gap0 + max(0, v headway + v (v - v_lead) / (2 sqrt(acc_max brake)))
+ * (no leader: the last term is 0), v' = max(v + a dt, 0), s' = s + v' dt.  A
+ * vehicle with !(v0 > 0) is parked (v' = 0, s' = s).  A live episode's step
+ * advances (s, v); every step, frozen ones included, writes the vehicles' rows
+ * (x, y, vx, vy, psi) from (s, d, v) into io->vehicles -- whose contents on
+ * entry are not read -- and the rest of the step reads those rows as before.
+ * All in fp64 in this order, rounded once; every NaN is stored as the quiet NaN.
+ * A model of this library's, not CARLA's traffic manager.
+ *
+ * mpcmmd_world_step_host_routed / _device_routed are mpcmmd_world_step_host /
+ * _device with that policy; the kernel is the routed instantiation of
+ * k_world_step and equals the host step in every word
+ * (tests/test_gpu_world_vehicles.py).  tick < 0 is the reset-mode step of the
+ * chained route: no plan is read (cx, cy, steer, u may hold anything), nothing
+ * moves, done_tick and the log rows are not written; it makes tick 0's inputs
+ * and the vehicles' rows from the start states.
+ *
+ * Before any HIP call, beyond the plain step's errors: MPCMMD_E_INVALID for a
+ * NULL rt, a NULL veh_s, veh_v or veh_param when total_obs > 0, or scalars
+ * that break acc_max > 0, brake > 0, gap_min > 0, acc_min < 0, lane_tol >= 0. */
+typedef struct mpcmmd_world_routed { /* leading axis n_episodes for the device step */
+  double* veh_s;          /* [total_obs] updated in place unless frozen */
+  float* veh_v;           /* [total_obs] likewise */
+  const float* veh_param; /* [total_obs][2] d, v0 */
+  float* veh_log;         /* [total_obs][2] v after this step and the acceleration applied (0: parked, frozen), or
+                             NULL; s after the step is veh_s itself, in fp64; not written when tick < 0 */
+  float acc_max, brake, gap0, headway, length, lane_tol, gap_min, acc_min;
+} mpcmmd_world_routed;
+int mpcmmd_world_step_host_routed(const mpcmmd_world_model* m, int32_t tick, const mpcmmd_world_step_io* io,
+                                  const mpcmmd_world_routed* rt);
+int mpcmmd_world_step_device_routed(const mpcmmd_world_model* m, int32_t device, int32_t n_episodes, int32_t tick,
+                                    const mpcmmd_world_step_io* io, const mpcmmd_world_routed* rt);
+
 /* The chained route: E <= max_configs closed-loop episodes on a tick context's
  * handle with nothing crossing the host between two solves.  A world context
  * belongs to one tick context (its num_path and its handle's num_obs must be
@@ -839,6 +882,37 @@ int mpcmmd_world_run(mpcmmd_world* w, int32_t cost_kind, int32_t tick_begin, int
                      const float* v_des, float threshold);
 int mpcmmd_world_log(mpcmmd_world* w, int32_t ticks, double* log_d, float* log_f, int32_t* log_i, float* plan,
                      int32_t* done_tick);
+
+/* Routed vehicles on the chained route (the policy of mpcmmd_world_routed
+ * above; no ABI version change: detect the entry points by their symbols).
+ *
+ * mpcmmd_world_route_vehicles stages the start states veh_s, veh_v
+ * [n_episodes][total_obs], the parameters veh_param [n_episodes][total_obs][2]
+ * = d, v0 and the eight scalars (acc_max, brake, gap0, headway, length,
+ * lane_tol, gap_min, acc_min, in this order) in the world context, allocates
+ * the states and a vehicle log [max_ticks][max_configs][total_obs] there (none
+ * of it in the handle's buffer list) and synchronises.  It takes effect at the
+ * next mpcmmd_world_reset, which must be given the same n_episodes
+ * (MPCMMD_E_INVALID otherwise) and whose `vehicles` argument is then ignored
+ * and may be NULL: the reset-mode step makes tick 0's rows from (s, v, d).
+ * Every reset starts from the staged states again.  A run before that reset is
+ * MPCMMD_E_STATE.  NULL arrays (all three) turn the policy off and free its
+ * memory.  With the policy on the reset-mode step and every tick's step are
+ * the routed kernel; the loop gains no readback, synchronisation or
+ * allocation, and the validation stage reads whatever rows the step wrote.
+ *
+ * mpcmmd_world_vehicle_log synchronises and reads back the first `ticks` rows:
+ * veh_s [ticks][E][total_obs] (fp64) and veh_va [ticks][E][total_obs][2] = v
+ * and the acceleration applied, every vehicle's state after each tick's step;
+ * MPCMMD_E_STATE with the policy off.  Every word equals the host-stepped
+ * loop's (tests/test_gpu_closed_loop_vehicles.py).
+ *
+ * Before any HIP call: MPCMMD_E_INVALID for a NULL w, some but not all arrays
+ * NULL, NULL scalars with arrays given, n_episodes outside 1..max_configs, the
+ * scalars' rules of mpcmmd_world_routed, a tick range outside [0, max_ticks]. */
+int mpcmmd_world_route_vehicles(mpcmmd_world* w, int32_t n_episodes, const double* veh_s, const float* veh_v,
+                                const float* veh_param, const float* scalars);
+int mpcmmd_world_vehicle_log(mpcmmd_world* w, int32_t ticks, double* veh_s, float* veh_va);
 
 /* The validation stage of the chained route: the Monte-Carlo risk of every
  * tick's plan, computed inside the loop from the device buffers the solve just

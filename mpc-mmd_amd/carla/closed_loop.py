@@ -38,6 +38,18 @@ line per cost gives, over the live (tick, episode) pairs, the plans' mean
 Monte-Carlo collision probability count_rows / R and the mean validated CVaR of
 the obstacle cost beside the mean of the solver's own obstacle cost.
 
+With ``--vehicles routed [--speed-limit V]`` the vehicles are not parked: they
+follow the route at their spawn lane with car-following (DESIGN.md section 24,
+a model of this project's, not CARLA's traffic manager).  Vehicle i of episode
+e starts at rest at the spawn offset of ``replay.py`` ahead of the episode's
+start, on its spawn lane, with the target speed (1 - p) V, p drawn from the
+reference's (0.4, 0.6, 0.4) by a NumPy generator seeded with the episode's key;
+V defaults to 8.33 m/s.  The npz then also holds ``veh`` [T, E, total_obs, 3]
+(s, v and the acceleration applied after each tick's step), and one more line
+per cost gives the mean vehicle speed, the smallest bumper gap between two
+vehicles on one lane and the count of ticks on which the ego was some
+vehicle's leader, over the live (tick, episode) pairs.
+
 The episode runner is a parameter of ``closed_loop`` (``run=``), so the
 accounting is testable without a GPU.
 """
@@ -54,6 +66,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 COSTS = ("mmd", "cvar", "det")
 V_DES = 10.0
 LOG_KEYS = ("log_d", "log_f", "log_i", "done_tick", "collided", "goal")
+SPEED_LIMIT = 8.33                # m/s (30 km/h)
+SPEED_DIFFERENCE = (0.4, 0.6, 0.4)  # carla_simulation.py:222-225: vehicle_percentage_speed_difference
+KEY_STRIDE = 100000               # run_episodes' default: episode e has the key KEY_STRIDE e
+# the routed vehicles' scalars as the library defaults them (_native.ROUTED_DEFAULTS); the accounting reads three
+LENGTH, LANE_TOL = 4.5, 1.75
 VAL_KEYS = ("val_counts", "val_count_pos", "val_var", "val_cvar", "val_mean", "val_max", "val_mmd", "val_est")
 
 
@@ -87,6 +104,54 @@ def synthetic_starts(route, episodes, spread=0.0, v0=0.1):
     s = spread * np.arange(episodes) / max(episodes, 1)
     x, y, psi = rt.at(s)
     return np.stack([x, y, np.full(episodes, v0), np.arctan2(np.sin(psi), np.cos(psi))], 1)
+
+
+def routed_traffic(route, starts, town="Town05", speed_limit=SPEED_LIMIT, key_base=0, key_stride=KEY_STRIDE):
+    """The ``routed`` dict of ``run_episodes`` for the spawns of ``replay.py``: s [E, total_obs] the spawn
+    offsets ahead of each episode's start (its arc length on the route), d the spawn lanes, v = 0 and
+    v0 = (1 - p) speed_limit with p one of SPEED_DIFFERENCE per vehicle, drawn by
+    ``np.random.default_rng(key of the episode)``."""
+    R = _replay()
+    offs, lanes = R.SPAWN["Town10HD" if town.startswith("Town10") else "Town05"]
+    rt = R.Route(*route)
+    starts = np.asarray(starts, np.float64).reshape(-1, 4)
+    E, V = starts.shape[0], offs.size
+    s0 = np.array([rt.s[int(np.argmin(np.hypot(rt.x - x, rt.y - y)))] for x, y in starts[:, :2]])
+    p = np.stack([np.random.default_rng(int(key_base) + int(key_stride) * e).choice(SPEED_DIFFERENCE, V)
+                  for e in range(E)])
+    return dict(s=s0[:, None] + offs[None, :], v=np.zeros((E, V), np.float32),
+                d=np.tile(np.array([lanes[i % 2] for i in range(V)], np.float32), (E, 1)),
+                v0=((1.0 - p) * float(speed_limit)).astype(np.float32))
+
+
+def summarise_vehicles(res, routed):
+    """The three figures of one cost's routed traffic over the live (tick, episode) pairs
+    (``summarise``'s convention): the mean vehicle speed as (mean, sample sd) over the episodes, the
+    smallest bumper gap s_k - s_j - length between two vehicles on one lane (|d_k - d_j| < lane_tol),
+    and the count of ticks on which the ego -- at (arc, d) of its log row -- was the nearest thing
+    ahead of some vehicle on its lane."""
+    veh = np.asarray(res["veh"], np.float64)
+    T, E, V = veh.shape[:3]
+    done = np.asarray(res["done_tick"])
+    last = np.where(done >= 0, done, T - 1)
+    live = np.arange(T)[:, None] <= last[None, :]
+    d = np.broadcast_to(np.asarray(routed["d"], np.float64).reshape(-1, V), (E, V))
+    length, tol = float(routed.get("length", LENGTH)), float(routed.get("lane_tol", LANE_TOL))
+    n = np.maximum(live.sum(axis=0), 1)
+    speed = np.where(live, veh[:, :, :, 1].mean(axis=2) if V else np.zeros((T, E)), 0.0).sum(axis=0) / n
+    s = veh[:, :, :, 0]
+    ahead = s[:, :, None, :] - s[:, :, :, None]                          # [T, E, j, k] = s_k - s_j
+    lane = np.abs(d[:, None, :] - d[:, :, None]) < tol                   # [E, j, k]
+    pair = lane[None] & (ahead > 0) & live[:, :, None, None]
+    gaps = np.where(pair, ahead - length, np.inf)
+    ego_s, ego_d = np.asarray(res["log_d"])[:, :, 2], np.asarray(res["log_f"], np.float64)[:, :, 12]
+    ego_ahead = ego_s[:, :, None] - s                                    # [T, E, j]
+    ego_lane = np.abs(ego_d[:, :, None] - d[None]) < tol
+    cand = ego_lane & (ego_ahead > 0)
+    nearest = np.where(pair, ahead, np.inf).min(axis=3) if V else np.zeros((T, E, 0))
+    leads = (cand & (ego_ahead < nearest)).any(axis=2) & live
+    return dict(vehicle_speed=_mean_std(speed), min_gap=float(gaps.min()) if gaps.size else float("inf"),
+                ego_led=int(leads.sum()))
 
 
 def _run(prob, cost, route, goal_index, vehicles, starts, ticks, **kw):
@@ -137,7 +202,8 @@ def closed_loop(prob, costs, route, goal_index, vehicles, starts, ticks, out_dir
     lines of the module docstring.  Returns {cost: (the result, its summary)}."""
     run = run or _run
     val = kw.get("validate")
-    keys = LOG_KEYS + (VAL_KEYS if val is not None else ())
+    routed = kw.get("routed")
+    keys = LOG_KEYS + (VAL_KEYS if val is not None else ()) + (("veh",) if routed is not None else ())
     results = {}
     for cost in costs:
         if cost not in COSTS:
@@ -159,11 +225,16 @@ def closed_loop(prob, costs, route, goal_index, vehicles, starts, ticks, out_dir
                 f"{sv['p_collision'][0]:.4f} +- {sv['p_collision'][1]:.4f}, mean validated CVaR(obs) = "
                 f"{sv['cvar_obs'][0]:.4f} +- {sv['cvar_obs'][1]:.4f}, mean solver cost_obs = "
                 f"{sv['est_obs'][0]:.4f} +- {sv['est_obs'][1]:.4f}")
+        if routed is not None:
+            sr = summarise_vehicles(res, routed)
+            s.update(sr)
+            log(f"{cost}: routed vehicles, mean speed = {sr['vehicle_speed'][0]:.4f} +- {sr['vehicle_speed'][1]:.4f} "
+                f"m/s, smallest bumper gap = {sr['min_gap']:.4f} m, ticks with the ego as a leader = {sr['ego_led']}")
         results[cost] = (res, s)
     return results
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="closed-loop CARLA episodes on the surrogate world")
     ap.add_argument("--synthetic", action="store_true", help="the synthetic route and spawns of replay.py")
     ap.add_argument("--town", default="Town05")
@@ -188,9 +259,18 @@ def main(argv=None):
                     help="also roll every tick's plan out under R fresh noise rows (Monte-Carlo risk of the plans)")
     ap.add_argument("--alpha", type=float, default=0.98, help="quantile level of the validated VaR / CVaR")
     ap.add_argument("--risk-sigma", type=float, nargs="*", default=[], metavar="s", help="MMD bandwidths (at most 8)")
+    ap.add_argument("--vehicles", default="parked", choices=["parked", "routed"],
+                    help="routed: the vehicles follow the route with car-following (DESIGN.md section 24)")
+    ap.add_argument("--speed-limit", type=float, default=SPEED_LIMIT, metavar="V",
+                    help="speed limit of the routed vehicles in m/s; each drives 40 or 60 per cent below it")
     a = ap.parse_args(argv)
     if not a.synthetic:
         ap.error("only --synthetic worlds are built in")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     if sys.path[0] != _HERE:
         sys.path.insert(0, _HERE)
     from optimizer import cem
@@ -199,8 +279,10 @@ def main(argv=None):
                    a.steer_const_noise, num_batch=a.num_batch, maxiter_cem=a.maxiter_cem, seed=a.seed,
                    max_configs=a.episodes)
     kw = {} if a.validate is None else dict(validate=dict(rollouts=a.validate, alpha=a.alpha, sigma=a.risk_sigma))
-    closed_loop(prob, a.costs, route, goal_index, vehicles, synthetic_starts(route, a.episodes, a.start_spread),
-                a.ticks, a.out, num_path=a.num_path, v_des=V_DES, seed=a.seed, chained=not a.host_step,
+    starts = synthetic_starts(route, a.episodes, a.start_spread)
+    if a.vehicles == "routed":
+        kw["routed"] = routed_traffic(route, starts, a.town, a.speed_limit)
+    closed_loop(prob, a.costs, route, goal_index, vehicles, starts, a.ticks, a.out, num_path=a.num_path, v_des=V_DES, seed=a.seed, chained=not a.host_step,
                 device_step=False, **kw)
     prob.close()
 

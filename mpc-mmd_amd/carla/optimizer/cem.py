@@ -183,7 +183,7 @@ class CEM:
 
     def run_episodes(self, cost, route, vehicles, starts, ticks, *, goal_index=None, num_path=600, mean=None, cov=None,
                      v_des=10.0, dt=0.05, threshold=0.1, u=None, key_base=0, key_stride=100000, seed=0,
-                     device_step=True, chained=False, validate=None):
+                     device_step=True, chained=False, validate=None, routed=None):
         """E closed-loop episodes of ``ticks`` ticks on the surrogate world
         (DESIGN.md section 19): each tick all E episodes are ONE batched solve
         through the tick route (E <= max_configs), then one world step turns
@@ -216,7 +216,17 @@ class CEM:
         cost_obs the solve itself estimated).  On the chained route the stage
         runs inside the loop on the device (mpcmmd_world_validate); on the two
         host-linked routes each tick's obs and path are read back and the
-        validator is called from the host -- the same bits, the slow way."""
+        validator is called from the host -- the same bits, the slow way.
+
+        ``routed`` = dict(s=, v=, d=, v0=, **scalars) replaces the constant-velocity
+        vehicles by route-following traffic with car-following (DESIGN.md section
+        24): s (float64 arc lengths on the route's splines), v (speeds), d (signed
+        lateral offsets, left positive) and v0 (target speeds; <= 0: parked), each
+        [total_obs] for every episode or [E, total_obs]; the scalars are
+        ``_native.ROUTED_SCALARS``.  ``vehicles`` is then ignored (None will do):
+        tick 0's rows come from (s, v, d).  The result gains veh [T, E, total_obs, 3]
+        = s, v and the acceleration applied after each tick's step, the same bits
+        on all three routes."""
         N = native()
         kinds = {"mmd": "mmd_opt", "cvar": "cvar", "det": "det"}
         if cost not in kinds:
@@ -240,6 +250,17 @@ class CEM:
         keys = int(key_base) + int(key_stride) * np.arange(E)
         mean = np.array([v_des] * 4 + [0.0] * 4, np.float32) if mean is None else np.asarray(mean, np.float32)
         cov = np.diag([20.0] * 4 + [100.0] * 4).astype(np.float32) if cov is None else np.asarray(cov, np.float32)
+        rt = None
+        if routed is not None:
+            if not {"s", "v", "d", "v0"} <= set(routed):
+                raise ValueError("routed: dict(s=..., v=..., d=..., v0=..., **scalars)")
+            V = np.asarray(routed["s"]).shape[-1] if np.ndim(routed["s"]) else 1
+            per = lambda a, dt: np.ascontiguousarray(np.broadcast_to(np.asarray(a, dt).reshape(-1, V), (E, V)))
+            rt = dict(s=per(routed["s"], np.float64), v=per(routed["v"], np.float32),
+                      param=np.stack([per(routed["d"], np.float32), per(routed["v0"], np.float32)], -1),
+                      **{k: x for k, x in routed.items() if k not in ("s", "v", "d", "v0")})
+            N.routed_scalars({k: x for k, x in rt.items() if k not in ("s", "v", "param")})   # unknown names raise
+            vehicles = np.zeros((V, 5), np.float32)
         vehicles = np.asarray(vehicles, np.float32).reshape(-1, 5)
         model, tk = self.world_model(route, vehicles.shape[0], goal_index, num_path, cov, dt, seed)
         if chained:
@@ -247,6 +268,8 @@ class CEM:
             try:
                 if val is not None:
                     world.validate(**val)
+                if rt is not None:
+                    world.route_vehicles(**rt)
                 world.reset(starts[:, :2], np.stack([starts[:, 2], starts[:, 3], np.zeros(E)], 1),
                             np.tile(vehicles[None], (E, 1, 1)), np.tile(mean.reshape(1, 8), (E, 1)), cov, u, keys)
                 k0 = 0
@@ -256,6 +279,8 @@ class CEM:
                 if k0 != T:
                     raise ValueError("chained: the tick counts must add up to ticks")
                 out = world.log(T)
+                if rt is not None:
+                    out["veh"] = world.vehicle_log(T)
                 if val is not None:
                     out.update(world.validation_log(T))
             finally:
@@ -271,7 +296,10 @@ class CEM:
         # a frozen step leaves the state alone and writes the raw inputs of the state it is given: tick 0's
         zero = lambda n: np.zeros((E, n), np.float32)
         nxt = N.world_step(model, -1, zero(11), zero(11), zero(4), zero(4), means, st["pos"], st["ego"],
-                           st["vehicles"], np.zeros(E, np.int32), device=dev)
+                           st["vehicles"], np.zeros(E, np.int32), device=dev, routed=rt)
+        if rt is not None:   # the reset-mode step made tick 0's rows
+            st["vehicles"] = nxt["vehicles"]
+            out_veh = np.empty((T, E, vehicles.shape[0], 3))
         out = dict(log_d=np.empty((T, E, 3)), log_f=np.empty((T, E, 13), np.float32),
                    log_i=np.empty((T, E, 4), np.int32), cx=np.empty((T, E, 11), np.float32),
                    cy=np.empty((T, E, 11), np.float32), steering=np.empty((T, E, 4), np.float32),
@@ -308,10 +336,16 @@ class CEM:
                     out["val_" + key][k] = r[key]
                 out["val_est"][k] = [[x["cost_lane"], x["cost_obs"]] for x in rs]
             nxt = N.world_step(model, k, out["cx"][k], out["cy"][k], out["steering"][k], None if u is None else u[k],
-                               means, st["pos"], st["ego"], st["vehicles"], st["done_tick"], device=dev, keys=keys)
+                               means, st["pos"], st["ego"], st["vehicles"], st["done_tick"], device=dev, keys=keys,
+                               routed=rt)
             st = {key: nxt[key] for key in st}
+            if rt is not None:
+                rt.update(s=nxt["veh_s"], v=nxt["veh_v"])
+                out_veh[k, :, :, 0], out_veh[k, :, :, 1:] = nxt["veh_s"], nxt["veh_log"]
             for key in ("log_d", "log_f", "log_i"):
                 out[key][k] = nxt[key]
+        if rt is not None:
+            out["veh"] = out_veh
         out["done_tick"] = st["done_tick"]
         done = np.where(st["done_tick"] >= 0, st["done_tick"], T - 1)
         at_end = out["log_i"][done, np.arange(E)]

@@ -17,6 +17,16 @@
 //      all threads: the first population, an element per thread
 // Latency-bound by construction (a handful of dependent fp64 chains); launched
 // once per tick.
+//
+// The kernel is a template on the vehicle policy (world.hpp).  With
+// WorldRoutedParams the vehicles need the ego's route
+// point and lateral offset, so phase 2 only stages their (s, d, v) in LDS beside
+// the route argmin, and after that barrier wave 0, a lane per vehicle, finds its
+// leader by broadcast reads of the staged states (the values before the step),
+// advances (s, v), evaluates its pose on the splines and writes its row; one
+// more barrier then hands the rows' clear term to thread 64.
+#include <type_traits>
+
 #include "cr_math.hpp"
 #include "world.hpp"
 #include "world_draw.hpp"
@@ -33,7 +43,9 @@ struct DevMath {
   static DEVI double acos64(double a) { return ::acos(a); }
 };
 
-__global__ __launch_bounds__(kWorldThreads) void k_world_step(const WorldStepParams q) {
+template <class Policy>
+__global__ __launch_bounds__(kWorldThreads) void k_world_step(const WorldStepParams q, const Policy pol) {
+  constexpr bool kRouted = std::is_same<Policy, WorldRoutedParams>::value;
   const WorldScalars& w = q.w;
   const int ep = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   __shared__ WorldEgo s_ego;
@@ -46,6 +58,8 @@ __global__ __launch_bounds__(kWorldThreads) void k_world_step(const WorldStepPar
   __shared__ int s_src[kWorldMaxObs];
   __shared__ double s_dist[kWorldMaxObs];
   __shared__ int s_kept;
+  __shared__ double s_rs[kRouted ? kWorldMaxObs : 1];  // the routed vehicles' states before the step
+  __shared__ float s_rd[kRouted ? kWorldMaxObs : 1], s_rv[kRouted ? kWorldMaxObs : 1];
 
   const bool frozen = q.reset || q.done[ep] >= 0;
   float* veh = q.veh + size_t(ep) * w.total * 5;
@@ -75,7 +89,12 @@ __global__ __launch_bounds__(kWorldThreads) void k_world_step(const WorldStepPar
   const WorldEgo e = s_ego;
 
   // 2
-  if (wave == 0) {
+  if constexpr (kRouted) {
+    if (wave == 0 && lane < w.total) {
+      const size_t j = size_t(ep) * w.total + lane;
+      s_rs[lane] = pol.s[j], s_rd[lane] = pol.param[j * 2], s_rv[lane] = pol.v[j];
+    }
+  } else if (wave == 0) {
     float t = -INFINITY;
     if (lane < w.total) {
       float v[5];
@@ -112,6 +131,34 @@ __global__ __launch_bounds__(kWorldThreads) void k_world_step(const WorldStepPar
   const int idx = int(uidx);  // n_route >= 1: some thread holds a key below ~0
   const double s0 = q.arc[idx];
 
+  if constexpr (kRouted) {  // the vehicles, behind the ego's route point
+    if (wave == 0) {
+      float t = -INFINITY;
+      if (lane < w.total) {
+        const size_t j = size_t(ep) * w.total + lane;
+        double s = s_rs[lane];
+        float v = s_rv[lane], a = 0.0f;
+        if (!frozen) {
+          const float d_ego = world_lateral(w, q.route_x, q.route_y, q.arc, q.sx, q.sy, idx, e);
+          const VehLeader l = vehicle_leader(pol.p, lane, w.total, s_rs, s_rd, 1, s_rv, s0, d_ego, e.v);
+          vehicle_advance(pol.p, w.dt, pol.param[j * 2 + 1], l, &s, &v, &a);
+          pol.s[j] = s, pol.v[j] = v;
+        }
+        if (!q.reset) {
+          if (pol.log) pol.log[j * 2] = v, pol.log[j * 2 + 1] = a;
+          if (pol.log_s) pol.log_s[j] = s;
+        }
+        float row[5];
+        vehicle_pose<DevMath>(q.arc, q.sx, q.sy, w.n_route, s, s_rd[lane], v, row);
+        for (int k = 0; k < 5; ++k) veh[lane * 5 + k] = row[k], s_veh[lane][k] = row[k];
+        t = clear_term<DevMath>(w, e, row);
+      }
+      const bool any_nan = __ballot(t != t) != 0;
+      const float m = wave_max(t != t ? -INFINITY : t);
+      if (lane == 0) s_clear = any_nan ? canon_nan(NAN) : m;
+    }
+  }
+
   // 3
   for (int i = tid; i < w.P; i += kWorldThreads)
     world_waypoint(w, q.arc, q.sx, q.sy, s0, e, i, q.xw + size_t(ep) * q.s_wp + i, q.yw + size_t(ep) * q.s_wp + i);
@@ -124,6 +171,7 @@ __global__ __launch_bounds__(kWorldThreads) void k_world_step(const WorldStepPar
       s0r[5] = s0r[6] = s0r[7] = 0.0f;
     }
   }
+  if constexpr (kRouted) __syncthreads();  // s_clear of the rows just written
   if (tid == 64 && !q.reset) {
     const WorldControl c = s_ctl;
     const float clear = s_clear;
@@ -188,7 +236,12 @@ __global__ __launch_bounds__(kWorldThreads) void k_world_step(const WorldStepPar
 }  // namespace
 
 void launch_world_step(const WorldStepParams& q, int episodes, hipStream_t s) {
-  hipLaunchKernelGGL(k_world_step, dim3(episodes), dim3(kWorldThreads), 0, s, q);
+  hipLaunchKernelGGL(k_world_step<WorldConstantVelocity>, dim3(episodes), dim3(kWorldThreads), 0, s, q,
+                     WorldConstantVelocity{});
+}
+
+void launch_world_step_routed(const WorldStepParams& q, const WorldRoutedParams& r, int episodes, hipStream_t s) {
+  hipLaunchKernelGGL(k_world_step<WorldRoutedParams>, dim3(episodes), dim3(kWorldThreads), 0, s, q, r);
 }
 
 }  // namespace mpcmmd

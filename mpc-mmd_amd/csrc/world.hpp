@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "world_step.hpp"
+#include "world_vehicle.hpp"
 
 namespace mpcmmd {
 
@@ -38,6 +39,21 @@ struct WorldStepParams {
   int32_t* logi;                                    // [E][4]
 };
 
+// The vehicle policy k_world_step is instantiated on.  Constant velocity: the rows of q.veh move by
+// (vx, vy) dt and carry no further state.
+struct WorldConstantVelocity {};
+
+// Routed (world_vehicle.hpp): the arrays of mpcmmd_world_routed with a leading episode axis, device pointers.
+struct WorldRoutedParams {
+  VehScalars p;
+  double* s;           // [E][total]
+  float* v;            // [E][total]
+  const float* param;  // [E][total][2] d, v0
+  float* log;          // [E][total][2] v, a of this step, or null
+  double* log_s;       // [E][total] s after this step (the chained route's vehicle log), or null
+};
+
 void launch_world_step(const WorldStepParams& q, int episodes, hipStream_t s);
+void launch_world_step_routed(const WorldStepParams& q, const WorldRoutedParams& r, int episodes, hipStream_t s);
 
 }  // namespace mpcmmd

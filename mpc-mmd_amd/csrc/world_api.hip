@@ -11,7 +11,10 @@
 // its CEM iterations and its world step, the Monte-Carlo risk of the plan it
 // just made: k_world_validate_prep packs the validators' inputs from the device
 // buffers the solve used, then mpcmmd_validate_carla_risk's own launches write
-// the tick's row of the validation log.
+// the tick's row of the validation log.  With routed vehicles configured
+// (mpcmmd_world_route_vehicles) the reset's and every
+// tick's step is the routed instantiation of k_world_step: the states, the
+// parameters and the vehicle log live in the context.
 #include <array>
 #include <cmath>
 #include <cstring>
@@ -57,6 +60,15 @@ struct mpcmmd_world {
   float *vl_var = nullptr, *vl_cvar = nullptr, *vl_mean = nullptr, *vl_max = nullptr;  // [Tmax][Emax][3]
   float* vl_mmd = nullptr;                                              // [Tmax][Emax][3][S]
   float* vl_est = nullptr;                                              // [Tmax][Emax][2]
+  // the routed vehicles (off: veh_on false, none of the buffers exists)
+  bool veh_on = false;
+  int veh_E = 0;                // the episodes the staged arrays are for
+  std::vector<void*> veh_bufs;  // the policy's device allocations
+  WorldRoutedParams rv{};       // scalars, states [E][V], parameters
+  double* veh_s0 = nullptr;     // [E][V] the staged start states
+  float* veh_v0 = nullptr;
+  double* veh_log_s = nullptr;  // [Tmax][Emax][V]
+  float* veh_log = nullptr;     // [Tmax][Emax][V][2]
 };
 
 namespace {
@@ -93,7 +105,13 @@ void enqueue_step(mpcmmd_world* w, int tick, bool reset) {
   q.logd = w->logd + row * 3, q.logf = w->logf + row * 13, q.logi = w->logi + row * 4;
   q.plan = w->plan + row * 34;
   q.chol = w->chol;
-  launch_world_step(q, w->E, h->stream);
+  if (w->veh_on) {
+    WorldRoutedParams r = w->rv;
+    r.log = w->veh_log + row * size_t(q.w.total) * 2, r.log_s = w->veh_log_s + row * size_t(q.w.total);
+    launch_world_step_routed(q, r, w->E, h->stream);
+  } else {
+    launch_world_step(q, w->E, h->stream);
+  }
   HIPC(hipGetLastError());
 }
 
@@ -140,6 +158,25 @@ void drop_validation(mpcmmd_world* w) {
   for (size_t i = w->val_first; i < w->bufs.size(); ++i) (void)hipFree(w->bufs[i]);
   w->bufs.resize(w->val_first);
   w->val_on = false;
+}
+
+// frees the routed vehicles' buffers
+void drop_vehicles(mpcmmd_world* w) {
+  for (void* d : w->veh_bufs) (void)hipFree(d);
+  w->veh_bufs.clear();
+  w->rv = WorldRoutedParams{};
+  w->veh_s0 = w->veh_log_s = nullptr;
+  w->veh_v0 = w->veh_log = nullptr;
+  w->veh_on = false, w->veh_E = 0;
+}
+
+template <class T>
+T* veh_alloc(mpcmmd_world* w, size_t count, const void* src = nullptr) {
+  void* d = nullptr;
+  HIPC(hipMalloc(&d, (count ? count : 4) * sizeof(T)));
+  w->veh_bufs.push_back(d);
+  if (src && count) HIPC(hipMemcpy(d, src, count * sizeof(T), hipMemcpyHostToDevice));
+  return static_cast<T*>(d);
 }
 
 }  // namespace
@@ -199,6 +236,7 @@ void mpcmmd_world_destroy(mpcmmd_world* w) {
   if (!w) return;
   (void)hipSetDevice(w->h->device);
   if (w->h->stream) (void)hipStreamSynchronize(w->h->stream);  // the steps in flight
+  drop_vehicles(w);
   for (void* d : w->bufs) (void)hipFree(d);
   delete w;
 }
@@ -206,10 +244,12 @@ void mpcmmd_world_destroy(mpcmmd_world* w) {
 int mpcmmd_world_reset(mpcmmd_world* w, int32_t n_episodes, const double* pos, const float* ego,
                        const float* vehicles, const float* mean, const float* cov, const float* u,
                        const int32_t* keys) {
-  if (!w || !pos || !ego || !mean || !cov || !keys || (w->w.total > 0 && !vehicles))
+  if (!w || !pos || !ego || !mean || !cov || !keys || (w->w.total > 0 && !vehicles && !w->veh_on))
     return fail(MPCMMD_E_INVALID, "null argument");
   if (n_episodes < 1 || n_episodes > w->Emax)
     return fail(MPCMMD_E_INVALID, "world: n_episodes must be 1..max_configs of the handle");
+  if (w->veh_on && n_episodes != w->veh_E)
+    return fail(MPCMMD_E_INVALID, "world: n_episodes is not the one mpcmmd_world_route_vehicles staged");
   double cv[64];
   for (int i = 0; i < 64; ++i) cv[i] = double(cov[i]);
   if (!chol8(cv, w->chol_host.data())) return fail(MPCMMD_E_INVALID, "cov_param_init is not positive definite");
@@ -224,7 +264,12 @@ int mpcmmd_world_reset(mpcmmd_world* w, int32_t n_episodes, const double* pos, c
     const std::vector<int32_t> running(E, -1);
     HIPC(hipMemcpy(w->q.pos, pos, E * 2 * 8, hipMemcpyHostToDevice));
     HIPC(hipMemcpy(w->q.ego, ego, E * 3 * 4, hipMemcpyHostToDevice));
-    if (V) HIPC(hipMemcpy(w->q.veh, vehicles, E * V * 5 * 4, hipMemcpyHostToDevice));
+    if (w->veh_on && V) {  // the rows come from the reset-mode step
+      HIPC(hipMemcpy(w->rv.s, w->veh_s0, E * V * 8, hipMemcpyDeviceToDevice));
+      HIPC(hipMemcpy(w->rv.v, w->veh_v0, E * V * 4, hipMemcpyDeviceToDevice));
+    } else if (V) {
+      HIPC(hipMemcpy(w->q.veh, vehicles, E * V * 5 * 4, hipMemcpyHostToDevice));
+    }
     HIPC(hipMemcpy(w->q.done, running.data(), E * 4, hipMemcpyHostToDevice));
     HIPC(hipMemcpy(w->chol, w->chol_host.data(), 64 * 8, hipMemcpyHostToDevice));
     HIPC(hipMemcpy(h->p.mean, mean, E * 8 * 4, hipMemcpyHostToDevice));
@@ -274,6 +319,62 @@ int mpcmmd_world_log(mpcmmd_world* w, int32_t ticks, double* log_d, float* log_f
     };
     back(log_d, w->logd, 3 * 8), back(log_f, w->logf, 13 * 4), back(log_i, w->logi, 4 * 4), back(plan, w->plan, 34 * 4);
     HIPC(hipMemcpy(done_tick, w->q.done, E * 4, hipMemcpyDeviceToHost));
+    return MPCMMD_OK;
+  });
+}
+
+int mpcmmd_world_route_vehicles(mpcmmd_world* w, int32_t n_episodes, const double* veh_s, const float* veh_v,
+                                const float* veh_param, const float* scalars) {
+  if (!w) return fail(MPCMMD_E_INVALID, "null argument");
+  const bool off = !veh_s && !veh_v && !veh_param;
+  mpcmmd_world_routed rt{};
+  if (!off) {
+    if (!veh_s || !veh_v || !veh_param || !scalars) return fail(MPCMMD_E_INVALID, "null argument");
+    if (n_episodes < 1 || n_episodes > w->Emax)
+      return fail(MPCMMD_E_INVALID, "world: n_episodes must be 1..max_configs of the handle");
+    rt.veh_s = const_cast<double*>(veh_s), rt.veh_v = const_cast<float*>(veh_v), rt.veh_param = veh_param;
+    rt.acc_max = scalars[0], rt.brake = scalars[1], rt.gap0 = scalars[2], rt.headway = scalars[3];
+    rt.length = scalars[4], rt.lane_tol = scalars[5], rt.gap_min = scalars[6], rt.acc_min = scalars[7];
+    mpcmmd_world_model mm{};
+    mm.total_obs = w->w.total;
+    if (int rc = check_world_routed(&mm, &rt)) return rc;
+  }
+  const int rc = guarded([&] {
+    check_device(w->h);
+    HIPC(hipStreamSynchronize(w->h->stream));  // nothing in flight reads the buffers about to go
+    drop_vehicles(w);
+    w->reset_done = false;  // the policy changes with the episodes: the next run needs a reset
+    if (off) return MPCMMD_OK;
+    const size_t E = size_t(n_episodes), V = size_t(w->w.total), rows = size_t(w->Tmax) * size_t(w->Emax);
+    w->rv.p = veh_scalars(rt);
+    w->veh_s0 = veh_alloc<double>(w, E * V, veh_s), w->veh_v0 = veh_alloc<float>(w, E * V, veh_v);
+    w->rv.param = veh_alloc<float>(w, E * V * 2, veh_param);
+    w->rv.s = veh_alloc<double>(w, E * V), w->rv.v = veh_alloc<float>(w, E * V);
+    w->veh_log_s = veh_alloc<double>(w, rows * V), w->veh_log = veh_alloc<float>(w, rows * V * 2);
+    HIPC(hipDeviceSynchronize());
+    w->veh_E = n_episodes;
+    w->veh_on = true;
+    return MPCMMD_OK;
+  });
+  if (rc != MPCMMD_OK) {  // a failed allocation leaves no half-made policy
+    drop_vehicles(w);
+    (void)hipGetLastError();
+  }
+  return rc;
+}
+
+int mpcmmd_world_vehicle_log(mpcmmd_world* w, int32_t ticks, double* veh_s, float* veh_va) {
+  if (!w || !veh_s || !veh_va) return fail(MPCMMD_E_INVALID, "null argument");
+  if (ticks < 0 || ticks > w->Tmax) return fail(MPCMMD_E_INVALID, "world: tick range");
+  if (!w->veh_on) return fail(MPCMMD_E_STATE, "mpcmmd_world_vehicle_log without routed vehicles");
+  return guarded([&] {
+    check_device(w->h);
+    HIPC(hipStreamSynchronize(w->h->stream));
+    const size_t E = size_t(w->E), Em = size_t(w->Emax), V = size_t(w->w.total);
+    if (ticks == 0 || E == 0 || V == 0) return MPCMMD_OK;
+    // rows of Emax -> [ticks][n_episodes]: one strided copy per array
+    HIPC(hipMemcpy2D(veh_s, E * V * 8, w->veh_log_s, Em * V * 8, E * V * 8, size_t(ticks), hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy2D(veh_va, E * V * 8, w->veh_log, Em * V * 8, E * V * 8, size_t(ticks), hipMemcpyDeviceToHost));
     return MPCMMD_OK;
   });
 }
@@ -422,9 +523,17 @@ extern "C" int mpcmmd_world_step_host(const mpcmmd_world_model* m, int32_t tick,
   return MPCMMD_OK;
 }
 
-extern "C" int mpcmmd_world_step_device(const mpcmmd_world_model* m, int32_t device, int32_t n_episodes, int32_t tick,
-                                        const mpcmmd_world_step_io* io) {
+extern "C" int mpcmmd_world_step_host_routed(const mpcmmd_world_model* m, int32_t tick, const mpcmmd_world_step_io* io,
+                                             const mpcmmd_world_routed* rt) {
   if (int rc = check_world(m, io)) return rc;
+  if (int rc = check_world_routed(m, rt)) return rc;
+  world_step_host(*m, tick, *io, world_draw, rt);
+  return MPCMMD_OK;
+}
+
+// one launch over the harness's arrays; rt: the routed instantiation
+static int world_step_device(const mpcmmd_world_model* m, int32_t device, int32_t n_episodes, int32_t tick,
+                             const mpcmmd_world_step_io* io, const mpcmmd_world_routed* rt) {
   if (n_episodes < 1 || n_episodes > 65535) return fail(MPCMMD_E_INVALID, "world: 1 <= n_episodes <= 65535");
   return guarded([&] {
     int count = 0;
@@ -436,7 +545,7 @@ extern "C" int mpcmmd_world_step_device(const mpcmmd_world_model* m, int32_t dev
     Scratch sc;
     WorldStepParams q{};
     q.w = world_scalars(*m);
-    q.tick = tick;
+    q.tick = tick, q.reset = rt && tick < 0 ? 1 : 0;
     q.s_plan = 11, q.s_steer = 4, q.s_init = 6, q.s_wp = int(P), q.s_obs = int(O) * 5;
     auto in = [&](const void* src, size_t bytes) { return sc.up(src, bytes); };
     q.route_x = static_cast<const double*>(in(m->route_x, n * 8));
@@ -475,13 +584,39 @@ extern "C" int mpcmmd_world_step_device(const mpcmmd_world_model* m, int32_t dev
     q.yw = static_cast<float*>(io_buf(io->y_wp, E * P * 4, false));
     q.obs = static_cast<float*>(io_buf(io->obstacles, E * O * 5 * 4, false));
     q.pop = static_cast<float*>(io_buf(io->pop, E * B * 8 * 4, false));
-    q.logd = static_cast<double*>(io_buf(io->log_d, E * MPCMMD_WORLD_LOG_D * 8, false));
-    q.logf = static_cast<float*>(io_buf(io->log_f, E * MPCMMD_WORLD_LOG_F * 4, false));
-    q.logi = static_cast<int32_t*>(io_buf(io->log_i, E * MPCMMD_WORLD_LOG_I * 4, false));
-    launch_world_step(q, n_episodes, nullptr);
+    // a reset-mode launch writes no log row: what the caller's arrays hold goes up and comes back
+    const bool keep = q.reset != 0;
+    q.logd = static_cast<double*>(io_buf(io->log_d, E * MPCMMD_WORLD_LOG_D * 8, keep));
+    q.logf = static_cast<float*>(io_buf(io->log_f, E * MPCMMD_WORLD_LOG_F * 4, keep));
+    q.logi = static_cast<int32_t*>(io_buf(io->log_i, E * MPCMMD_WORLD_LOG_I * 4, keep));
+    if (rt) {
+      WorldRoutedParams r{};
+      r.p = veh_scalars(*rt);
+      r.s = static_cast<double*>(io_buf(rt->veh_s, E * V * 8, true));
+      r.v = static_cast<float*>(io_buf(rt->veh_v, E * V * 4, true));
+      r.param = static_cast<const float*>(sc.up(V ? rt->veh_param : nullptr, V ? E * V * 2 * 4 : 16));
+      r.log = rt->veh_log ? static_cast<float*>(io_buf(rt->veh_log, E * V * 2 * 4, true)) : nullptr;
+      launch_world_step_routed(q, r, n_episodes, nullptr);
+    } else {
+      launch_world_step(q, n_episodes, nullptr);
+    }
     HIPC(hipGetLastError());
     HIPC(hipDeviceSynchronize());
     for (const Out& o : outs) HIPC(hipMemcpy(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost));
     return MPCMMD_OK;
   });
+}
+
+extern "C" int mpcmmd_world_step_device(const mpcmmd_world_model* m, int32_t device, int32_t n_episodes, int32_t tick,
+                                        const mpcmmd_world_step_io* io) {
+  if (int rc = check_world(m, io)) return rc;
+  return world_step_device(m, device, n_episodes, tick, io, nullptr);
+}
+
+extern "C" int mpcmmd_world_step_device_routed(const mpcmmd_world_model* m, int32_t device, int32_t n_episodes,
+                                               int32_t tick, const mpcmmd_world_step_io* io,
+                                               const mpcmmd_world_routed* rt) {
+  if (int rc = check_world(m, io)) return rc;
+  if (int rc = check_world_routed(m, rt)) return rc;
+  return world_step_device(m, device, n_episodes, tick, io, rt);
 }

@@ -57,24 +57,68 @@ int check_world(const mpcmmd_world_model* m, const mpcmmd_world_step_io* io) {
   return MPCMMD_OK;
 }
 
-void world_step_host(const mpcmmd_world_model& m, int tick, const mpcmmd_world_step_io& io, WorldDraw draw) {
+VehScalars veh_scalars(const mpcmmd_world_routed& r) {
+  return VehScalars{r.acc_max, r.brake, r.gap0, r.headway, r.length, r.lane_tol, r.gap_min, r.acc_min};
+}
+
+int check_world_routed(const mpcmmd_world_model* m, const mpcmmd_world_routed* rt) {
+  if (!m || !rt) return fail(MPCMMD_E_INVALID, "null argument");
+  if (m->total_obs > 0 && (!rt->veh_s || !rt->veh_v || !rt->veh_param))
+    return fail(MPCMMD_E_INVALID, "routed vehicles: null array");
+  if (!(rt->acc_max > 0.0f) || !(rt->brake > 0.0f) || !(rt->gap_min > 0.0f) || !(rt->acc_min < 0.0f) ||
+      !(rt->lane_tol >= 0.0f))
+    return fail(MPCMMD_E_INVALID,
+                "routed vehicles: acc_max > 0, brake > 0, gap_min > 0, acc_min < 0, lane_tol >= 0 must hold");
+  return MPCMMD_OK;
+}
+
+void world_step_host(const mpcmmd_world_model& m, int tick, const mpcmmd_world_step_io& io, WorldDraw draw,
+                     const mpcmmd_world_routed* rt) {
   const WorldScalars w = world_scalars(m);
+  const bool reset = rt && tick < 0;  // the chained route's reset-mode step: no plan, nothing moves, no log
   WorldEgo e{io.pos[0], io.pos[1], io.ego[0], io.ego[1], io.ego[2]};
-  WorldControl c = world_controller(w, m.pdot4, io.cx, io.cy, io.steer, e.v);
-  float u[4];
-  if (io.u) std::memcpy(u, io.u, sizeof u);
-  else draw(w.noise, io.key[0], m.seed, tick, c.a_c, c.s_c, u);
-  world_perturb(w, u, c);
-  const bool frozen = io.done_tick[0] >= 0;
+  WorldControl c{};
+  float u[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (!reset) {
+    c = world_controller(w, m.pdot4, io.cx, io.cy, io.steer, e.v);
+    if (io.u) std::memcpy(u, io.u, sizeof u);
+    else draw(w.noise, io.key[0], m.seed, tick, c.a_c, c.s_c, u);
+    world_perturb(w, u, c);
+  }
+  const bool frozen = reset || io.done_tick[0] >= 0;
   if (!frozen) {
     e = world_ego_step<HostMath>(e, c.a, c.s, w.dt);
-    for (int o = 0; o < w.total; ++o) {
-      float* v = io.vehicles + size_t(o) * 5;
-      v[0] = v[0] + v[2] * w.dt;
-      v[1] = v[1] + v[3] * w.dt;
-    }
+    if (!rt)
+      for (int o = 0; o < w.total; ++o) {
+        float* v = io.vehicles + size_t(o) * 5;
+        v[0] = v[0] + v[2] * w.dt;
+        v[1] = v[1] + v[3] * w.dt;
+      }
     io.pos[0] = e.x, io.pos[1] = e.y;
     io.ego[0] = e.v, io.ego[1] = e.psi, io.ego[2] = e.psidot;
+  }
+  // the ego on the route
+  uint64_t best = ~uint64_t(0);
+  int idx = 0;
+  for (int j = 0; j < w.n_route; ++j) {
+    const uint64_t k = route_key(e.x, e.y, m.route_x[j], m.route_y[j]);
+    if (k < best) best = k, idx = j;
+  }
+  const double s0 = m.route_arc[idx];
+  const float d = world_lateral(w, m.route_x, m.route_y, m.route_arc, m.spline_x, m.spline_y, idx, e);
+  if (rt) {  // the routed vehicles: every leader from the states before the step, then the rows
+    const VehScalars p = veh_scalars(*rt);
+    VehLeader lead[kWorldMaxObs];
+    if (!frozen)
+      for (int o = 0; o < w.total; ++o)
+        lead[o] = vehicle_leader(p, o, w.total, rt->veh_s, rt->veh_param, 2, rt->veh_v, s0, d, e.v);
+    for (int o = 0; o < w.total; ++o) {
+      float a = 0.0f;
+      if (!frozen) vehicle_advance(p, w.dt, rt->veh_param[o * 2 + 1], lead[o], rt->veh_s + o, rt->veh_v + o, &a);
+      if (rt->veh_log && !reset) rt->veh_log[o * 2] = rt->veh_v[o], rt->veh_log[o * 2 + 1] = a;
+      vehicle_pose<HostMath>(m.route_arc, m.spline_x, m.spline_y, w.n_route, rt->veh_s[o], rt->veh_param[o * 2],
+                             rt->veh_v[o], io.vehicles + size_t(o) * 5);
+    }
   }
   // flags
   float clear = -std::numeric_limits<float>::infinity();
@@ -85,23 +129,17 @@ void world_step_host(const mpcmmd_world_model& m, int tick, const mpcmmd_world_s
     clear = fmaxf(clear, t);  // a NaN term is ignored here and reported below
   }
   if (clear_nan) clear = canon_nan(NAN);
-  uint64_t best = ~uint64_t(0);
-  int idx = 0;
-  for (int j = 0; j < w.n_route; ++j) {
-    const uint64_t k = route_key(e.x, e.y, m.route_x[j], m.route_y[j]);
-    if (k < best) best = k, idx = j;
-  }
-  const double s0 = m.route_arc[idx];
-  const float d = world_lateral(w, m.route_x, m.route_y, m.route_arc, m.spline_x, m.spline_y, idx, e);
   const bool lane_out = d < w.y_lb || d > w.y_ub;
   const bool collided = !(clear <= 0.0f);
   const bool goal = world_goal(w, m.route_x, m.route_y, e);
   if (!frozen && (collided || goal)) io.done_tick[0] = tick;
-  io.log_d[0] = e.x, io.log_d[1] = e.y, io.log_d[2] = s0;
-  const float lf[MPCMMD_WORLD_LOG_F] = {e.v, e.psi, e.psidot, c.a_c, c.s_c, c.a, c.s, u[0], u[1], u[2],
-                                        u[3], clear, d};
-  std::memcpy(io.log_f, lf, sizeof lf);
-  io.log_i[0] = idx, io.log_i[1] = lane_out, io.log_i[2] = collided, io.log_i[3] = goal;
+  if (!reset) {
+    io.log_d[0] = e.x, io.log_d[1] = e.y, io.log_d[2] = s0;
+    const float lf[MPCMMD_WORLD_LOG_F] = {e.v, e.psi, e.psidot, c.a_c, c.s_c, c.a, c.s, u[0], u[1], u[2],
+                                          u[3], clear, d};
+    std::memcpy(io.log_f, lf, sizeof lf);
+    io.log_i[0] = idx, io.log_i[1] = lane_out, io.log_i[2] = collided, io.log_i[3] = goal;
+  }
   // the next tick's raw inputs
   const float init[6] = {0.0f, 0.0f, e.v, 0.0f, e.psi, e.psidot};
   std::memcpy(io.init_state, init, sizeof init);

@@ -40,6 +40,8 @@ SYMBOLS = (
     "mpcmmd_mpc_validate", "mpcmmd_mpc_validation_log", "mpcmmd_mpc_validation_inputs",
     "mpcmmd_mpc_vehicle_constant", "mpcmmd_mpc_step_host_planned", "mpcmmd_mpc_step_device_planned",
     "mpcmmd_mpc_plan_vehicles", "mpcmmd_mpc_vehicle_log",
+    "mpcmmd_world_step_host_routed", "mpcmmd_world_step_device_routed", "mpcmmd_world_route_vehicles",
+    "mpcmmd_world_vehicle_log",
 )
 
 
@@ -146,6 +148,17 @@ class WorldStepIO(C.Structure):
                 [(k, C.POINTER(C.c_float)) for k in ("init_state", "x_wp", "y_wp", "obstacles", "pop")] +
                 [("log_d", C.POINTER(C.c_double)), ("log_f", C.POINTER(C.c_float)), ("log_i", C.POINTER(C.c_int32)),
                  ("key", C.POINTER(C.c_uint32))])
+
+
+ROUTED_SCALARS = ("acc_max", "brake", "gap0", "headway", "length", "lane_tol", "gap_min", "acc_min")
+ROUTED_DEFAULTS = dict(acc_max=1.5, brake=2.0, gap0=5.0, headway=1.0, length=4.5, lane_tol=1.75, gap_min=0.5,
+                       acc_min=-8.0)
+
+
+class WorldRouted(C.Structure):
+    _fields_ = ([("veh_s", C.POINTER(C.c_double)), ("veh_v", C.POINTER(C.c_float)),
+                 ("veh_param", C.POINTER(C.c_float)), ("veh_log", C.POINTER(C.c_float))] +
+                [(k, C.c_float) for k in ROUTED_SCALARS])
 
 
 class WorldValidation(C.Structure):
@@ -276,6 +289,14 @@ def lib():
         L.mpcmmd_world_reset.argtypes = [vp, C.c_int32, dp, fp, fp, fp, fp, fp, ip]
         L.mpcmmd_world_run.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp, fp, C.c_float]
         L.mpcmmd_world_log.argtypes = [vp, C.c_int32, dp, fp, ip, fp, ip]
+    if hasattr(L, "mpcmmd_world_route_vehicles"):   # an older library lacks the routed vehicles: the callers raise
+        dp = C.POINTER(C.c_double)
+        L.mpcmmd_world_step_host_routed.argtypes = [C.POINTER(WorldModelStruct), C.c_int32, C.POINTER(WorldStepIO),
+                                                    C.POINTER(WorldRouted)]
+        L.mpcmmd_world_step_device_routed.argtypes = [C.POINTER(WorldModelStruct), C.c_int32, C.c_int32, C.c_int32,
+                                                      C.POINTER(WorldStepIO), C.POINTER(WorldRouted)]
+        L.mpcmmd_world_route_vehicles.argtypes = [vp, C.c_int32, dp, fp, fp, fp]
+        L.mpcmmd_world_vehicle_log.argtypes = [vp, C.c_int32, dp, fp]
     if hasattr(L, "mpcmmd_world_validate"):   # an older library lacks the stage: World.validate raises
         L.mpcmmd_world_validate.argtypes = [vp, C.POINTER(WorldValidation)]
         L.mpcmmd_world_validation_log.argtypes = [vp, C.c_int32, ip, ip, fp, fp, fp]
@@ -659,7 +680,22 @@ class WorldModel:
                                   int(seed) & 0xFFFFFFFF)
 
 
-def world_step(model, tick, cx, cy, steer, u, mean, pos, ego, vehicles, done_tick, device=None, keys=None):
+def _need_routed(L):
+    if not hasattr(L, "mpcmmd_world_route_vehicles"):
+        raise NativeError(f"{LIB_PATH} has no mpcmmd_world_route_vehicles (built before the routed vehicles existed): "
+                          "rebuild it")
+
+
+def routed_scalars(over):
+    """The eight scalars of the routed vehicles in ROUTED_SCALARS' order, ROUTED_DEFAULTS overridden by ``over``."""
+    extra = set(over) - set(ROUTED_SCALARS)
+    if extra:
+        raise ValueError(f"routed vehicles: unknown scalars {sorted(extra)}")
+    return np.array([over.get(k, ROUTED_DEFAULTS[k]) for k in ROUTED_SCALARS], np.float32)
+
+
+def world_step(model, tick, cx, cy, steer, u, mean, pos, ego, vehicles, done_tick, device=None, keys=None,
+               routed=None):
     """One step of E episodes of the surrogate world: mpcmmd_world_step_host per
     episode (device None), or one k_world_step launch on GPU ``device``
     (mpcmmd_world_step_device).  cx, cy [E, 11], steer [E, >= 4] (the plan's
@@ -669,8 +705,16 @@ def world_step(model, tick, cx, cy, steer, u, mean, pos, ego, vehicles, done_tic
     modified.  Returns a dict: the new state under the same names, the next
     tick's init_state [E, 6], x_wp, y_wp [E, P], obstacles [E, O, 5], pop
     [E, B, 8] and the log row log_d [E, 3], log_f [E, 13], log_i [E, 4]
-    (WORLD_LOG_D / _F / _I name the columns)."""
+    (WORLD_LOG_D / _F / _I name the columns).
+
+    routed = dict(s=[E, total_obs] float64, v=[E, total_obs], param=[E, total_obs, 2] = d, v0, plus any
+    of ROUTED_SCALARS) steps the vehicles by the routed policy (DESIGN.md section 24,
+    mpcmmd_world_step_host_routed / _device_routed): ``vehicles`` is then not read (None will do) and
+    comes back as the rows the step made; the dict gains veh_s, veh_v (the new states) and veh_log
+    [E, total_obs, 2] = v, a.  tick < 0 is then the reset-mode step (no plan read, no log row)."""
     L = lib()
+    if routed is not None:
+        _need_routed(L)
     if not hasattr(L, "mpcmmd_world_step_host"):
         raise NativeError(f"{LIB_PATH} has no mpcmmd_world_step_host (built before the entry point existed): rebuild it")
     E = np.asarray(pos).reshape(-1, 2).shape[0]
@@ -683,7 +727,8 @@ def world_step(model, tick, cx, cy, steer, u, mean, pos, ego, vehicles, done_tic
              key=np.zeros(0, np.uint32) if keys is None else
              np.array(np.asarray(keys, np.int64).reshape(E) & 0xFFFFFFFF, np.uint32),
              mean=f(mean, 8), pos=np.array(np.asarray(pos, np.float64).reshape(E, 2), order="C"), ego=f(ego, 3),
-             vehicles=f(vehicles, m.total_obs, 5),
+             vehicles=np.zeros((E, m.total_obs, 5), np.float32) if routed is not None and vehicles is None
+             else f(vehicles, m.total_obs, 5),
              done_tick=np.array(np.asarray(done_tick).reshape(E), np.int32, order="C"),
              init_state=np.empty((E, 6), np.float32), x_wp=np.empty((E, m.num_path), np.float32),
              y_wp=np.empty((E, m.num_path), np.float32), obstacles=np.empty((E, m.num_obs, 5), np.float32),
@@ -698,7 +743,27 @@ def world_step(model, tick, cx, cy, steer, u, mean, pos, ego, vehicles, done_tic
             ptr.append(C.cast(row.ctypes.data, dict(WorldStepIO._fields_)[k]) if row.size else None)
         return WorldStepIO(*ptr)
 
-    if device is None:
+    if routed is not None:
+        if int(tick) < 0:   # the reset-mode step writes no log row
+            a["log_d"][:], a["log_f"][:], a["log_i"][:] = 0.0, 0.0, 0
+        V = m.total_obs
+        sc = routed_scalars({k: v for k, v in routed.items() if k not in ("s", "v", "param")})
+        a["veh_s"] = np.array(np.asarray(routed["s"], np.float64).reshape(E, V), order="C")
+        a["veh_v"], par = f(routed["v"], V), f(routed["param"], V, 2)
+        a["veh_log"] = np.zeros((E, V, 2), np.float32)
+
+        def rt_of(e):
+            ptr = [C.cast(x[e:].ctypes.data, t) if x[e:].size else None
+                   for x, (_, t) in zip((a["veh_s"], a["veh_v"], par, a["veh_log"]), WorldRouted._fields_)]
+            return WorldRouted(*ptr, *[float(x) for x in sc])
+
+        if device is None:
+            for e in range(E):
+                check(L.mpcmmd_world_step_host_routed(C.byref(m.c), int(tick), C.byref(io_of(e)), C.byref(rt_of(e))))
+        else:
+            check(L.mpcmmd_world_step_device_routed(C.byref(m.c), int(device), E, int(tick), C.byref(io_of(0)),
+                                                    C.byref(rt_of(0))))
+    elif device is None:
         for e in range(E):
             check(L.mpcmmd_world_step_host(C.byref(m.c), int(tick), C.byref(io_of(e))))
     else:
@@ -706,6 +771,13 @@ def world_step(model, tick, cx, cy, steer, u, mean, pos, ego, vehicles, done_tic
     for k in ("cx", "cy", "steer", "u", "mean", "key"):
         del a[k]
     return a
+
+
+def pad_ptr(a, ctype):
+    """The address of ``a``'s data, or of a dummy word when it is empty (a NULL would be an argument error)."""
+    if a.size:
+        return a.ctypes.data_as(C.POINTER(ctype))
+    return C.cast(C.pointer(C.c_double(0.0)), C.POINTER(ctype))
 
 
 class World:
@@ -747,7 +819,8 @@ class World:
         pos = np.ascontiguousarray(np.asarray(pos, np.float64).reshape(-1, 2))
         E = self.E = pos.shape[0]
         f = lambda a, *sh: np.ascontiguousarray(np.asarray(a, np.float32).reshape(*sh))
-        veh = f(vehicles, E, self.model.total_obs, 5)
+        veh = (np.zeros((E, 0, 5), np.float32) if vehicles is None and getattr(self, "_routed", False)
+               else f(vehicles, E, self.model.total_obs, 5))
         kk = np.ascontiguousarray(np.asarray(keys, np.int64).reshape(E).astype(np.int32))
         check(self._L.mpcmmd_world_reset(self._w, E, pos.ctypes.data_as(C.POINTER(C.c_double)), _fptr(f(ego, E, 3)),
                                          _fptr(veh) if veh.size else None, _fptr(f(mean, E, 8)), _fptr(f(cov, 64)),
@@ -771,6 +844,36 @@ class World:
                                        li.ctypes.data_as(ip), _fptr(pl), dn.ctypes.data_as(ip)))
         return dict(log_d=ld, log_f=lf, log_i=li, cx=pl[..., :11].copy(), cy=pl[..., 11:22].copy(),
                     steering=pl[..., 22:26].copy(), mean_param=pl[..., 26:].copy(), done_tick=dn)
+
+    def route_vehicles(self, s, v=None, param=None, **scalars):
+        """mpcmmd_world_route_vehicles: from the next ``reset`` on (which must be given as many episodes, and
+        whose ``vehicles`` may be None), the vehicles follow the route.  s [E, total_obs]
+        float64 arc lengths, v [E, total_obs] speeds, param [E, total_obs, 2] = d, v0 per vehicle; the
+        scalars are ROUTED_SCALARS (defaults ROUTED_DEFAULTS).  ``s`` None turns the policy off."""
+        _need_routed(self._L)
+        if s is None:
+            check(self._L.mpcmmd_world_route_vehicles(self._w, 0, None, None, None, None))
+            self._routed = False
+            return
+        V = self.model.total_obs
+        ss = np.ascontiguousarray(np.asarray(s, np.float64).reshape(-1, V))
+        E = ss.shape[0] if V else int(np.asarray(param).shape[0])
+        f = lambda a, *sh: np.ascontiguousarray(np.asarray(a, np.float32).reshape(*sh))
+        vv, pp, sc = f(v, E, V), f(param, E, V, 2), routed_scalars(scalars)
+        # a world without vehicles still hands over addresses: NULL arrays would turn the policy off
+        pad = lambda x, dt: x if x.size else np.zeros(2, dt)
+        check(self._L.mpcmmd_world_route_vehicles(self._w, E, pad(ss, np.float64).ctypes.data_as(C.POINTER(C.c_double)),
+                                                  _fptr(pad(vv, np.float32)), _fptr(pad(pp, np.float32)), _fptr(sc)))
+        self._routed = True
+
+    def vehicle_log(self, ticks):
+        """veh [ticks, E, total_obs, 3] float64: every routed vehicle's s, v and the acceleration applied,
+        after each tick's step (v and a are the step's fp32 values, held exactly)."""
+        _need_routed(self._L)
+        T, E, V = int(ticks), self.E, self.model.total_obs
+        vs, va = np.zeros((max(T, 0), E, V), np.float64), np.zeros((max(T, 0), E, V, 2), np.float32)
+        check(self._L.mpcmmd_world_vehicle_log(self._w, T, pad_ptr(vs, C.c_double), pad_ptr(va, C.c_float)))
+        return np.concatenate([vs[..., None], va.astype(np.float64)], -1)
 
     def validate(self, rollouts, alpha=0.98, sigma=()):
         """mpcmmd_world_validate: from the next ``reset`` on, every tick of ``run`` also computes the
