@@ -260,6 +260,13 @@ DEVI void block_store(const d4* Yv, float* plane, int p0, int M, int ys, int s0,
 // holds samples 88 + 2h + t % 2 >= kNew but for (t = 4, h = 0) -- that store
 // takes v43, out of range (dropped by the buffer unit) for h > 0, and tile
 // 5's register 3 is not stored.
+// The stores are non-temporal (kStoreNt, the buffer instructions' nt bit): a
+// launch streams 89 rows x M + 1 floats per candidate (177 MB at B = 1024,
+// n = 22) that nothing reads before k_bselect, so their lines are marked for
+// early eviction and do not displace what the sampler itself and the other
+// candidate group's kernels, which run beside it, keep in L2.  A cache policy
+// only: the bytes written are the same.
+constexpr int kStoreNt = 2;
 DEVI __amdgpu_buffer_rsrc_t ygen_rsrc(float* plane, int ys) {
   return __builtin_amdgcn_make_buffer_rsrc(plane, short(0), kBzCols * ys * 4, 0x00020000);
 }
@@ -272,7 +279,7 @@ DEVI void block_store_rows(const d4* Yv, __amdgpu_buffer_rsrc_t yr, int p0, int 
     for (int i = 0; i < 4; ++i) {
       if (t == 5 && i == 3) continue;
       const int soff = ((32 * (t >> 1) + (t & 1) + 8 * i) * ys + p0) * 4;
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(float(Yv[t][i])), yr, t == 4 && i == 3 ? v43 : vl, soff, 0);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(float(Yv[t][i])), yr, t == 4 && i == 3 ? v43 : vl, soff, kStoreNt);
     }
 }
 
