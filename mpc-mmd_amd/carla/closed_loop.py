@@ -74,14 +74,22 @@ LENGTH, LANE_TOL = 4.5, 1.75
 VAL_KEYS = ("val_counts", "val_count_pos", "val_var", "val_cvar", "val_mean", "val_max", "val_mmd", "val_est")
 
 
-def _replay():
-    name = "mpcmmd_carla_replay"
+def _load(name, *path):
+    """The module at ``path``, loaded by file path once (this directory's ``optimizer`` hides the other one)."""
     if name not in sys.modules:
-        spec = importlib.util.spec_from_file_location(name, os.path.join(_HERE, "replay.py"))
+        spec = importlib.util.spec_from_file_location(name, os.path.join(*path))
         mod = importlib.util.module_from_spec(spec)
         sys.modules[name] = mod
         spec.loader.exec_module(mod)
     return sys.modules[name]
+
+
+def _replay():
+    return _load("mpcmmd_carla_replay", _HERE, "replay.py")
+
+
+# (mean, sample sd) of a vector: one definition for both drivers, in a module without relative imports
+_mean_std = _load("mpcmmd_episode_stats", os.path.dirname(_HERE), "optimizer", "episode_stats.py").mean_std
 
 
 def synthetic_world(town="Town05"):
@@ -156,11 +164,6 @@ def summarise_vehicles(res, routed):
 
 def _run(prob, cost, route, goal_index, vehicles, starts, ticks, **kw):
     return prob.run_episodes(cost, route, vehicles, starts, ticks, goal_index=goal_index, **kw)
-
-
-def _mean_std(v):
-    v = np.asarray(v, np.float64)
-    return float(v.mean()) if v.size else 0.0, float(v.std(ddof=1)) if v.size > 1 else 0.0
 
 
 def summarise(res):

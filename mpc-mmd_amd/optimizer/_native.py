@@ -780,31 +780,33 @@ def pad_ptr(a, ctype):
     return C.cast(C.pointer(C.c_double(0.0)), C.POINTER(ctype))
 
 
-class World:
-    """Owns one mpcmmd_world: the chained closed loop of ``tick``'s handle on the
-    surrogate world ``model`` (its num_path and num_obs must be the tick
-    context's) for up to ``max_ticks`` ticks.  ``reset`` takes the episodes'
-    start states, ``run(cost, tick_begin, count)`` enqueues begin, CEM and world
-    step per tick with nothing crossing the host, ``log(ticks)`` performs the
-    one readback.  Close it before its tick context."""
+class _Episodes:
+    """What World and Mpc share: they own one episode context of the library (mpcmmd_<_NAME>_*),
+    registered with the object that must outlive it, and coerce the arrays of reset, run, log and
+    the validation stage.  ``_U`` and ``_LOG`` are the row widths of u and of log_d, log_f, log_i
+    and the plan, ``_COUNTS`` the count columns of the validation log, ``_VALIDATION`` its struct."""
 
-    def __init__(self, tick, model, max_ticks):
+    def _open(self, owner_ptr, siblings, handle, model, max_ticks):
         self._L = lib()
-        if not hasattr(self._L, "mpcmmd_world_create"):
-            raise NativeError(f"{LIB_PATH} has no mpcmmd_world_create (built before the entry point existed): rebuild it")
-        self.tick, self.model, self.max_ticks = tick, model, int(max_ticks)
-        w = C.c_void_p()
-        check(self._L.mpcmmd_world_create(tick._t, C.byref(model.c), self.max_ticks, C.byref(w)))
-        self._w = w
+        if not hasattr(self._L, f"mpcmmd_{self._NAME}_create"):
+            raise NativeError(f"{LIB_PATH} has no mpcmmd_{self._NAME}_create (built before the entry point existed): "
+                              "rebuild it")
+        self.model, self.max_ticks, self._handle, self._siblings = model, int(max_ticks), handle, siblings
+        p = C.c_void_p()
+        check(self._fn("create")(owner_ptr, C.byref(model.c), self.max_ticks, C.byref(p)))
+        self._p = p
         self.E = 0
-        tick._worlds.append(self)   # Tick.close frees its world contexts first
+        siblings.append(self)   # the owner's close frees its contexts first
+
+    def _fn(self, name):
+        return getattr(self._L, f"mpcmmd_{self._NAME}_{name}")
 
     def close(self):
-        if getattr(self, "_w", None):
-            self._L.mpcmmd_world_destroy(self._w)
-            self._w = None
-            if self in self.tick._worlds:
-                self.tick._worlds.remove(self)
+        if getattr(self, "_p", None):
+            self._fn("destroy")(self._p)
+            self._p = None
+            if self in self._siblings:
+                self._siblings.remove(self)
 
     def __del__(self):
         try:
@@ -812,36 +814,91 @@ class World:
         except Exception:
             pass
 
+    def _reset(self, pos, state, vehicles, veh_shape, mean, cov, u, keys):
+        pos = np.ascontiguousarray(np.asarray(pos, np.float64).reshape(-1, 2))
+        E = self.E = pos.shape[0]
+        f = lambda a, *sh: np.ascontiguousarray(np.asarray(a, np.float32).reshape(*sh))
+        veh = f(vehicles, E, *veh_shape)
+        kk = np.ascontiguousarray(np.asarray(keys, np.int64).reshape(E).astype(np.int32))
+        check(self._fn("reset")(self._p, E, pos.ctypes.data_as(C.POINTER(C.c_double)), _fptr(f(state, E, 3)),
+                                _fptr(veh) if veh.size else None, _fptr(f(mean, E, 8)), _fptr(f(cov, 64)),
+                                None if u is None else _fptr(f(u, self.max_ticks, E, self._U)),
+                                kk.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._handle._G = E
+
+    def _run(self, cost, tick_begin, count, cov, v_des, *more):
+        f = lambda a, *sh: np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32), sh))
+        check(self._fn("run")(self._p, COST[cost], int(tick_begin), int(count),
+                              _fptr(np.ascontiguousarray(np.asarray(cov, np.float32).reshape(64))),
+                              _fptr(f(np.asarray(v_des, np.float32).reshape(-1), self.E)), *more))
+
+    def _log(self, ticks):
+        """log_d, log_f, log_i, the plan rows and done_tick of the first ``ticks`` rows."""
+        T, E, (wd, wf, wi, wp) = int(ticks), self.E, self._LOG
+        ld, lf = np.empty((T, E, wd), np.float64), np.empty((T, E, wf), np.float32)
+        li, pl, dn = np.empty((T, E, wi), np.int32), np.empty((T, E, wp), np.float32), np.empty(E, np.int32)
+        ip = C.POINTER(C.c_int32)
+        check(self._fn("log")(self._p, T, ld.ctypes.data_as(C.POINTER(C.c_double)), _fptr(lf), li.ctypes.data_as(ip),
+                              _fptr(pl), dn.ctypes.data_as(ip)))
+        return ld, lf, li, pl, dn
+
+    def _validate(self, rollouts, alpha, sigma, **fields):
+        if not hasattr(self._L, f"mpcmmd_{self._NAME}_validate"):
+            raise NativeError(f"{LIB_PATH} has no mpcmmd_{self._NAME}_validate (built before the entry point existed): "
+                              "rebuild it")
+        self._val_S = 0
+        if rollouts is None:
+            check(self._fn("validate")(self._p, None))
+            return
+        sg = np.asarray(() if sigma is None else sigma, np.float32).reshape(-1)
+        cfg = self._VALIDATION(int(rollouts), float(alpha), int(sg.size))
+        for i, v in enumerate(sg[:8]):   # more than 8: num_sigma says so and the library refuses
+            cfg.sigma[i] = float(v)
+        for k, v in fields.items():
+            setattr(cfg, k, v)
+        check(self._fn("validate")(self._p, C.byref(cfg)))
+        self._val_S = int(sg.size)
+
+    def _validation_log(self, ticks):
+        """val_counts, val_count_pos, the statistics [T, E, 4, 3], val_mmd and val_est of the first ``ticks`` rows."""
+        T, E, S = int(ticks), self.E, getattr(self, "_val_S", 0)
+        n = max(T, 0)
+        cn, cp = np.zeros((n, E, self._COUNTS), np.int32), np.zeros((n, E, 3), np.int32)
+        st, mm = np.zeros((n, E, 4, 3), np.float32), np.zeros((n, E, 3, S), np.float32)
+        es = np.zeros((n, E, 2), np.float32)
+        ip = C.POINTER(C.c_int32)
+        check(self._fn("validation_log")(self._p, T, cn.ctypes.data_as(ip), cp.ctypes.data_as(ip), _fptr(st),
+                                         _fptr(mm) if S else None, _fptr(es)))
+        return dict(val_counts=cn, val_count_pos=cp, val_mmd=mm, val_est=es), st
+
+
+class World(_Episodes):
+    """Owns one mpcmmd_world: the chained closed loop of ``tick``'s handle on the
+    surrogate world ``model`` (its num_path and num_obs must be the tick
+    context's) for up to ``max_ticks`` ticks.  ``reset`` takes the episodes'
+    start states, ``run(cost, tick_begin, count)`` enqueues begin, CEM and world
+    step per tick with nothing crossing the host, ``log(ticks)`` performs the
+    one readback.  Close it before its tick context."""
+    _NAME, _U, _LOG, _COUNTS, _VALIDATION = "world", 4, (3, 13, 4, 34), 3, WorldValidation
+    _w = property(lambda self: self._p)   # the raw context, for tests that call the C entry points themselves
+
+    def __init__(self, tick, model, max_ticks):
+        self.tick = tick
+        self._open(tick._t, tick._worlds, tick.handle, model, max_ticks)   # Tick.close frees its worlds first
+
     def reset(self, pos, ego, vehicles, mean, cov, u, keys):
         """pos [E, 2] float64, ego [E, 3] = v, psi, psidot, vehicles [E, total_obs, 5], mean [E, 8],
         cov [8, 8], keys [E] (episode e solves tick k with idx_mpc = k + keys[e]), u [max_ticks, E, 4]
         or None: the kernel draws each tick's variates from (keys[e], the handle's seed, tick)."""
-        pos = np.ascontiguousarray(np.asarray(pos, np.float64).reshape(-1, 2))
-        E = self.E = pos.shape[0]
-        f = lambda a, *sh: np.ascontiguousarray(np.asarray(a, np.float32).reshape(*sh))
-        veh = (np.zeros((E, 0, 5), np.float32) if vehicles is None and getattr(self, "_routed", False)
-               else f(vehicles, E, self.model.total_obs, 5))
-        kk = np.ascontiguousarray(np.asarray(keys, np.int64).reshape(E).astype(np.int32))
-        check(self._L.mpcmmd_world_reset(self._w, E, pos.ctypes.data_as(C.POINTER(C.c_double)), _fptr(f(ego, E, 3)),
-                                         _fptr(veh) if veh.size else None, _fptr(f(mean, E, 8)), _fptr(f(cov, 64)),
-                                         None if u is None else _fptr(f(u, self.max_ticks, E, 4)),
-                                         kk.ctypes.data_as(C.POINTER(C.c_int32))))
-        self.tick.handle._G = E
+        none = vehicles is None and getattr(self, "_routed", False)
+        self._reset(pos, ego, () if none else vehicles, (0 if none else self.model.total_obs, 5), mean, cov, u, keys)
 
     def run(self, cost, tick_begin, count, cov, v_des, threshold=0.1):
-        f = lambda a, *sh: np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32), sh))
-        check(self._L.mpcmmd_world_run(self._w, COST[cost], int(tick_begin), int(count),
-                                       _fptr(np.ascontiguousarray(np.asarray(cov, np.float32).reshape(64))),
-                                       _fptr(f(np.asarray(v_des, np.float32).reshape(-1), self.E)), float(threshold)))
+        self._run(cost, tick_begin, count, cov, v_des, float(threshold))
 
     def log(self, ticks):
         """The first ``ticks`` rows: dict of log_d, log_f, log_i, cx, cy, steering, mean_param, done_tick."""
-        T, E = int(ticks), self.E
-        ld, lf = np.empty((T, E, 3), np.float64), np.empty((T, E, 13), np.float32)
-        li, pl, dn = np.empty((T, E, 4), np.int32), np.empty((T, E, 34), np.float32), np.empty(E, np.int32)
-        ip = C.POINTER(C.c_int32)
-        check(self._L.mpcmmd_world_log(self._w, T, ld.ctypes.data_as(C.POINTER(C.c_double)), _fptr(lf),
-                                       li.ctypes.data_as(ip), _fptr(pl), dn.ctypes.data_as(ip)))
+        ld, lf, li, pl, dn = self._log(ticks)
         return dict(log_d=ld, log_f=lf, log_i=li, cx=pl[..., :11].copy(), cy=pl[..., 11:22].copy(),
                     steering=pl[..., 22:26].copy(), mean_param=pl[..., 26:].copy(), done_tick=dn)
 
@@ -852,7 +909,7 @@ class World:
         scalars are ROUTED_SCALARS (defaults ROUTED_DEFAULTS).  ``s`` None turns the policy off."""
         _need_routed(self._L)
         if s is None:
-            check(self._L.mpcmmd_world_route_vehicles(self._w, 0, None, None, None, None))
+            check(self._L.mpcmmd_world_route_vehicles(self._p, 0, None, None, None, None))
             self._routed = False
             return
         V = self.model.total_obs
@@ -862,7 +919,7 @@ class World:
         vv, pp, sc = f(v, E, V), f(param, E, V, 2), routed_scalars(scalars)
         # a world without vehicles still hands over addresses: NULL arrays would turn the policy off
         pad = lambda x, dt: x if x.size else np.zeros(2, dt)
-        check(self._L.mpcmmd_world_route_vehicles(self._w, E, pad(ss, np.float64).ctypes.data_as(C.POINTER(C.c_double)),
+        check(self._L.mpcmmd_world_route_vehicles(self._p, E, pad(ss, np.float64).ctypes.data_as(C.POINTER(C.c_double)),
                                                   _fptr(pad(vv, np.float32)), _fptr(pad(pp, np.float32)), _fptr(sc)))
         self._routed = True
 
@@ -872,7 +929,7 @@ class World:
         _need_routed(self._L)
         T, E, V = int(ticks), self.E, self.model.total_obs
         vs, va = np.zeros((max(T, 0), E, V), np.float64), np.zeros((max(T, 0), E, V, 2), np.float32)
-        check(self._L.mpcmmd_world_vehicle_log(self._w, T, pad_ptr(vs, C.c_double), pad_ptr(va, C.c_float)))
+        check(self._L.mpcmmd_world_vehicle_log(self._p, T, pad_ptr(vs, C.c_double), pad_ptr(va, C.c_float)))
         return np.concatenate([vs[..., None], va.astype(np.float64)], -1)
 
     def validate(self, rollouts, alpha=0.98, sigma=()):
@@ -880,35 +937,16 @@ class World:
         Monte-Carlo risk of the plan it made (``validate_carla_risk`` of that tick with ``rollouts``
         fresh noise rows, quantile level ``alpha`` and the MMD bandwidths ``sigma``, at most 8) into
         the validation log.  ``rollouts`` None turns the stage off."""
-        if not hasattr(self._L, "mpcmmd_world_validate"):
-            raise NativeError(f"{LIB_PATH} has no mpcmmd_world_validate (built before the entry point existed): "
-                              "rebuild it")
-        self._val_S = 0
-        if rollouts is None:
-            check(self._L.mpcmmd_world_validate(self._w, None))
-            return
-        sg = np.asarray(() if sigma is None else sigma, np.float32).reshape(-1)
-        cfg = WorldValidation(int(rollouts), float(alpha), int(sg.size))
-        for i, v in enumerate(sg[:8]):   # more than 8: num_sigma says so and the library refuses
-            cfg.sigma[i] = float(v)
-        check(self._L.mpcmmd_world_validate(self._w, C.byref(cfg)))
-        self._val_S = int(sg.size)
+        self._validate(rollouts, alpha, sigma)
 
     def validation_log(self, ticks):
         """The first ``ticks`` rows of the validation log: val_counts [T, E, 3] (count, count_lane,
         count_rows of ``validate_carla``), val_count_pos [T, E, 3], val_var, val_cvar, val_mean,
         val_max [T, E, 3] (channels RISK_CHANNELS), val_mmd [T, E, 3, S] and val_est [T, E, 2]
         (the cost_lane and cost_obs the solve itself estimated)."""
-        T, E, S = int(ticks), self.E, getattr(self, "_val_S", 0)
-        n = max(T, 0)
-        cn, cp = np.zeros((n, E, 3), np.int32), np.zeros((n, E, 3), np.int32)
-        st, mm = np.zeros((n, E, 4, 3), np.float32), np.zeros((n, E, 3, S), np.float32)
-        es = np.zeros((n, E, 2), np.float32)
-        ip = C.POINTER(C.c_int32)
-        check(self._L.mpcmmd_world_validation_log(self._w, T, cn.ctypes.data_as(ip), cp.ctypes.data_as(ip), _fptr(st),
-                                                  _fptr(mm) if S else None, _fptr(es)))
-        return dict(val_counts=cn, val_count_pos=cp, val_var=st[:, :, 0].copy(), val_cvar=st[:, :, 1].copy(),
-                    val_mean=st[:, :, 2].copy(), val_max=st[:, :, 3].copy(), val_mmd=mm, val_est=es)
+        out, st = self._validation_log(ticks)
+        return dict(out, val_var=st[:, :, 0].copy(), val_cvar=st[:, :, 1].copy(), val_mean=st[:, :, 2].copy(),
+                    val_max=st[:, :, 3].copy())
 
     def validation_inputs(self):
         """The packed inputs of the last validated tick, as the validators read them: acc, steer [E, H],
@@ -920,7 +958,7 @@ class World:
                    x_obs=np.zeros((E, O, 100), np.float32), y_obs=np.zeros((E, O, 100), np.float32),
                    keys=np.zeros(E, np.uint32))
         check(self._L.mpcmmd_world_validation_inputs(
-            self._w, *[_fptr(out[k]) for k in ("acc", "steer", "st0", "path", "x_obs", "y_obs")],
+            self._p, *[_fptr(out[k]) for k in ("acc", "steer", "st0", "path", "x_obs", "y_obs")],
             out["keys"].ctypes.data_as(C.POINTER(C.c_uint32))))
         return out
 
@@ -1068,66 +1106,31 @@ def mpc_step(model, tick, cx, cy, u, mean, pos, vel, vehicles, done_tick, device
     return a
 
 
-class Mpc:
+class Mpc(_Episodes):
     """Owns one mpcmmd_mpc: the chained closed loop of a static / dynamic
     ``handle`` on ``model`` for up to ``max_ticks`` ticks.  ``reset`` takes the
     episodes' start states, ``run(cost, tick_begin, count)`` enqueues begin, CEM
     and k_mpc_step per tick with nothing crossing the host, ``log(ticks)``
     performs the one readback.  Close it before its handle."""
+    _NAME, _U, _LOG, _COUNTS, _VALIDATION = "mpc", 3, (2, 12, 4, 30), 2, MpcValidation
+    _c = property(lambda self: self._p)   # the raw context, for tests that call the C entry points themselves
 
     def __init__(self, handle, model, max_ticks):
-        self._L = lib()
-        if not hasattr(self._L, "mpcmmd_mpc_create"):
-            raise NativeError(f"{LIB_PATH} has no mpcmmd_mpc_create (built before the entry point existed): rebuild it")
-        self.handle, self.model, self.max_ticks = handle, model, int(max_ticks)
-        c = C.c_void_p()
-        check(self._L.mpcmmd_mpc_create(handle._h, C.byref(model.c), self.max_ticks, C.byref(c)))
-        self._c = c
-        self.E = 0
-        handle._ticks.append(self)   # Handle.close frees its contexts first
-
-    def close(self):
-        if getattr(self, "_c", None):
-            self._L.mpcmmd_mpc_destroy(self._c)
-            self._c = None
-            if self in self.handle._ticks:
-                self.handle._ticks.remove(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.handle = handle
+        self._open(handle._h, handle._ticks, handle, model, max_ticks)   # Handle.close frees its contexts first
 
     def reset(self, pos, vel, vehicles, mean, cov, u, keys):
         """pos [E, 2] float64, vel [E, 3] = vx, vy, psi, vehicles [E, num_obs, 4], mean [E, 8], cov
         [8, 8], keys [E] (episode e solves tick k with idx_mpc = k + keys[e]), u [max_ticks, E, 3] or
         None: the kernel draws each tick's variates from (keys[e], the handle's seed, tick)."""
-        pos = np.ascontiguousarray(np.asarray(pos, np.float64).reshape(-1, 2))
-        E = self.E = pos.shape[0]
-        f = lambda a, *sh: np.ascontiguousarray(np.asarray(a, np.float32).reshape(*sh))
-        veh = f(vehicles, E, self.model.num_obs, 4)
-        kk = np.ascontiguousarray(np.asarray(keys, np.int64).reshape(E).astype(np.int32))
-        check(self._L.mpcmmd_mpc_reset(self._c, E, pos.ctypes.data_as(C.POINTER(C.c_double)), _fptr(f(vel, E, 3)),
-                                       _fptr(veh) if veh.size else None, _fptr(f(mean, E, 8)), _fptr(f(cov, 64)),
-                                       None if u is None else _fptr(f(u, self.max_ticks, E, 3)),
-                                       kk.ctypes.data_as(C.POINTER(C.c_int32))))
-        self.handle._G = E
+        self._reset(pos, vel, vehicles, (self.model.num_obs, 4), mean, cov, u, keys)
 
     def run(self, cost, tick_begin, count, cov, v_des):
-        f = lambda a, *sh: np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32), sh))
-        check(self._L.mpcmmd_mpc_run(self._c, COST[cost], int(tick_begin), int(count),
-                                     _fptr(np.ascontiguousarray(np.asarray(cov, np.float32).reshape(64))),
-                                     _fptr(f(np.asarray(v_des, np.float32).reshape(-1), self.E))))
+        self._run(cost, tick_begin, count, cov, v_des)
 
     def log(self, ticks):
         """The first ``ticks`` rows: dict of log_d, log_f, log_i, cx, cy, mean, done_tick."""
-        T, E = int(ticks), self.E
-        ld, lf = np.empty((T, E, 2), np.float64), np.empty((T, E, 12), np.float32)
-        li, pl, dn = np.empty((T, E, 4), np.int32), np.empty((T, E, 30), np.float32), np.empty(E, np.int32)
-        ip = C.POINTER(C.c_int32)
-        check(self._L.mpcmmd_mpc_log(self._c, T, ld.ctypes.data_as(C.POINTER(C.c_double)), _fptr(lf),
-                                     li.ctypes.data_as(ip), _fptr(pl), dn.ctypes.data_as(ip)))
+        ld, lf, li, pl, dn = self._log(ticks)
         return dict(log_d=ld, log_f=lf, log_i=li, cx=pl[..., :11].copy(), cy=pl[..., 11:22].copy(),
                     mean=pl[..., 22:].copy(), done_tick=dn)
 
@@ -1138,18 +1141,18 @@ class Mpc:
         the policy off."""
         _need_planned(self._L)
         if target is None:
-            check(self._L.mpcmmd_mpc_plan_vehicles(self._c, 0, None, None))
+            check(self._L.mpcmmd_mpc_plan_vehicles(self._p, 0, None, None))
             return
         O = self.model.num_obs
         tg = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, O, 2))
         ac = None if acc is None else np.ascontiguousarray(np.asarray(acc, np.float32).reshape(tg.shape))
-        check(self._L.mpcmmd_mpc_plan_vehicles(self._c, tg.shape[0], _fptr(tg), None if ac is None else _fptr(ac)))
+        check(self._L.mpcmmd_mpc_plan_vehicles(self._p, tg.shape[0], _fptr(tg), None if ac is None else _fptr(ac)))
 
     def vehicle_log(self, ticks):
         """veh [ticks, E, O, 6]: every planned vehicle's state (x, y, vx, vy, ax, ay) after each tick's step."""
         _need_planned(self._L)
         out = np.zeros((max(int(ticks), 0), self.E, self.model.num_obs, 6), np.float32)
-        check(self._L.mpcmmd_mpc_vehicle_log(self._c, int(ticks), _fptr(out)))
+        check(self._L.mpcmmd_mpc_vehicle_log(self._p, int(ticks), _fptr(out)))
         return out
 
     def validate(self, rollouts, alpha=0.98, sigma=(), overlap=True):
@@ -1159,35 +1162,15 @@ class Mpc:
         most 8) into the validation log; ``overlap`` puts the validators' launches on the context's
         side stream, off the loop's critical path (False: in-line on the handle's stream; same bits).
         ``rollouts`` None turns the stage off."""
-        if not hasattr(self._L, "mpcmmd_mpc_validate"):
-            raise NativeError(f"{LIB_PATH} has no mpcmmd_mpc_validate (built before the entry point existed): "
-                              "rebuild it")
-        self._val_S = 0
-        if rollouts is None:
-            check(self._L.mpcmmd_mpc_validate(self._c, None))
-            return
-        sg = np.asarray(() if sigma is None else sigma, np.float32).reshape(-1)
-        cfg = MpcValidation(int(rollouts), float(alpha), int(sg.size))
-        for i, v in enumerate(sg[:8]):   # more than 8: num_sigma says so and the library refuses
-            cfg.sigma[i] = float(v)
-        cfg.overlap = int(overlap)
-        check(self._L.mpcmmd_mpc_validate(self._c, C.byref(cfg)))
-        self._val_S = int(sg.size)
+        self._validate(rollouts, alpha, sigma, overlap=int(overlap))
 
     def validation_log(self, ticks):
         """The first ``ticks`` rows of the validation log: val_counts [T, E, 2] (count, count_lane of
         ``validate``), val_count_pos [T, E, 3], val_stats [T, E, 4, 3] (var, cvar, mean, max by
         channels RISK_CHANNELS), val_mmd [T, E, 3, S] and val_est [T, E, 2] (the cost_lane and
         cost_obs the solve itself estimated)."""
-        T, E, S = int(ticks), self.E, getattr(self, "_val_S", 0)
-        n = max(T, 0)
-        cn, cp = np.zeros((n, E, 2), np.int32), np.zeros((n, E, 3), np.int32)
-        st, mm = np.zeros((n, E, 4, 3), np.float32), np.zeros((n, E, 3, S), np.float32)
-        es = np.zeros((n, E, 2), np.float32)
-        ip = C.POINTER(C.c_int32)
-        check(self._L.mpcmmd_mpc_validation_log(self._c, T, cn.ctypes.data_as(ip), cp.ctypes.data_as(ip), _fptr(st),
-                                                _fptr(mm) if S else None, _fptr(es)))
-        return dict(val_counts=cn, val_count_pos=cp, val_stats=st, val_mmd=mm, val_est=es)
+        out, st = self._validation_log(ticks)
+        return dict(out, val_stats=st)
 
     def validation_inputs(self):
         """The packed inputs of the last validated tick, as the validators read them: cx, cy [E, 11],
@@ -1198,7 +1181,7 @@ class Mpc:
                    keys=np.zeros(E, np.uint32))
         dp = C.POINTER(C.c_double)
         check(self._L.mpcmmd_mpc_validation_inputs(
-            self._c, *[out[k].ctypes.data_as(dp) for k in ("cx", "cy", "init_state")], _fptr(out["x_obs"]),
+            self._p, *[out[k].ctypes.data_as(dp) for k in ("cx", "cy", "init_state")], _fptr(out["x_obs"]),
             _fptr(out["y_obs"]), out["keys"].ctypes.data_as(C.POINTER(C.c_uint32))))
         return out
 

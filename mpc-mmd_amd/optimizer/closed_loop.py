@@ -62,6 +62,8 @@ import os
 
 import numpy as np
 
+from .episode_stats import mean_std as _mean_std
+
 COSTS = ("mmd_opt", "mmd_random", "cvar", "saa")
 KEYS = ("log_d", "log_f", "log_i", "cx", "cy", "mean", "done_tick")
 VAL_KEYS = ("val_counts", "val_count_pos", "val_stats", "val_mmd", "val_est")
@@ -112,11 +114,6 @@ def starts_of(variant, episodes):
 
 def _run(prob, cost, vehicles, starts, ticks, **kw):
     return prob.run_episodes(cost, vehicles, starts, ticks, **kw)
-
-
-def _mean_std(v):
-    v = np.asarray(v, np.float64)
-    return float(v.mean()) if v.size else 0.0, float(v.std(ddof=1)) if v.size > 1 else 0.0
 
 
 def summarise(res):

@@ -1,7 +1,7 @@
 // Host-code sanitizer harness ("run the CPU-side C++ under
 // ASan/UBSan").  Built by `make -C mpc-mmd_amd asan` with
 // -fsanitize=address,undefined from the library's own host sources
-// (csrc/*.cpp: host_constants, carla_host, solve_host, host_api), no GPU and no
+// (csrc/*.cpp: host_constants, carla_host, solve_host, host_api, episodes_host), no GPU and no
 // HIP runtime.  Exercises every host-only entry: the batch-invariant constants
 // of each variant and horizon (mpcmmd_host_constant's builders) and the
 // dynamic-obstacle QP trajectories (mpcmmd_obs_dynamic_traj's builder), then
@@ -9,8 +9,10 @@
 // tests/test_asan_host.py to compare with the product library's values.  The
 // C entry points that need no device (host_api.cpp) are called with valid and
 // with each kind of invalid argument, mpcmmd_create_batch's range check at its
-// boundaries, and the device buffer list (buffers.hpp) is expanded for five
-// shapes; a wrong status ends the run with exit code 3.
+// boundaries, the device buffer list (buffers.hpp) is expanded for five shapes,
+// and the episode contexts' host-only pieces (episodes_host.cpp) meet every
+// rejection, a hand-written table and a wrapping index; a wrong status ends the
+// run with exit code 3.
 //
 // Given a file name, it also writes there the inputs and results of the path
 // helpers (carla_host.cpp) and of every function of solve_host.cpp at the
@@ -22,12 +24,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../../mpc-mmd_amd/csrc/buffers.hpp"
+#include "../../mpc-mmd_amd/csrc/episodes_host.hpp"
 #include "../../mpc-mmd_amd/csrc/host_api.hpp"
 #include "../../mpc-mmd_amd/csrc/host_constants.hpp"
 #include "../../mpc-mmd_amd/csrc/layout.hpp"
@@ -374,10 +378,81 @@ static void buffer_list_cases() {
   }
 }
 
+// episodes_host.cpp: the validation stage's configuration check at each rejection and one acceptance,
+// the log's interleave at ticks = 2, E = 3 for both count widths against a table written out by
+// hand, and a tick's idx_mpc where the 32-bit sum wraps
+static void episode_host_cases() {
+  const int OK = MPCMMD_OK, BAD = MPCMMD_E_INVALID;
+  const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
+  const float good[8] = {0.1f, 0.2f, 0.3f, 0.4f, 0.5f, 0.6f, 0.7f, 0.8f};
+  int32_t lo = -1, hi = -1;
+  float w_lo = 0.0f, w_hi = 0.0f;
+  auto check = [&](int R, float alpha, int S, const float* sigma) {
+    return check_risk_config("t", R, alpha, S, sigma, &lo, &hi, &w_lo, &w_hi);
+  };
+  expect("risk config", check(10, 0.95f, 8, good), OK);
+  expect_true("risk config quantile", lo == 8 && hi == 9 && w_lo + w_hi == 1.0f);
+  expect("risk config edges", check(1 << 20, 1.0f, 0, nullptr), OK);
+  expect("risk config R 1, alpha 0", check(1, 0.0f, 0, nullptr), OK);
+  expect("risk config R 0", check(0, 0.5f, 0, nullptr), BAD);
+  expect_true("risk config text", std::string(mpcmmd_last_error()) == "t validation: num_rollouts out of 1..2^20");
+  expect("risk config R -1", check(-1, 0.5f, 0, nullptr), BAD);
+  expect("risk config R 2^20 + 1", check((1 << 20) + 1, 0.5f, 0, nullptr), BAD);
+  expect("risk config alpha < 0", check(10, -0.01f, 0, nullptr), BAD);
+  expect("risk config alpha > 1", check(10, 1.01f, 0, nullptr), BAD);
+  expect("risk config alpha NaN", check(10, nan, 0, nullptr), BAD);
+  expect_true("risk config text", std::string(mpcmmd_last_error()) == "t validation: alpha out of [0, 1]");
+  expect("risk config S -1", check(10, 0.5f, -1, good), BAD);
+  expect("risk config S 9", check(10, 0.5f, 9, good), BAD);
+  expect_true("risk config text", std::string(mpcmmd_last_error()) == "t validation: num_sigma out of [0, 8]");
+  for (float bad : {0.0f, -0.3f, inf, nan}) {
+    const float sigma[2] = {0.3f, bad};
+    expect("risk config sigma", check(10, 0.5f, 2, sigma), BAD);
+    expect_true("risk config text",
+                std::string(mpcmmd_last_error()) == "t validation: every sigma must be finite and > 0");
+    expect("risk config sigma beyond S", check(10, 0.5f, 1, sigma), OK);
+  }
+  // n = ticks * E = 6 rows: plane k of the counts holds 100 k + i, statistic k of row i holds
+  // 1000 k + 10 i + channel
+  const size_t n = 2 * 3;
+  std::vector<int32_t> planes(3 * n);
+  std::vector<float> stat_planes(4 * n * 3);
+  for (size_t k = 0; k < 3; ++k)
+    for (size_t i = 0; i < n; ++i) planes[k * n + i] = int32_t(100 * k + i);
+  for (size_t k = 0; k < 4; ++k)
+    for (size_t i = 0; i < n; ++i)
+      for (size_t ch = 0; ch < 3; ++ch) stat_planes[(k * n + i) * 3 + ch] = float(1000 * k + 10 * i + ch);
+  const int32_t want2[12] = {0, 100, 1, 101, 2, 102, 3, 103, 4, 104, 5, 105};
+  const int32_t want3[18] = {0, 100, 200, 1, 101, 201, 2, 102, 202, 3, 103, 203, 4, 104, 204, 5, 105, 205};
+  const float want_stats[12] = {20, 21, 22, 1020, 1021, 1022, 2020, 2021, 2022, 3020, 3021, 3022};  // row i = 2
+  for (int nc : {2, 3}) {
+    std::vector<int32_t> counts(n * nc, -1);   // exactly the documented sizes: a write past them is ASan's to find
+    std::vector<float> stats(n * 12, -1.0f);
+    interleave_risk_log(n, nc, planes.data(), stat_planes.data(), counts.data(), stats.data());
+    expect_true("interleave counts", std::memcmp(counts.data(), nc == 2 ? want2 : want3, counts.size() * 4) == 0);
+    expect_true("interleave stats", std::memcmp(stats.data() + 2 * 12, want_stats, sizeof want_stats) == 0);
+    expect_true("interleave stats ends", stats[0] == 0.0f && stats[n * 12 - 1] == 3052.0f);
+  }
+  // keys -1 and 7 at tick 2^20 - 1: the sum wraps in uint32 to 2^20 - 2; the covariance once per episode
+  const std::vector<uint32_t> keys = {0xFFFFFFFFu, 7u, 0x7FFFFFFFu};
+  std::vector<int32_t> idx(keys.size(), 0);
+  tick_indices((1 << 20) - 1, keys, idx.data());
+  expect_true("tick_indices",
+              idx[0] == (1 << 20) - 2 && idx[1] == (1 << 20) + 6 && idx[2] == INT32_MIN + (1 << 20) - 2);
+  tick_indices(0, keys, idx.data());
+  expect_true("tick_indices tick 0", idx[0] == -1 && idx[1] == 7 && idx[2] == INT32_MAX);
+  std::vector<float> cov(64);
+  for (int i = 0; i < 64; ++i) cov[i] = float(i);
+  const std::vector<float> covs = replicate_cov(cov.data(), 3);
+  expect_true("replicate_cov", covs.size() == 192 && covs[64] == 0.0f && covs[191] == 63.0f && covs[127] == 63.0f);
+  expect_true("replicate_cov none", replicate_cov(cov.data(), 0).empty());
+}
+
 int main(int argc, char** argv) {
   api_cases();
   create_range_cases();
   buffer_list_cases();
+  episode_host_cases();
   for (int variant = 0; variant < 4; ++variant) {
     for (int H : {2, 8, 20, 30, 50, 60, 100}) {
       if (variant >= 2 && H > 100) continue;
