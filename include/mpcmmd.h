@@ -1267,6 +1267,95 @@ int mpcmmd_mpc_step_device_planned(const mpcmmd_mpc_model* m, int32_t device, in
 int mpcmmd_mpc_plan_vehicles(mpcmmd_mpc* c, int32_t n_episodes, const float* veh_target, const float* veh_acc);
 int mpcmmd_mpc_vehicle_log(mpcmmd_mpc* c, int32_t ticks, float* veh);
 
+/* The scene queue of the synthetic chained route: N
+ * scenes through E slots, a slot refilled on the device as soon as its episode
+ * ends, one readback at the end.  (No ABI version change: callers detect the
+ * entry points by their symbols.)
+ *
+ * The rule, per slot e with scene[e] (a scene index, or -1: idle) and ltick[e]
+ * (its episode's local tick): after the step of a lockstep tick the episode has
+ * ended if done[e] >= 0 (a collision or the goal) or ltick[e] ==
+ * ticks_per_episode - 1.  Ended slots are served in ascending slot order; each
+ * takes the next unstarted scene, or becomes idle (and frozen) once the table
+ * is exhausted; every other live slot advances ltick[e] by one.  For every slot
+ * the next solve's idx_mpc[e] = ltick[e] + key[e] (32-bit wrap).  One schedule
+ * row per scene: sched [N][4] = slot, first lockstep tick, ticks run, end
+ * reason (MPCMMD_QUEUE_*); a scene never started has slot and first tick -1.
+ *
+ * mpcmmd_mpc_queue_host applies the rule to host arrays (no GPU needed);
+ * mpcmmd_mpc_queue_device is one k_mpc_queue launch on `device` over the same
+ * arrays: the same words.  flags [E][4] is the step's log_i row of the tick,
+ * keys and v_des [N] the scene table's; scene, ltick, done, key [E], sched and
+ * count [2] = started, finished are state (in and out), fresh [E] (the scene a
+ * slot took this tick, or -1), idx_mpc and slot_v_des [E] outputs (slot_v_des
+ * is written for slots that take a scene only).  MPCMMD_E_INVALID for a NULL
+ * array, n_slots or n_scenes < 1 (n_slots > 65535), ticks_per_episode < 1, a
+ * scene word outside -1..N-1, count[0] outside 0..N. */
+#define MPCMMD_QUEUE_UNFINISHED 0
+#define MPCMMD_QUEUE_COLLISION 1
+#define MPCMMD_QUEUE_GOAL 2
+#define MPCMMD_QUEUE_TICK_LIMIT 3
+typedef struct mpcmmd_mpc_queue_io {
+  int32_t n_slots, n_scenes, ticks_per_episode, tick;
+  const int32_t* flags;
+  const int32_t* keys;
+  const float* v_des;
+  int32_t *scene, *ltick, *done, *fresh;
+  uint32_t* key;
+  int32_t* idx_mpc;
+  float* slot_v_des;
+  int32_t* sched;
+  int32_t* count;
+} mpcmmd_mpc_queue_io;
+int mpcmmd_mpc_queue_host(const mpcmmd_mpc_queue_io* io);
+int mpcmmd_mpc_queue_device(int32_t device, const mpcmmd_mpc_queue_io* io);
+
+/* The queue on a context.  The scene table: pos [N][2], vel [N][3], vehicles
+ * [N][num_obs][4], mean [N][8] (a scene's start mean), v_des [N], keys [N] and,
+ * with the planned policy on (mpcmmd_mpc_plan_vehicles; its staged arrays are
+ * not read), veh_target and veh_acc [N][num_obs][2]: both NULL without it.
+ *
+ * mpcmmd_mpc_queue_reset (synchronous, like mpcmmd_mpc_reset) uploads the
+ * table, fills slots 0..min(N, n_slots)-1 with scenes in order -- a slot beyond
+ * them is idle from the start: frozen on a copy of scene 0's start state, owned
+ * by no scene -- and runs the reset-mode step.  The variates are always drawn.
+ *
+ * mpcmmd_mpc_queue_run enqueues, per lockstep tick of [tick_begin, tick_begin +
+ * count): the chained begin (only cov is staged: idx_mpc and v_des are on the
+ * device), the T CEM iterations, the step with each slot's own tick,
+ * k_mpc_queue, and the reset-mode step masked to the slots that took a scene.
+ * No readback, no synchronisation beyond the begin's staging-event wait, no
+ * allocation.  The lockstep log is mpcmmd_mpc_log's, [tick][slot] rows
+ * (done_tick holds local ticks); the schedule cuts it into per-scene episodes,
+ * each bit-equal to that scene run alone (tests/test_gpu_mpc_queue.py).
+ *
+ * mpcmmd_mpc_queue_status synchronises and reads the two counters;
+ * mpcmmd_mpc_queue_log synchronises and reads sched [N][4].
+ *
+ * MPCMMD_E_INVALID for a NULL argument, n_slots outside 1..max_configs,
+ * n_scenes < 1, ticks_per_episode < 1, policy arrays that do not match the
+ * policy's state, a tick range outside [0, max_ticks].  MPCMMD_E_STATE for any
+ * queue call with the validation stage on (its validators are keyed by the
+ * lockstep tick), for a queue run, status or log before a queue reset, and for
+ * mpcmmd_mpc_run after a queue reset (until an ordinary reset) or a queue run
+ * after an ordinary reset. */
+typedef struct mpcmmd_mpc_scenes {
+  int32_t n_scenes;
+  const double* pos;
+  const float* vel;
+  const float* vehicles;
+  const float* mean;
+  const float* v_des;
+  const int32_t* keys;
+  const float* veh_target;
+  const float* veh_acc;
+} mpcmmd_mpc_scenes;
+int mpcmmd_mpc_queue_reset(mpcmmd_mpc* c, int32_t n_slots, int32_t ticks_per_episode, const mpcmmd_mpc_scenes* scenes,
+                           const float* cov);
+int mpcmmd_mpc_queue_run(mpcmmd_mpc* c, int32_t cost_kind, int32_t tick_begin, int32_t count, const float* cov);
+int mpcmmd_mpc_queue_status(mpcmmd_mpc* c, int32_t* started, int32_t* finished);
+int mpcmmd_mpc_queue_log(mpcmmd_mpc* c, int32_t* sched);
+
 #ifdef __cplusplus
 }
 #endif

@@ -66,8 +66,10 @@ int mpcmmd::begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const
                        const float* init_state, const float* mean, const float* cov, const float* x_obs,
                        const float* y_obs, const float* v_des, const mpcmmd_draws* draws, const mpcmmd_path* path,
                        const TickRoute* tick, bool resident) {
+  // the resident route of the scene queue: idx_mpc and v_des are on the device already (k_mpc_queue wrote them)
+  const bool queued = resident && !idx_mpc && !v_des;
   if (resident) {  // the synthetic closed loop (mpc_api.hip): only idx_mpc, cov and v_des come from the host
-    if (!h || !idx_mpc || !cov || !v_des) return fail(MPCMMD_E_INVALID, "null argument");
+    if (!h || !cov || (!queued && (!idx_mpc || !v_des))) return fail(MPCMMD_E_INVALID, "null argument");
     if (h->carla || path || tick || draws)
       return fail(MPCMMD_E_INVALID, "the resident begin is the static / dynamic variants' own");
   } else if (!h || !idx_mpc || !init_state || !mean || !cov || (!tick && (!x_obs || !y_obs)) || !v_des) {
@@ -132,8 +134,10 @@ int mpcmmd::begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const
       p.w_lane = cost_kind == MPCMMD_COST_MMD_OPT ? 0.01f : cost_kind == MPCMMD_COST_DET ? 0.0f : 25.0f;
       p.w_des = 0.0f;
     }
-    upload_staged(h, p.idx_mpc, idx_mpc, cfg_bytes(h, p.idx_mpc, G));
-    upload_staged(h, p.v_des, v_des, cfg_bytes(h, p.v_des, G));
+    if (!queued) {
+      upload_staged(h, p.idx_mpc, idx_mpc, cfg_bytes(h, p.idx_mpc, G));
+      upload_staged(h, p.v_des, v_des, cfg_bytes(h, p.v_des, G));
+    }
     // sampling_param (cem_helper.py:122-150): fixed key, the same draws for every configuration
     // (the internal draws depend on the seed and B only: made once per handle)
     std::vector<float> z0x;

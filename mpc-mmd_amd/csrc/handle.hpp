@@ -204,7 +204,9 @@ struct TickRoute {
 // synthetic closed loop's route (mpc_api.hip) for static / dynamic handles, on
 // which st0, solve_c, obs, the first population and the mean are on the device
 // already (k_mpc_step wrote them; init_state, mean, x_obs, y_obs are not read):
-// only idx_mpc, v_des and cov are staged.
+// only idx_mpc, v_des and cov are staged.  resident with idx_mpc and v_des both
+// null: the scene queue's mode, in which those two are on
+// the device as well (k_mpc_queue wrote them) and only cov is staged.
 int begin_impl(mpcmmd_handle* h, int32_t n_cfg, int32_t cost_kind, const int32_t* idx_mpc, const float* init_state,
                const float* mean, const float* cov, const float* x_obs, const float* y_obs, const float* v_des,
                const mpcmmd_draws* draws, const mpcmmd_path* path = nullptr, const TickRoute* tick = nullptr,

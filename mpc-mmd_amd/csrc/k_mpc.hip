@@ -14,8 +14,10 @@
 // Static LDS only (about 1.1 KB).  Latency-bound by construction (a handful of
 // dependent fp64 chains); launched once per tick.
 // k_mpc_step_planned is the same step with the vehicles following their
-// re-planned QP: the body below is written once and
-// instantiated twice.
+// re-planned QP, k_mpc_step_queue and
+// k_mpc_step_planned_queue the same two steps with a tick per slot and a mask
+// (the scene queue): the body below is written once and
+// instantiated four times.
 #include "mpc.hpp"
 #include "mpc_draw.hpp"
 
@@ -38,10 +40,16 @@ struct DevMath {
 //      vehicle (its coefficients broadcast) and read rows of s_P 88 B apart (no bank shared)
 // The instantiation without the policy references none of the policy's LDS and is the kernel
 // it was: about 1.1 KB of static LDS; with the policy about 17 KB.
-template <bool kPlanned>
+// kQueue: the scene queue's step -- the slot's own tick (q.ltick) where the
+// step reads q.tick (the drawn variates, done), and with q.fresh a slot that took no scene returns
+// at once (the masked reset).  The instantiations without it read neither pointer.
+template <bool kPlanned, bool kQueue = false>
 DEVI void mpc_step_body(const MpcStepParams& q, const MpcVehParams* pv) {
   const MpcScalars& w = q.w;
   const int ep = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if constexpr (kQueue) {
+    if (q.fresh && q.fresh[ep] < 0) return;  // the whole workgroup
+  }
   __shared__ MpcEgo s_ego;
   __shared__ MpcControl s_ctl;
   __shared__ float s_u[3];
@@ -78,7 +86,7 @@ DEVI void mpc_step_body(const MpcStepParams& q, const MpcVehParams* pv) {
     if (!q.reset) {  // a reset runs before any solve: the result buffers hold nothing yet
       c = mpc_controller<DevMath>(q.pdot2, q.pddot1, cx, cy);
       if (q.u) for (int k = 0; k < 3; ++k) u[k] = q.u[ep * 3 + k];
-      else mpc_draw(w.noise, q.key[ep], q.seed, q.tick, c.a_c, c.s_c, u);
+      else mpc_draw(w.noise, q.key[ep], q.seed, kQueue ? q.ltick[ep] : q.tick, c.a_c, c.s_c, u);
       mpc_perturb(w, u, c);
     }
     for (int k = 0; k < 3; ++k) s_u[k] = u[k];
@@ -177,7 +185,7 @@ DEVI void mpc_step_body(const MpcStepParams& q, const MpcVehParams* pv) {
     const MpcControl c = s_ctl;
     const float clear = s_clear;
     const bool lane_out = mpc_lane_out(w, e), collided = !(clear <= 0.0f), goal = mpc_goal(w, e);
-    if (!frozen && (collided || goal)) q.done[ep] = q.tick;
+    if (!frozen && (collided || goal)) q.done[ep] = kQueue ? q.ltick[ep] : q.tick;
     double* ld = q.logd + size_t(ep) * 2;
     ld[0] = e.x, ld[1] = e.y;
     float* lf = q.logf + size_t(ep) * 12;
@@ -203,6 +211,14 @@ __global__ __launch_bounds__(kMpcThreads) void k_mpc_step_planned(const MpcStepP
   mpc_step_body<true>(q, &pv);
 }
 
+__global__ __launch_bounds__(kMpcThreads) void k_mpc_step_queue(const MpcStepParams q) {
+  mpc_step_body<false, true>(q, nullptr);
+}
+
+__global__ __launch_bounds__(kMpcThreads) void k_mpc_step_planned_queue(const MpcStepParams q, const MpcVehParams pv) {
+  mpc_step_body<true, true>(q, &pv);
+}
+
 }  // namespace
 
 void launch_mpc_step(const MpcStepParams& q, int episodes, hipStream_t s) {
@@ -211,6 +227,14 @@ void launch_mpc_step(const MpcStepParams& q, int episodes, hipStream_t s) {
 
 void launch_mpc_step_planned(const MpcStepParams& q, const MpcVehParams& pv, int episodes, hipStream_t s) {
   hipLaunchKernelGGL(k_mpc_step_planned, dim3(episodes), dim3(kMpcThreads), 0, s, q, pv);
+}
+
+void launch_mpc_step_queue(const MpcStepParams& q, int episodes, hipStream_t s) {
+  hipLaunchKernelGGL(k_mpc_step_queue, dim3(episodes), dim3(kMpcThreads), 0, s, q);
+}
+
+void launch_mpc_step_planned_queue(const MpcStepParams& q, const MpcVehParams& pv, int episodes, hipStream_t s) {
+  hipLaunchKernelGGL(k_mpc_step_planned_queue, dim3(episodes), dim3(kMpcThreads), 0, s, q, pv);
 }
 
 }  // namespace mpcmmd

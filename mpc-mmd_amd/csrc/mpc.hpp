@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "mpc_queue.hpp"
 #include "mpc_step.hpp"
 #include "mpc_vehicle.hpp"
 
@@ -41,6 +42,9 @@ struct MpcStepParams {
   float* logf;                     // [E][12]
   int32_t* logi;                   // [E][4]
   float* plan;                     // [E][30] cx, cy, mean: the chained route's log of the plan, or null
+  // the scene queue's instantiations only
+  const int32_t* ltick;            // [E] each slot's own tick, in place of `tick`
+  const int32_t* fresh;            // [E] or null: a slot whose word is < 0 is left alone (the masked reset)
 };
 
 // The planned instantiation's further arguments: the
@@ -54,5 +58,26 @@ struct MpcVehParams {
 
 void launch_mpc_step(const MpcStepParams& q, int episodes, hipStream_t s);
 void launch_mpc_step_planned(const MpcStepParams& q, const MpcVehParams& pv, int episodes, hipStream_t s);
+// the same two steps with a tick per slot (q.ltick) and the mask (q.fresh)
+void launch_mpc_step_queue(const MpcStepParams& q, int episodes, hipStream_t s);
+void launch_mpc_step_planned_queue(const MpcStepParams& q, const MpcVehParams& pv, int episodes, hipStream_t s);
+
+// k_mpc_queue's arguments: the rule's words (mpc_queue.hpp), the step's log_i row of this tick, the
+// scene table and the slots' state it refills.  The state tables are null in the harness.
+struct MpcQueueParams {
+  MpcQueueState st;
+  int E, N, ticks_per_episode, tick, O;
+  const int32_t* flags;        // [E][4]
+  const uint32_t* tab_key;     // [N]
+  const float* tab_v_des;      // [N]
+  const double* tab_pos;       // [N][2], or null: no state is copied
+  const float *tab_vel, *tab_veh, *tab_mean;  // [N][3], [N][O][4], [N][8]
+  const float *tab_target, *tab_acc;          // [N][O][2] each, or null (no planned policy)
+  double* pos;                 // [E][2]
+  float *vel, *veh, *mean;     // [E][3], [E][O][4], [E][8] (the handle's mean)
+  float *target, *acc;         // [E][O][2]
+};
+
+void launch_mpc_queue(const MpcQueueParams& p, hipStream_t s);
 
 }  // namespace mpcmmd

@@ -15,12 +15,20 @@
 // 23) the reset's and every tick's step is k_mpc_step_planned: the constants, the
 // accelerations, the targets and the vehicle log live in the context, and the
 // loop gains no copy, synchronisation or allocation.
+// The scene queue (mpcmmd_mpc_queue_*) runs N scenes
+// through the context's slots: per tick the begin stages only cov, the step takes
+// each slot's own tick, k_mpc_queue (k_mpc_queue.hip) refills the slots whose
+// episode ended and a reset-mode step masked to them writes their next solve's
+// buffers.
+#include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 #include "episodes.hpp"
 #include "mpc.hpp"
 #include "mpc_draw.hpp"
 #include "mpc_host.hpp"
+#include "mpc_queue_host.hpp"
 #include "mpc_validate.hpp"
 #include "rng.hpp"
 #include "solve_host.hpp"
@@ -41,6 +49,11 @@ struct __attribute__((visibility("hidden"))) mpcmmd_mpc {
   MpcVehParams pv{};             // the constants, the live accelerations, the targets
   float* veh_acc0 = nullptr;     // [Emax][O][2] the staged accelerations every reset starts from
   float* veh_log = nullptr;      // [Tmax][Emax][O][6]
+  // the scene queue
+  Arena queue;               // the scene table, the slots' words and the schedule of the last queue reset
+  MpcQueueParams qp{};       // k_mpc_queue's arguments but the tick and its log_i row
+  bool queue_on = false;     // the steps are the queue's instantiations (set by either reset)
+  bool queue_ready = false;  // a queue reset succeeded and nothing replaced it since
 };
 
 namespace {
@@ -61,7 +74,9 @@ std::vector<double> kkt_columns(const ProblemConsts& pc) {
 // mpcmmd_iterate enqueued (the group streams of large handles join it before iterate returns),
 // ahead of the next begin.  The plan from the handle's results of the last iteration, the next
 // solve's buffers where begin_impl's resident route expects them.
-void enqueue_step(mpcmmd_mpc* c, int tick, bool reset) {
+// With the queue on the step is the queue's instantiation: each slot's own tick, and with `masked`
+// (the reset-mode step behind k_mpc_queue) only the slots that took a scene.
+void enqueue_step(mpcmmd_mpc* c, int tick, bool reset, bool masked = false) {
   const Episodes& s = c->s;
   mpcmmd_handle* h = s.h;
   MpcStepParams q = c->q;
@@ -81,14 +96,37 @@ void enqueue_step(mpcmmd_mpc* c, int tick, bool reset) {
   q.logd = s.logd + row * 2, q.logf = s.logf + row * 12, q.logi = s.logi + row * 4;
   q.plan = s.plan + row * 30;
   q.chol = s.chol;
+  if (c->queue_on) q.ltick = c->qp.st.ltick, q.fresh = masked ? c->qp.st.fresh : nullptr;
   if (s.veh_on) {
     MpcVehParams pv = c->pv;
-    pv.log = c->veh_log + row * size_t(q.w.O) * 6;
-    launch_mpc_step_planned(q, pv, s.E, h->stream);
+    pv.log = masked ? nullptr : c->veh_log + row * size_t(q.w.O) * 6;  // a refill logs no row
+    if (c->queue_on) launch_mpc_step_planned_queue(q, pv, s.E, h->stream);
+    else launch_mpc_step_planned(q, pv, s.E, h->stream);
+  } else if (c->queue_on) {
+    launch_mpc_step_queue(q, s.E, h->stream);
   } else {
     launch_mpc_step(q, s.E, h->stream);
   }
   HIPC(hipGetLastError());
+}
+
+// k_mpc_queue behind the step of lockstep tick `tick`: the rule on the slots' words, the refills
+void enqueue_queue(mpcmmd_mpc* c, int tick) {
+  MpcQueueParams p = c->qp;
+  p.tick = tick;
+  p.flags = c->s.logi + size_t(tick) * c->s.Emax * 4;
+  launch_mpc_queue(p, c->s.h->stream);
+  HIPC(hipGetLastError());
+}
+
+// what every queue call checks first
+int queue_state(mpcmmd_mpc* c, const char* entry, bool need_reset) {
+  if (c->s.val_on)
+    return fail(MPCMMD_E_STATE, std::string(entry) + " with the validation stage on (its validators are keyed by the lockstep tick)");
+  if (need_reset && !c->queue_ready)
+    return fail(MPCMMD_E_STATE, std::string(entry) + (c->s.reset_done ? " after mpcmmd_mpc_reset: the queue needs mpcmmd_mpc_queue_reset"
+                                                                     : " before mpcmmd_mpc_queue_reset"));
+  return MPCMMD_OK;
 }
 
 // the validation stage of tick `tick`, behind its CEM iterations and before its step (the step
@@ -323,6 +361,7 @@ int mpcmmd_mpc_reset(mpcmmd_mpc* c, int32_t n_episodes, const double* pos, const
     return fail(MPCMMD_E_INVALID, "mpc: n_episodes must be 1..max_configs of the handle");
   if (c->s.veh_on && n_episodes != c->s.veh_E)
     return fail(MPCMMD_E_INVALID, "mpc: n_episodes is not the one mpcmmd_mpc_plan_vehicles staged");
+  c->queue_on = c->queue_ready = false;  // nothing is in flight once the reset has synchronised
   auto upload = [&](size_t E) {
     const size_t O = size_t(c->q.w.O);
     HIPC(hipMemcpy(c->q.vel, vel, E * 3 * 4, hipMemcpyHostToDevice));
@@ -338,7 +377,9 @@ int mpcmmd_mpc_reset(mpcmmd_mpc* c, int32_t n_episodes, const double* pos, const
 int mpcmmd_mpc_run(mpcmmd_mpc* c, int32_t cost_kind, int32_t tick_begin, int32_t count, const float* cov,
                    const float* v_des) {
   if (!c || !cov || !v_des) return fail(MPCMMD_E_INVALID, "null argument");
-  if (!c->s.reset_done) return fail(MPCMMD_E_STATE, "mpcmmd_mpc_run before mpcmmd_mpc_reset");
+  if (!c->s.reset_done)
+    return fail(MPCMMD_E_STATE, c->queue_ready ? "mpcmmd_mpc_run after mpcmmd_mpc_queue_reset: an ordinary run needs mpcmmd_mpc_reset"
+                                               : "mpcmmd_mpc_run before mpcmmd_mpc_reset");
   if (tick_begin < 0 || count < 0 || tick_begin + count > c->s.Tmax) return fail(MPCMMD_E_INVALID, "mpc: tick range");
   return run_ticks(
       c->s, tick_begin, count, cov,
@@ -368,6 +409,7 @@ int mpcmmd_mpc_log(mpcmmd_mpc* c, int32_t ticks, double* log_d, float* log_f, in
 
 int mpcmmd_mpc_validate(mpcmmd_mpc* c, const mpcmmd_mpc_validation* cfg) {
   if (!c) return fail(MPCMMD_E_INVALID, "null argument");
+  c->queue_ready = false;  // like reset_done: the stage changes with the episodes
   Episodes& s = c->s;
   mpcmmd_handle* h = s.h;
   const int O = h->O, H = h->H;
@@ -436,6 +478,7 @@ int mpcmmd_mpc_validation_inputs(mpcmmd_mpc* c, double* cx, double* cy, double* 
 
 int mpcmmd_mpc_plan_vehicles(mpcmmd_mpc* c, int32_t n_episodes, const float* veh_target, const float* veh_acc) {
   if (!c) return fail(MPCMMD_E_INVALID, "null argument");
+  c->queue_ready = false;  // the queue's refills point into the policy's arrays
   MpcVehTables t{};
   if (veh_target) {
     if (n_episodes < 1 || n_episodes > c->s.Emax)
@@ -476,6 +519,149 @@ int mpcmmd_mpc_vehicle_log(mpcmmd_mpc* c, int32_t ticks, float* veh) {
     sync_streams(c);
     const size_t row = size_t(c->q.w.O) * 6 * 4, E = size_t(c->s.E);
     if (ticks > 0 && E > 0 && row > 0) rows_back(veh, c->veh_log, row, ticks, E, size_t(c->s.Emax));
+    return MPCMMD_OK;
+  });
+}
+
+int mpcmmd_mpc_queue_device(int32_t device, const mpcmmd_mpc_queue_io* io) {
+  if (int rc = check_mpc_queue(io)) return rc;
+  return guarded([&] {
+    StepHarness hs;
+    if (int rc = hs.open("mpc queue", device, io->n_slots)) return rc;
+    const size_t E = size_t(io->n_slots), N = size_t(io->n_scenes);
+    MpcQueueParams p{};
+    p.E = io->n_slots, p.N = io->n_scenes, p.ticks_per_episode = io->ticks_per_episode, p.tick = io->tick;
+    p.flags = hs.in(io->flags, E * 4);
+    p.tab_key = hs.in(reinterpret_cast<const uint32_t*>(io->keys), N), p.tab_v_des = hs.in(io->v_des, N);
+    MpcQueueState& st = p.st;
+    st.scene = hs.io(io->scene, E, true), st.ltick = hs.io(io->ltick, E, true), st.done = hs.io(io->done, E, true);
+    st.fresh = hs.io(io->fresh, E, false), st.key = hs.io(io->key, E, true);
+    st.idx_mpc = hs.io(io->idx_mpc, E, false), st.v_des = hs.io(io->slot_v_des, E, true);
+    st.sched = hs.io(io->sched, N * 4, true), st.count = hs.io(io->count, 2, true);
+    launch_mpc_queue(p, nullptr);  // no state tables: the rule's words only
+    hs.finish();
+    return MPCMMD_OK;
+  });
+}
+
+int mpcmmd_mpc_queue_reset(mpcmmd_mpc* c, int32_t n_slots, int32_t ticks_per_episode, const mpcmmd_mpc_scenes* sc,
+                           const float* cov) {
+  if (!c || !sc || !cov) return fail(MPCMMD_E_INVALID, "null argument");
+  if (int rc = queue_state(c, "mpcmmd_mpc_queue_reset", false)) return rc;
+  const size_t O = size_t(c->q.w.O);
+  if (!sc->pos || !sc->vel || !sc->mean || !sc->v_des || !sc->keys || (O > 0 && !sc->vehicles))
+    return fail(MPCMMD_E_INVALID, "null argument");
+  if (n_slots < 1 || n_slots > c->s.Emax) return fail(MPCMMD_E_INVALID, "mpc queue: n_slots must be 1..max_configs of the handle");
+  if (sc->n_scenes < 1 || sc->n_scenes > (1 << 24)) return fail(MPCMMD_E_INVALID, "mpc queue: 1 <= n_scenes <= 2^24");
+  if (ticks_per_episode < 1) return fail(MPCMMD_E_INVALID, "mpc queue: ticks_per_episode >= 1");
+  const bool planned = c->s.veh_on;
+  if (planned ? (O > 0 && (!sc->veh_target || !sc->veh_acc)) : (sc->veh_target || sc->veh_acc))
+    return fail(MPCMMD_E_INVALID, planned ? "mpc queue: the planned policy is on: veh_target and veh_acc are needed"
+                                          : "mpc queue: veh_target and veh_acc need the planned policy (mpcmmd_mpc_plan_vehicles)");
+  const size_t E = size_t(n_slots), N = size_t(sc->n_scenes), filled = std::min(E, N);
+  // the slots' start: scene e in slot e; a slot beyond the table idles on a copy of scene 0
+  auto of = [&](size_t e) { return e < filled ? e : size_t(0); };
+  auto rows = [&](auto* tab, size_t width) {
+    std::vector<std::remove_cv_t<std::remove_pointer_t<decltype(tab)>>> v(E * width);
+    for (size_t e = 0; e < E; ++e) std::copy(tab + of(e) * width, tab + (of(e) + 1) * width, v.begin() + e * width);
+    return v;
+  };
+  const std::vector<double> pos = rows(sc->pos, 2);
+  const std::vector<float> vel = rows(sc->vel, 3), mean = rows(sc->mean, 8), vdes = rows(sc->v_des, 1);
+  const std::vector<int32_t> keys = rows(sc->keys, 1);
+  std::vector<int32_t> scene(E), done(E), idx(E), none(E, -1), sched(N * 4, 0), count = {int32_t(filled), 0};
+  for (size_t e = 0; e < E; ++e) {
+    scene[e] = e < filled ? int32_t(e) : -1, done[e] = e < filled ? -1 : 0;
+    idx[e] = queue_idx(0, uint32_t(keys[e]));
+  }
+  for (size_t n = 0; n < N; ++n) sched[n * 4] = n < filled ? int32_t(n) : -1, sched[n * 4 + 1] = n < filled ? 0 : -1;
+  c->s.reset_done = c->queue_ready = false;
+  auto upload = [&](size_t) {
+    mpcmmd_handle* h = c->s.h;
+    HIPC(hipMemcpy(c->q.vel, vel.data(), E * 3 * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(const_cast<int32_t*>(h->p.idx_mpc), idx.data(), E * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(const_cast<float*>(h->p.v_des), vdes.data(), E * 4, hipMemcpyHostToDevice));
+    if (O) {
+      const std::vector<float> veh = rows(sc->vehicles, O * 4);
+      HIPC(hipMemcpy(c->q.veh, veh.data(), E * O * 4 * 4, hipMemcpyHostToDevice));
+    }
+    if (planned && O) {
+      const std::vector<float> tg = rows(sc->veh_target, O * 2), ac = rows(sc->veh_acc, O * 2);
+      HIPC(hipMemcpy(const_cast<float*>(c->pv.target), tg.data(), E * O * 2 * 4, hipMemcpyHostToDevice));
+      HIPC(hipMemcpy(c->pv.acc, ac.data(), E * O * 2 * 4, hipMemcpyHostToDevice));
+    }
+    Arena& a = c->queue;
+    a.release();  // the last campaign's table
+    MpcQueueParams& p = c->qp;
+    p = MpcQueueParams{};
+    p.E = n_slots, p.N = sc->n_scenes, p.ticks_per_episode = ticks_per_episode, p.O = int(O);
+    p.tab_key = a.alloc<uint32_t>(N, sc->keys), p.tab_v_des = a.alloc<float>(N, sc->v_des);
+    p.tab_pos = a.alloc<double>(N * 2, sc->pos), p.tab_vel = a.alloc<float>(N * 3, sc->vel);
+    p.tab_veh = a.alloc<float>(N * O * 4, sc->vehicles), p.tab_mean = a.alloc<float>(N * 8, sc->mean);
+    if (planned && O)
+      p.tab_target = a.alloc<float>(N * O * 2, sc->veh_target), p.tab_acc = a.alloc<float>(N * O * 2, sc->veh_acc);
+    p.pos = c->q.pos, p.vel = c->q.vel, p.veh = c->q.veh, p.mean = h->p.mean;
+    p.target = const_cast<float*>(c->pv.target), p.acc = c->pv.acc;
+    MpcQueueState& st = p.st;
+    st.scene = a.alloc<int32_t>(E, scene.data()), st.ltick = a.alloc<int32_t>(E);
+    HIPC(hipMemset(st.ltick, 0, E * 4));
+    st.done = c->s.done, st.fresh = a.alloc<int32_t>(E, none.data()), st.key = c->s.keys_dev;
+    st.idx_mpc = const_cast<int32_t*>(h->p.idx_mpc), st.v_des = const_cast<float*>(h->p.v_des);
+    st.sched = a.alloc<int32_t>(N * 4, sched.data()), st.count = a.alloc<int32_t>(2, count.data());
+  };
+  c->queue_on = true;
+  const int rc = reset_common(c->s, n_slots, pos.data(), mean.data(), cov, nullptr, keys.data(), [&] { sync_streams(c); },
+                              upload, [&] {
+    HIPC(hipMemcpy(c->s.done, done.data(), E * 4, hipMemcpyHostToDevice));  // the idle slots are frozen
+    enqueue_step(c, -1, true);
+    HIPC(hipStreamSynchronize(c->s.h->stream));
+  });
+  c->s.reset_done = false;  // an ordinary run needs an ordinary reset
+  c->queue_ready = rc == MPCMMD_OK;
+  return rc;
+}
+
+int mpcmmd_mpc_queue_run(mpcmmd_mpc* c, int32_t cost_kind, int32_t tick_begin, int32_t count, const float* cov) {
+  if (!c || !cov) return fail(MPCMMD_E_INVALID, "null argument");
+  if (int rc = queue_state(c, "mpcmmd_mpc_queue_run", true)) return rc;
+  if (tick_begin < 0 || count < 0 || tick_begin + count > c->s.Tmax) return fail(MPCMMD_E_INVALID, "mpc: tick range");
+  const std::vector<float> covs = replicate_cov(cov, c->s.E);
+  for (int k = tick_begin; k < tick_begin + count; ++k) {
+    if (int rc = begin_impl(c->s.h, c->s.E, cost_kind, nullptr, nullptr, nullptr, covs.data(), nullptr, nullptr, nullptr,
+                            nullptr, nullptr, nullptr, true))
+      return rc;
+    if (int rc = mpcmmd_iterate(c->s.h, 0, c->s.h->T)) return rc;
+    if (int rc = guarded([&] {
+          enqueue_step(c, k, false);
+          enqueue_queue(c, k);
+          enqueue_step(c, k, true, true);  // st0, solve_c, obs, the population of the refilled slots
+          return MPCMMD_OK;
+        }))
+      return rc;
+  }
+  return MPCMMD_OK;
+}
+
+int mpcmmd_mpc_queue_status(mpcmmd_mpc* c, int32_t* started, int32_t* finished) {
+  if (!c || !started || !finished) return fail(MPCMMD_E_INVALID, "null argument");
+  if (int rc = queue_state(c, "mpcmmd_mpc_queue_status", true)) return rc;
+  return guarded([&] {
+    check_device(c->s.h);
+    sync_streams(c);
+    int32_t count[2];
+    HIPC(hipMemcpy(count, c->qp.st.count, sizeof count, hipMemcpyDeviceToHost));
+    *started = count[0], *finished = count[1];
+    return MPCMMD_OK;
+  });
+}
+
+int mpcmmd_mpc_queue_log(mpcmmd_mpc* c, int32_t* sched) {
+  if (!c || !sched) return fail(MPCMMD_E_INVALID, "null argument");
+  if (int rc = queue_state(c, "mpcmmd_mpc_queue_log", true)) return rc;
+  return guarded([&] {
+    check_device(c->s.h);
+    sync_streams(c);
+    HIPC(hipMemcpy(sched, c->qp.st.sched, size_t(c->qp.N) * 16, hipMemcpyDeviceToHost));
     return MPCMMD_OK;
   });
 }

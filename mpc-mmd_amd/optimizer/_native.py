@@ -40,6 +40,8 @@ SYMBOLS = (
     "mpcmmd_mpc_validate", "mpcmmd_mpc_validation_log", "mpcmmd_mpc_validation_inputs",
     "mpcmmd_mpc_vehicle_constant", "mpcmmd_mpc_step_host_planned", "mpcmmd_mpc_step_device_planned",
     "mpcmmd_mpc_plan_vehicles", "mpcmmd_mpc_vehicle_log",
+    "mpcmmd_mpc_queue_host", "mpcmmd_mpc_queue_device", "mpcmmd_mpc_queue_reset", "mpcmmd_mpc_queue_run",
+    "mpcmmd_mpc_queue_status", "mpcmmd_mpc_queue_log",
     "mpcmmd_world_step_host_routed", "mpcmmd_world_step_device_routed", "mpcmmd_world_route_vehicles",
     "mpcmmd_world_vehicle_log",
 )
@@ -192,6 +194,25 @@ class MpcPlanned(C.Structure):
     _fields_ = [(k, C.POINTER(C.c_float)) for k in ("veh_acc", "veh_target", "veh_log")]
 
 
+class MpcQueueIO(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("n_slots", "n_scenes", "ticks_per_episode", "tick")] +
+                [("flags", C.POINTER(C.c_int32)), ("keys", C.POINTER(C.c_int32)), ("v_des", C.POINTER(C.c_float))] +
+                [(k, C.POINTER(C.c_int32)) for k in ("scene", "ltick", "done", "fresh")] +
+                [("key", C.POINTER(C.c_uint32)), ("idx_mpc", C.POINTER(C.c_int32)),
+                 ("slot_v_des", C.POINTER(C.c_float)), ("sched", C.POINTER(C.c_int32)),
+                 ("count", C.POINTER(C.c_int32))])
+
+
+class MpcScenes(C.Structure):
+    _fields_ = ([("n_scenes", C.c_int32), ("pos", C.POINTER(C.c_double))] +
+                [(k, C.POINTER(C.c_float)) for k in ("vel", "vehicles", "mean", "v_des")] +
+                [("keys", C.POINTER(C.c_int32)), ("veh_target", C.POINTER(C.c_float)),
+                 ("veh_acc", C.POINTER(C.c_float))])
+
+
+QUEUE_REASONS = ("unfinished", "collision", "goal", "tick_limit")   # MPCMMD_QUEUE_*: sched[:, 3]
+QUEUE_SCHED = ("slot", "first_tick", "ticks", "reason")
+
 MPC_LOG_D = ("x", "y")
 MPC_LOG_F = ("vx", "vy", "psi", "a_c", "s_c", "a", "s", "u0", "u1", "u2", "clear", "curv")
 MPC_LOG_I = ("lane_out", "collided", "goal", "frozen")
@@ -326,6 +347,13 @@ def lib():
                                                      C.POINTER(MpcStepIO), C.POINTER(MpcPlanned)]
         L.mpcmmd_mpc_plan_vehicles.argtypes = [vp, C.c_int32, fp, fp]
         L.mpcmmd_mpc_vehicle_log.argtypes = [vp, C.c_int32, fp]
+    if hasattr(L, "mpcmmd_mpc_queue_reset"):   # an older library lacks the scene queue: the callers raise
+        L.mpcmmd_mpc_queue_host.argtypes = [C.POINTER(MpcQueueIO)]
+        L.mpcmmd_mpc_queue_device.argtypes = [C.c_int32, C.POINTER(MpcQueueIO)]
+        L.mpcmmd_mpc_queue_reset.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(MpcScenes), fp]
+        L.mpcmmd_mpc_queue_run.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp]
+        L.mpcmmd_mpc_queue_status.argtypes = [vp, ip, ip]
+        L.mpcmmd_mpc_queue_log.argtypes = [vp, ip]
     L.mpcmmd_path_smoothing.argtypes = [C.c_int32, fp, fp, C.c_float, fp, fp]
     L.mpcmmd_path_parameters.argtypes = [C.c_int32, fp, fp, fp, fp, fp, fp, fp, fp, fp]
     L.mpcmmd_global_to_frenet.argtypes = [C.POINTER(Path), C.c_int32, fp, fp, fp, fp, fp, fp, fp]
@@ -1106,6 +1134,42 @@ def mpc_step(model, tick, cx, cy, u, mean, pos, vel, vehicles, done_tick, device
     return a
 
 
+def _need_queue(L):
+    if not hasattr(L, "mpcmmd_mpc_queue_reset"):
+        raise NativeError(f"{LIB_PATH} has no mpcmmd_mpc_queue_reset (built before the scene queue existed): "
+                          "rebuild it")
+
+
+def mpc_queue(tick, ticks_per_episode, flags, keys, v_des, scene, ltick, done, key, slot_v_des, sched, count,
+              device=None):
+    """One lockstep tick of the scene queue's rule over E slots and N scenes:
+    mpcmmd_mpc_queue_host (device None) or one k_mpc_queue launch on GPU ``device``
+    (mpcmmd_mpc_queue_device).  flags [E, 4] is the step's log_i row, keys and v_des [N] the scene
+    table's; scene, ltick, done, key, slot_v_des [E], sched [N, 4] and count [2] are the state before
+    the tick.  Nothing given is modified; returns a dict of the state after it plus fresh and
+    idx_mpc [E]."""
+    L = lib()
+    _need_queue(L)
+    i32 = lambda a, *sh: np.ascontiguousarray(np.asarray(a, np.int64).astype(np.int32).reshape(*sh))
+    fl, kt = i32(flags, -1, 4), i32(keys, -1)   # keys wrap to 32 bits
+    E, N = fl.shape[0], kt.shape[0]
+    vt = np.ascontiguousarray(np.asarray(v_des, np.float32).reshape(N))
+    out = dict(scene=i32(scene, E).copy(), ltick=i32(ltick, E).copy(), done=i32(done, E).copy(),
+               fresh=np.full(E, -7, np.int32), key=np.asarray(key, np.uint32).reshape(E).copy(),
+               idx_mpc=np.full(E, -7, np.int32), slot_v_des=np.asarray(slot_v_des, np.float32).reshape(E).copy(),
+               sched=i32(sched, N, 4).copy(), count=i32(count, 2).copy())
+    ip = C.POINTER(C.c_int32)
+    io = MpcQueueIO(E, N, int(ticks_per_episode), int(tick), fl.ctypes.data_as(ip), kt.ctypes.data_as(ip), _fptr(vt),
+                    *[out[k].ctypes.data_as(ip) for k in ("scene", "ltick", "done", "fresh")],
+                    out["key"].ctypes.data_as(C.POINTER(C.c_uint32)), out["idx_mpc"].ctypes.data_as(ip),
+                    _fptr(out["slot_v_des"]), out["sched"].ctypes.data_as(ip), out["count"].ctypes.data_as(ip))
+    if device is None:
+        check(L.mpcmmd_mpc_queue_host(C.byref(io)))
+    else:
+        check(L.mpcmmd_mpc_queue_device(int(device), C.byref(io)))
+    return out
+
+
 class Mpc(_Episodes):
     """Owns one mpcmmd_mpc: the chained closed loop of a static / dynamic
     ``handle`` on ``model`` for up to ``max_ticks`` ticks.  ``reset`` takes the
@@ -1154,6 +1218,52 @@ class Mpc(_Episodes):
         out = np.zeros((max(int(ticks), 0), self.E, self.model.num_obs, 6), np.float32)
         check(self._L.mpcmmd_mpc_vehicle_log(self._p, int(ticks), _fptr(out)))
         return out
+
+    def queue_reset(self, slots, ticks_per_episode, pos, vel, vehicles, mean, cov, v_des, keys, planned=None):
+        """mpcmmd_mpc_queue_reset: the scene table of a campaign -- pos [N, 2]
+        float64, vel [N, 3], vehicles [N, num_obs, 4], mean [N, 8], v_des [N], keys [N] and, with the
+        planned policy on, planned = dict(target=[N, O, 2], acc=[N, O, 2]) -- through ``slots`` slots
+        of at most ``ticks_per_episode`` ticks per scene.  Scenes 0..min(N, slots)-1 start at once."""
+        _need_queue(self._L)
+        pos = np.ascontiguousarray(np.asarray(pos, np.float64).reshape(-1, 2))
+        N, O = pos.shape[0], self.model.num_obs
+        f = lambda a, *sh: np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32), sh))
+        kk = np.ascontiguousarray(np.asarray(keys, np.int64).reshape(N).astype(np.int32))
+        veh = f(np.asarray(vehicles, np.float32).reshape(N, O, 4), N, O, 4)
+        arrs = [f(np.asarray(vel, np.float32).reshape(N, 3), N, 3), veh, f(np.asarray(mean, np.float32).reshape(-1, 8), N, 8),
+                f(np.asarray(v_des, np.float32).reshape(-1), N)]
+        pl = [None, None]
+        if planned is not None:
+            pl = [f(np.asarray(planned["target"], np.float32).reshape(N, O, 2), N, O, 2),
+                  f(np.asarray(planned["acc"], np.float32).reshape(N, O, 2), N, O, 2)]
+        sc = MpcScenes(N, pos.ctypes.data_as(C.POINTER(C.c_double)), *[_fptr(a) if a.size else None for a in arrs],
+                       kk.ctypes.data_as(C.POINTER(C.c_int32)), *[None if a is None or not a.size else _fptr(a) for a in pl])
+        check(self._L.mpcmmd_mpc_queue_reset(self._p, int(slots), int(ticks_per_episode), C.byref(sc),
+                                             _fptr(f(np.asarray(cov, np.float32).reshape(64), 64))))
+        self.E = self._handle._G = int(slots)
+        self.N = N
+
+    def queue_run(self, cost, tick_begin, count, cov):
+        """mpcmmd_mpc_queue_run: ``count`` lockstep ticks from ``tick_begin``, all enqueued."""
+        _need_queue(self._L)
+        check(self._L.mpcmmd_mpc_queue_run(self._p, COST[cost], int(tick_begin), int(count),
+                                           _fptr(np.ascontiguousarray(np.asarray(cov, np.float32).reshape(64)))))
+
+    def queue_status(self):
+        """mpcmmd_mpc_queue_status: synchronises; (started, finished) scenes."""
+        _need_queue(self._L)
+        a, b = C.c_int32(), C.c_int32()
+        check(self._L.mpcmmd_mpc_queue_status(self._p, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def queue_log(self):
+        """mpcmmd_mpc_queue_log: sched [N, 4] = slot, first lockstep tick, ticks run, end reason
+        (``QUEUE_SCHED``, ``QUEUE_REASONS``)."""
+        _need_queue(self._L)
+        N = getattr(self, "N", 0)
+        out = np.zeros((max(N, 1), 4), np.int32)
+        check(self._L.mpcmmd_mpc_queue_log(self._p, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out[:N]
 
     def validate(self, rollouts, alpha=0.98, sigma=(), overlap=True):
         """mpcmmd_mpc_validate: from the next ``reset`` on, every tick of ``run`` also computes the

@@ -261,6 +261,101 @@ class CEM:
         out["done_tick"] = done
         return out
 
+    # ------------------------------------------------------------------
+    def open_campaign(self, vehicles, starts, ticks_per_episode, max_lockstep_ticks, *, slots=None, v_des=15.0,
+                      keys=None, key_base=0, planned=None, goal_x=200.0, mean=None, cov=None, dt=0.15):
+        """The context of a campaign after its queue reset (``run_campaign`` says what the arguments
+        mean): ``(ctx, cov)``, for callers that drive ``ctx.queue_run`` / ``queue_status`` themselves
+        and read the result with ``campaign_result``.  Close ``ctx`` before the handle."""
+        h, cfg, f32 = self._h, self._cfg, np.float32
+        starts = np.asarray(starts, np.float64)
+        starts = starts.reshape(-1, starts.shape[-1])
+        N = starts.shape[0]
+        E = h.max_configs if slots is None else int(slots)
+        if N < 1:
+            raise ValueError("run_campaign: at least one scene")
+        if E < 1 or E > h.max_configs:
+            raise ValueError(f"{E} slots: the handle holds 1..{h.max_configs} (CEM(..., max_configs=))")
+        veh = np.ascontiguousarray(np.asarray(vehicles, f32).reshape(N, self.num_obs, 4))
+        vxy = starts[:, 2:4].astype(f32)
+        psi = starts[:, 4].astype(f32) if starts.shape[1] > 4 else np.arctan2(vxy[:, 1].astype(np.float64),
+                                                                               vxy[:, 0].astype(np.float64)).astype(f32)
+        vel = np.concatenate([vxy, psi[:, None]], 1)
+        mean = np.array([15.0] * 4 + [0.0] * 4, f32) if mean is None else np.asarray(mean, f32)
+        mean = np.broadcast_to(mean.reshape(-1, 8), (N, 8))
+        cov = np.diag([20.0] * 4 + [100.0] * 4).astype(f32) if cov is None else np.asarray(cov, f32).reshape(8, 8)
+        keys = (int(key_base) + 100003 * np.arange(N)) if keys is None else np.asarray(keys, np.int64).reshape(N)
+        pl = None
+        if planned is not None:
+            if set(planned) - {"target", "acc"} or "target" not in planned:
+                raise TypeError("run_campaign: planned takes target and acc")
+            acc = planned.get("acc")
+            pl = dict(target=np.asarray(planned["target"], f32).reshape(N, self.num_obs, 2),
+                      acc=np.zeros((N, self.num_obs, 2), f32) if acc is None else
+                      np.asarray(acc, f32).reshape(N, self.num_obs, 2))
+        model = _native.MpcModel(cfg, cov, _native.pop0_normals(cfg), goal_x=goal_x, dt=dt, a_obs=self.a_obs,
+                                 b_obs=self.b_obs)
+        ctx = _native.Mpc(h, model, max(int(max_lockstep_ticks), 1))
+        try:
+            if pl is not None:   # turns the policy on; the queue reads its own table, not these staged rows
+                ctx.plan_vehicles(pl["target"][:1], pl["acc"][:1])
+            ctx.queue_reset(E, ticks_per_episode, starts[:, :2], vel, veh, mean, cov,
+                            np.broadcast_to(np.asarray(v_des, f32).reshape(-1), (N,)), keys, planned=pl)
+        except Exception:
+            ctx.close()
+            raise
+        ctx.planned = pl is not None
+        return ctx, cov
+
+    @staticmethod
+    def campaign_result(ctx, ticks, ticks_per_episode):
+        """The per-scene arrays of a campaign whose first ``ticks`` lockstep ticks were enqueued."""
+        from .campaign import cut, lockstep_ticks
+        sched = ctx.queue_log()
+        log = ctx.log(ticks)
+        log.pop("done_tick")   # the slots' words; the scenes' come from the schedule
+        if ctx.planned:
+            log["veh"] = ctx.vehicle_log(ticks)
+        out = cut(log, sched, ticks_per_episode)
+        started, finished = ctx.queue_status()
+        out.update(sched=sched, lockstep_ticks=lockstep_ticks(sched), started=started, finished=finished)
+        return out
+
+    def run_campaign(self, cost, vehicles, starts, ticks_per_episode, *, slots=None, max_lockstep_ticks=None,
+                     chunk=None, **kw):
+        """N closed-loop scenes through ``slots`` slots (default: ``max_configs``) of the chained loop
+        (DESIGN.md section 25): a slot whose episode ends -- a collision, the goal, or
+        ``ticks_per_episode`` ticks -- is refilled on the GPU with the next scene at once, so no solve
+        works on a finished episode while scenes are left.  vehicles [N, num_obs, 4], starts [N, 4 or
+        5], v_des a scalar or [N], keys [N] (default key_base + 100003 i), planned = dict(target=[N,
+        num_obs, 2], acc=None), goal_x, mean, cov, dt as ``run_episodes`` takes them for E episodes.
+        Every scene's episode equals ``run_episodes`` of that scene alone, bit for bit.
+
+        Runs ``chunk`` lockstep ticks at a time (default: ticks_per_episode), reading the two
+        counters in between, until every scene has finished or ``max_lockstep_ticks`` (default:
+        (ceil(N / slots) + 1) ticks_per_episode, which always suffices) are spent.  Returns per-scene
+        arrays cut from the lockstep log: log_d [ticks_per_episode, N, 2], log_f, log_i, cx, cy, mean
+        (and veh with the planned policy) in ``run_episodes``' layout, the rows after a scene's end
+        repeating its last row; end_tick, end_reason (``_native.QUEUE_REASONS``) and done_tick [N];
+        the raw sched [N, 4]; lockstep_ticks, started and finished."""
+        Tp = int(ticks_per_episode)
+        N = np.asarray(starts, np.float64).reshape(-1, np.shape(starts)[-1]).shape[0]
+        E = self._h.max_configs if slots is None else int(slots)
+        budget = (-(-N // max(E, 1)) + 1) * Tp if max_lockstep_ticks is None else int(max_lockstep_ticks)
+        chunk = Tp if chunk is None else max(int(chunk), 1)
+        ctx, cov = self.open_campaign(vehicles, starts, Tp, budget, slots=slots, **kw)
+        try:
+            k = 0
+            while k < budget:
+                c = min(chunk, budget - k)
+                ctx.queue_run(cost, k, c, cov)
+                k += c
+                if ctx.queue_status()[1] >= N:
+                    break
+            return self.campaign_result(ctx, k, Tp)
+        finally:
+            ctx.close()
+
     @property
     def handle(self):
         """The underlying native handle (stage access, streams, profiling)."""

@@ -52,6 +52,15 @@ collision probability count_pos[obs] / R, the mean count / R (the reference's
 coll_* metric) and the mean validated CVaR of the obstacle cost beside the mean
 of the solver's own cost_obs.
 
+With ``--slots E`` and more episodes than slots the run is a campaign
+(``CEM.run_campaign``): the N scenes go through E slots of
+the chained loop, a slot refilled on the GPU as soon as its episode ends, so no
+solve works on a finished episode while scenes are left.  The lines and the
+files are the same, now over N scenes (every scene's rows equal those of the
+scene run alone; the rows after a scene's end repeat its last row), and one more
+line gives the lockstep ticks the campaign took.  The chained route only, and
+without ``--validate``.
+
 The episode runner is a parameter of ``closed_loop`` (``run=``), so the
 accounting is testable without a GPU.
 """
@@ -114,6 +123,19 @@ def starts_of(variant, episodes):
 
 def _run(prob, cost, vehicles, starts, ticks, **kw):
     return prob.run_episodes(cost, vehicles, starts, ticks, **kw)
+
+
+def campaign_runner(slots, log=print):
+    """A ``run=`` of ``closed_loop`` that puts the scenes through ``slots`` slots (``CEM.run_campaign``)."""
+    def run(prob, cost, vehicles, starts, ticks, chained=True, device_step=None, validate=None, **kw):
+        if chained is not True or validate is not None:
+            raise ValueError("a campaign (--slots) runs on the chained route, without --validate")
+        res = prob.run_campaign(cost, vehicles, starts, ticks, slots=slots, **kw)
+        n = np.asarray(res["done_tick"]).size
+        log(f"{cost}: campaign of {n} scenes through {slots} slots, {res['lockstep_ticks']} lockstep ticks "
+            f"({res['finished']} finished; {-(-n // slots) * int(ticks)} in batches of {slots})")
+        return res
+    return run
 
 
 def summarise(res):
@@ -194,6 +216,8 @@ def parse_args(argv=None):
     ap.add_argument("--variant", default="static", choices=["static", "dynamic"])
     ap.add_argument("--episodes", type=int, default=8)
     ap.add_argument("--ticks", type=int, default=100)
+    ap.add_argument("--slots", type=int, default=None, metavar="E",
+                    help="with more episodes than E: a campaign through E slots, refilled on the GPU as episodes end")
     ap.add_argument("--costs", nargs="+", default=list(COSTS), choices=sorted(COSTS))
     ap.add_argument("--host-step", action="store_true",
                     help="solve tick by tick and step the world on the host (mpcmmd_mpc_step_host)")
@@ -241,10 +265,11 @@ def main(argv=None):
     from .cem import CEM
     prob = CEM(a.num_reduced, a.num_obs, a.noise_level, a.num_prime, a.noise, a.acc_const_noise, a.steer_const_noise,
                num_batch=a.num_batch, variant=a.variant, maxiter_cem=a.maxiter_cem, seed=a.seed,
-               max_configs=a.episodes)
+               max_configs=a.episodes if a.slots is None else min(a.slots, a.episodes))
     vehicles, keys = scenario(a.variant, a.episodes, a.num_obs)
+    run = campaign_runner(a.slots) if a.slots is not None and a.episodes > a.slots else None
     try:
-        closed_loop(prob, a.costs, vehicles, starts_of(a.variant, a.episodes), a.ticks, a.out, keys=keys,
+        closed_loop(prob, a.costs, vehicles, starts_of(a.variant, a.episodes), a.ticks, a.out, run=run, keys=keys,
                     v_des=a.v_des, goal_x=a.goal_x, chained=not a.host_step, device_step=None, **validation_of(a),
                     **planned_of(a))
     finally:
