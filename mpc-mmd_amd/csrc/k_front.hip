@@ -293,7 +293,10 @@ __global__ __launch_bounds__(256) void k_front(Params p, int t) {
   const float* xob = sPath + 2 * p.P;
   const float* yob = xob + p.O * kN;
   float obsx[kNv], obsy[kNv];
-  unsigned long long nonfin = 0;  // bit 2 o + q: d_obs of the guess at (o, point q) is not finite
+  // bit 2 o + q: d_obs of the guess at (o, point q) is not finite.  The flags restate the reference's NaN bound
+  // (comp_d_obs_prev) but cannot change an output: such a d_obs makes b_obs below inf or NaN, A_obs^T b_obs and
+  // with it every coefficient NaN, so every obstacle residual is NaN whatever the shifted flag says
+  unsigned long long nonfin = 0;
   if (kDet) {
     double sox[kNv], soy[kNv];
 #pragma unroll
@@ -412,8 +415,8 @@ __global__ __launch_bounds__(256) void k_front(Params p, int t) {
     if (!ok) continue;
     const int j = (q == 0 ? t0 : t1) - 1;
     const float ac_ub = y[q], ac_lb = -y[q];
-    const float s_ub = fmaxf(0.0f, -ac_ub + y_ub);
-    const float s_lb = fmaxf(0.0f, -ac_lb + mlb);
+    const float s_ub = max_nan(0.0f, -ac_ub + y_ub);  // jnp.maximum: a NaN y gives a NaN slack
+    const float s_lb = max_nan(0.0f, -ac_lb + mlb);
     rl_ub[q] = (ac_ub - y_ub) + s_ub;
     rl_lb[q] = (ac_lb - mlb) + s_lb;
     sl[j] = s_ub;
